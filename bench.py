@@ -2,7 +2,13 @@
 """bench.py -- guided Msamples/s (+ image MSE vs ground truth) of the MI355X-native path-guiding integrator.
 
 Default workload = the one BASELINE.json's metric is quoted on: veach-ajar 1920x1080, the scene
-file's max_depth 13, the 2^(k+2) spp schedule (scenes/veach-ajar/scene.xml, main.py:170).  Phases:
+file's max_depth 13, the 2^(k+2) spp schedule (scenes/veach-ajar/scene.xml, main.py:170).
+
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does what `value` needs and nothing else: train, W warm-up
+steps, K timed steps, the line (value, ms_per_step = milliseconds of one timed step).  Everything below that is not `train`
+or `steps` -- mse, cpu_baseline, kernels_synthetic, roofline, kernels, traffic, the other configs, the whole schedule, the
+1-spp and two-in-flight variants, the full record -- runs with --full only.  --dump-outputs DIR writes what the last timed
+step computed (dump_step_outputs), in either form.  Phases:
 
   train   iterations 0 .. train_iters-1 are really rendered (4, 8, 16 ... spp; accumulators summed
           over the ranks and the SD-tree refined after each) and timed per iteration ->
@@ -56,10 +62,11 @@ config.c2_* / c3_* / c5_*: BASELINE configs[1], [2], [4] timed for a few steps i
 OUTPUT: stdout carries exactly ONE line -- compact_record(): < 6 KB of strict JSON with the contract's keys, `roofline`, `cpu_baseline`,
 kernel name -> ms per step, and the flat figures named below; it is the last thing the process writes (the driver could not
 parse round 5's 22.9 KB line).  The FULL record (every note, the per-kernel counter tables, kernels_synthetic, schedule, full_schedule)
-goes to --detail (default gpurun_out/bench_detail.json); a builder-run copy of it is committed per round under profiles/.
+goes to --detail (with --full, by default bench_detail.json in the folder detail_path() picks); a builder-run copy of it is committed
+per round under profiles/.
 
 `--synthetic` runs the renderer-free hot-path workload instead (seeded synthetic surface points).
-Launch:  python bench.py [--gpus N]      (N > 1 without WORLD_SIZE in the environment: this process starts N fresh
+Launch:  python bench.py [--gpus N] [--full]   (N > 1 without WORLD_SIZE in the environment: this process starts N fresh
                                           rank processes itself -- before anything touches the GPU -- and relays rank 0's line)
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N
 """
@@ -104,8 +111,16 @@ SCENES = {  # film width, aspect (w, h), max_depth of the BASELINE config
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: the legs below (--full-schedule, --synthetic-kernels, "
+                         "--spp1, --cpu, --pmc-in-run, --phase-probe, --other-configs; each on by default as it says, 0 skips it), the "
+                         "instrumented pass, the per-kernel table, the roofline region, the image MSE and the full record (--detail).  "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, < 64 MB; "
+                         "dump_step_outputs says what): the same arguments give the same inputs, run after run")
     ap.add_argument("--scene", default="veach-ajar", choices=sorted(SCENES),
                     help="veach-ajar 1920x1080 max_depth 13 (BASELINE configs[3], the metric's scene; default), cornell-box "
                          "512x512 max_depth 8 (configs[1]), veach-mis 1280x720 max_depth 3 (configs[2]), torus 1920x1080 "
@@ -121,7 +136,7 @@ def parse():
                          "to the separate passes, tests/test_gpu_render.py); 0: one pass of --spp-per-pass samples per pixel (mi.render(spp=N))")
     ap.add_argument("--synthetic-kernels", type=int, default=None,
                     help="1: time the stand-alone entry points on SURVEY 8(d)'s S1 / S2 / S3 at their stated sizes and put the figures into "
-                         "`roofline` (s1_*, s2_*, s3_*); default: 1 at N = 1, 0 otherwise")
+                         "`roofline` (s1_*, s2_*, s3_*); default with --full: 1 at N = 1, 0 otherwise")
     ap.add_argument("--train-iters", type=int, default=6, help="iterations rendered to train the SD-tree (the configs say 8/10/12)")
     ap.add_argument("--shard", default="tiles", choices=["tiles", "passes"], help="N > 1: strong scaling by tiles (default) or weak by passes")
     ap.add_argument("--backend", default="auto", choices=["auto", "nccl", "gloo"],
@@ -132,17 +147,17 @@ def parse():
     ap.add_argument("--full-schedule", type=int, default=None,
                     help="1: after the steady-state steps, run the BASELINE config's WHOLE schedule through driver.run_guided_render "
                          "(veach-ajar: 12 iterations = 16380 spp, main.py:157-170, with main.py's stop-training rule :334-377) and "
-                         "report value_full_schedule_12it + the final image's MSE; default: 1 at N = 1, 0 otherwise")
-    ap.add_argument("--spp1", type=int, default=1, help="0: skip the leg that times 1-spp passes (value_spp1)")
-    ap.add_argument("--cpu", type=int, default=1, help="0: skip the cpu_baseline / MSE-equality leg")
+                         "report value_full_schedule_12it + the final image's MSE; default with --full: 1 at N = 1, 0 otherwise")
+    ap.add_argument("--spp1", type=int, default=None, help="0: skip the leg that times 1-spp passes (value_spp1; default: 1 with --full)")
+    ap.add_argument("--cpu", type=int, default=None, help="0: skip the cpu_baseline / MSE-equality leg (default: 1 with --full)")
     ap.add_argument("--pmc-in-run", type=int, default=None,
                     help="1: `roofline.traffic` is MEASURED in this run -- behind the timed regions, rank 0 starts two bounded child "
                          "processes, `rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE` (one counter per pass, nothing traced) around three "
                          "steps of the same configuration, and reads their counter tables; 0: the committed figures of "
-                         "profiles/pmc_traffic.json only (default: 1 for the default one-GPU line)")
+                         "profiles/pmc_traffic.json only (default: 1 for the default one-GPU line with --full)")
     ap.add_argument("--other-configs", type=int, default=None,
                     help="1: also time BASELINE configs[1], [2], [4] (cornell-box 512x512, veach-mis 1280x720, torus 1920x1080 depth 32) for a "
-                         "few steps each and put the figures into `config` (c2_/c3_/c5_*); default: 1 at N = 1 on the default scene")
+                         "few steps each and put the figures into `config` (c2_/c3_/c5_*); default with --full: 1 at N = 1 on the default scene")
     ap.add_argument("--exchange-overlap", type=int, default=0,
                     help="N > 1, full-schedule leg: 1 lets the accumulators' all-reduce (libpgsd's RCCL communicator) travel beside the image "
                          "collectives of torch.distributed's communicator; 0 (default) orders it ahead of them -- two communicators in flight at "
@@ -166,12 +181,26 @@ def parse():
                     help="1: behind the timed regions rank 0 runs the PROBE build of the library (libpgsd_phases.so, csrc/Makefile `probe`: "
                          "k_wave_shade with wave-clock stamps at its phase boundaries) as a child process for three steps and reports the "
                          "SD-tree calls' share of k_wave_shade in the region `value` is quoted on (roofline.value_region_sdtree_*); "
-                         "default: 1 for the default one-GPU line.  2: (internal) this process IS that child")
+                         "default: 1 for the default one-GPU line with --full.  2: (internal) this process IS that child")
     ap.add_argument("--detail", default=None,
-                    help="file the FULL record is written to (default gpurun_out/bench_detail.json); stdout carries one compact line, "
-                         "< 6 KB of strict JSON, and nothing else")
+                    help="file the FULL record is written to (with --full by default: bench_detail.json in the folder detail_path() "
+                         "picks; without --full only when given); stdout carries one compact line, < 6 KB of strict JSON, and nothing else")
     ap.add_argument("--no-compaction", action="store_true", help="(synthetic) mask dead lanes instead of compacting")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.synthetic:
+        ap.error("--dump-outputs writes the outputs of the render workload, not of --synthetic")
+    if not args.full:  # (a plain run measures the headline figure only: a leg asked for by itself needs --full)
+        for k in ("full_schedule", "synthetic_kernels", "other_configs", "pmc_in_run", "phase_probe", "spp1", "cpu"):
+            v = getattr(args, k)
+            if v and not (k == "phase_probe" and v == 2):  # (--phase-probe 2: the probe child of measure_sdtree_phase)
+                ap.error("--%s %s needs --full" % (k.replace("_", "-"), v))
+            setattr(args, k, v or 0)
+    if args.spp1 is None:
+        args.spp1 = 1
+    if args.cpu is None:
+        args.cpu = 1
     w, _, d = SCENES[args.scene]
     if args.res is None:
         args.res = 512 if args.synthetic else w
@@ -241,7 +270,7 @@ def measure_traffic_in_run(args, launches_per_step, timeout_s=90.0):
     child = [sys.executable if os.path.basename(sys.executable).startswith("python") else "python3", os.path.abspath(__file__),
              "--scene", args.scene, "--res", str(args.res), "--depth", str(args.depth), "--spp-per-pass", str(args.spp_per_pass),
              "--batched", str(args.batched), "--train-iters", str(args.train_iters), "--sort", str(args.sort),
-             "--in-flight", str(args.in_flight), "--steps", str(PMC_CHILD_STEPS), "--warmup", "1", "--cpu", "0", "--full-schedule", "0",
+             "--in-flight", str(args.in_flight), "--steps", str(PMC_CHILD_STEPS), "--warmup", "1", "--full", "--cpu", "0", "--full-schedule", "0",
              "--spp1", "0", "--other-configs", "0", "--synthetic-kernels", "0", "--pmc-in-run", "0", "--phase-probe", "0", "--detail", os.devnull]
     env = dict(os.environ, TMPDIR="/tmp")
     t0 = time.perf_counter()
@@ -667,6 +696,51 @@ def measure_sdtree_phase(args, timeout_s=120.0):
     return None, "the probe process printed no result"
 
 
+DUMP_LANES = 1 << 19   # lanes of the last step in radiance_sample / valid_sample / sample_lane
+DUMP_PIXELS = 1 << 21  # pixels in radiance_pixel_mean: every pixel of a 1920x1080 film; a seeded sample of a larger one
+DUMP_SEED = 20251015
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_step_outputs(dirname, L, valid, passes, spp):
+    """--dump-outputs: what the last timed step computed, as a caller of PathGuidingIntegrator.sample() receives it.  L (3, N)
+    float32 and valid (N,) uint8 are the latest launch's, lanes pixel-major over this rank's pixels (lane = pixel * passes +
+    pass); the step is the launch's last `spp` passes.  Writes, < DUMP_MAX_BYTES in all:
+      radiance_pixel_mean (P, 3) float32  the step's mean radiance of each pixel (summed in float64): every pixel, up to
+                                          DUMP_PIXELS; beyond that a seeded sample of them, named by pixel_index (P,) float64
+      radiance_sample     (S, 3) float32  L of S = min(DUMP_LANES, lanes of the step) seeded lanes
+      valid_sample        (S,) float32    valid of those lanes, 0 / 1
+      sample_lane         (S,) float64    their index in the step: pixel * spp + sample
+    Returns {name: bytes}."""
+    import numpy as np
+    import torch
+
+    npix = L.shape[1] // passes
+    Ls = L.reshape(3, npix, passes)[:, :, passes - spp:]
+    vs = valid.reshape(npix, passes)[:, passes - spp:]
+    rng = np.random.default_rng(DUMP_SEED)
+    out = {}
+    mean = Ls.sum(dim=2, dtype=torch.float64) / spp
+    if npix > DUMP_PIXELS:
+        pix = np.sort(rng.choice(npix, DUMP_PIXELS, replace=False))
+        mean = mean[:, torch.from_numpy(pix).to(mean.device)]
+        out["pixel_index"] = pix.astype(np.float64)
+    out["radiance_pixel_mean"] = mean.t().float().cpu().numpy()
+    n = npix * spp
+    lanes = np.sort(rng.choice(n, min(DUMP_LANES, n), replace=False))
+    idx = torch.from_numpy(lanes).to(L.device)
+    out["radiance_sample"] = Ls.reshape(3, n)[:, idx].t().cpu().numpy()
+    out["valid_sample"] = vs.reshape(n)[idx].float().cpu().numpy()
+    out["sample_lane"] = lanes.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+    return {name: a.nbytes for name, a in out.items()}
+
+
 # ------------------------------------------------------------------------------------------------
 def run_render(args):
     import numpy as np
@@ -747,10 +821,11 @@ def run_render(args):
         per_iter.append({"iteration": k, "spp": iter_spp, "render_ms": round(1e3 * (t1 - t0), 2),
                          "exchange_refine_ms": round(1e3 * (t2 - t1), 2)})
     last_spp = 2 ** (args.train_iters + 1)
-    sums = all_reduce_sums(integ.sumL, integ.sumL2) if world > 1 else (integ.sumL, integ.sumL2)
     mse_train, mse_note = (None, None)
-    if rank == 0:
-        mse_train, mse_note = image_mse(sums[0].cpu().numpy(), last_spp, W, H, args.scene)
+    if args.full:
+        sums = all_reduce_sums(integ.sumL, integ.sumL2) if world > 1 else (integ.sumL, integ.sumL2)
+        if rank == 0:
+            mse_train, mse_note = image_mse(sums[0].cpu().numpy(), last_spp, W, H, args.scene)
     guided = [p for p in per_iter if p["iteration"] >= 2]
     t_guided = sum(p["render_ms"] + p["exchange_refine_ms"] for p in guided) * 1e-3
     full_schedule = (npix * sum(p["spp"] for p in guided) / t_guided / 1e6) if guided and t_guided > 0 else None
@@ -759,28 +834,93 @@ def run_render(args):
     integ.setIteration(k, False)
 
     # (tiles: every rank traces the same passes of its own pixels; passes: rank r takes every world-th group of passes)
-    queue = StepQueue(lambda n, sd: integ.sample(ws, IndependentSampler(n, sd, batched=batched)), args.spp_per_pass, group,
-                      cumm + (0 if tiles else rank * args.spp_per_pass), 1 if (tiles or world == 1) else world)
+    last = {}  # --dump-outputs: what the latest launch returned
+
+    def launch(n, sd):
+        L, valid, _ = integ.sample(ws, IndependentSampler(n, sd, batched=batched))
+        if args.dump_outputs:
+            last.update(L=L, valid=valid, passes=n)
+    queue = StepQueue(launch, args.spp_per_pass, group, cumm + (0 if tiles else rank * args.spp_per_pass), 1 if (tiles or world == 1) else world)
     step, flush = queue.step, queue.flush
     seed = [0]  # (the later legs count their own seeds on from the queue's: set where they start)
 
-    # one instrumented pass for the byte model (depth counters add atomics: not timed)
-    tree.enableDepthCounters(True)
-    tree.readDepthCounters(reset=True)
-    rec_before = int(tree.exportAccumulators()[0][0])  # records counted at the KD root so far
+    # one instrumented pass for the byte model (depth counters add atomics: not timed).  A plain run traces the same pass
+    # without the counters, so that the timed steps trace the same passes with and without --full.
+    if args.full:
+        tree.enableDepthCounters(True)
+        tree.readDepthCounters(reset=True)
+        rec_before = int(tree.exportAccumulators()[0][0])  # records counted at the KD root so far
     step()
     flush()  # (one step's passes by themselves: the counters below are per step)
-    dc = tree.readDepthCounters(reset=True)
-    tree.enableDepthCounters(False)
-    records_per_pass = int(tree.exportAccumulators()[0][0]) - rec_before
-    live = tree.renderLiveCounts(args.depth)  # paths alive after each bounce of that pass
-
-    tree.enableKernelTiming(True)
+    if args.full:
+        dc = tree.readDepthCounters(reset=True)
+        tree.enableDepthCounters(False)
+        records_per_pass = int(tree.exportAccumulators()[0][0]) - rec_before
+        live = tree.renderLiveCounts(args.depth)  # paths alive after each bounce of that pass
+        tree.enableKernelTiming(True)
     for _ in range(args.warmup):
         step()
     flush()
-    tree.readKernelTiming(reset=True)
+    if args.full:
+        tree.readKernelTiming(reset=True)
     elapsed = timed_steps(step, args.steps, 0, world, flush)
+    paths_per_step = npix * args.spp_per_pass * (1 if (tiles or world == 1) else world)  # all ranks
+    value = paths_per_step * args.steps / elapsed / 1e6
+    step_ms = 1e3 * elapsed / args.steps
+    if args.dump_outputs and rank == 0:
+        wrote = dump_step_outputs(args.dump_outputs, last["L"], last["valid"], last["passes"], args.spp_per_pass)
+        print(f"[bench] outputs of the last step: {sum(wrote.values())} bytes in {len(wrote)} files under {args.dump_outputs}",
+              file=sys.stderr, flush=True)
+    last.clear()
+    film = f"{W}x{H}"
+    what = {"cornell-box": "built-in scene (Mitsuba cornell-box parameters), no textures",
+            "veach-mis": "built-in scene (scenes/veach-mis/scene.xml parameters: 3 sphere lamps, 4 Beckmann rough-conductor "
+                         "plates, diffuse floor and wall)",
+            "torus": "built-in scene (scenes/torus/scene.xml parameters; its five meshes, 23614 triangles, from the package "
+                     "data torus_meshes.npz behind a BVH: diffuse donut in a frosted-glass case, aluminium brackets, "
+                     "directional light)",
+            "veach-ajar": "built-in scene (scenes/veach-ajar/scene.xml parameters; its 15 OBJ meshes present in the reference's "
+                          "files, 4482 triangles with texture coordinates, and its three bitmap textures at full "
+                          "resolution (the JPG files' bytes in the package data veach_ajar.npz, decoded with PIL as load_xml does); checkerboard GGX floor, Beckmann door handle; "
+                          "the six teapot shapes are absent: their mesh files are missing from the reference's files)"}[args.scene]
+    workload = (f"{args.scene} {film}, max_depth {args.depth}, " +
+                (f"{args.spp_per_pass} one-sample training passes (main.py:192, 218) per step in one batched launch"
+                 if batched else f"one {args.spp_per_pass}-spp pass per step") + " (the whole film"
+                + (", sharded by interleaved 4-row bands over the ranks" if tiles else (", per GPU" if world > 1 else ""))
+                + f"), guided iteration {k} (SD-tree trained by rendering iterations 0-{k - 1}, "
+                f"{cumm} spp); full PathGuidingIntegrator.sample(): camera rays, NEE, "
+                "BSDF/SD-tree MIS, record list, post-process + splat; " + what)
+    head = {"metric": f"Msamples/s guided, {args.scene} {film} max_depth {args.depth}", "value": round(value, 3), "unit": "Msamples/s",
+            "n_gpus": args.n_devices, "ranks": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(step_ms, 4),
+            "higher_is_better": True, "scaling": "strong" if (tiles or world == 1) else "weak", "vs_baseline": None, "dtype": "f32",
+            "data": "no dataset: the reference's scene (parameters, meshes and textures packaged from its scene files), sampler "
+                    "streams seeded per pass, SD-tree trained inside the run"}
+    head_config = {"pixels_this_rank": my_pixels, "pixels_per_rank_min": int(pix_min), "pixels_per_rank_max": int(pix_max),
+                   "spp_per_pass": args.spp_per_pass,
+                   "paths_per_step": paths_per_step, "kd_nodes": stats.n_kd_nodes, "kd_leaves": stats.n_kd_leaves,
+                   "quad_records": stats.n_quad_records, "mean_kd_leaf_depth": round(stats.mean_kd_leaf_depth, 3),
+                   "mean_quad_leaf_depth": round(stats.mean_quad_leaf_depth, 3),
+                   "pass_spp": 1 if batched else args.spp_per_pass, "passes_per_launch": (args.spp_per_pass if batched else 1) * group,
+                   "steps_per_launch": group, "jump_bits": int(stats.jump_bits), "kd_grid_bits": int(stats.kd_grid_bits),
+                   "bytes_jump_tables": int(stats.bytes_jump_tables)}
+    head_extra = {"library": os.path.relpath(N_LIB_PATH, ROOT), "source_hash": SRC_HASH, "exchange": exchange,
+                  "rccl_ranks": None if rccl_seen is None else rccl_seen[0], "rccl_rank": None if rccl_seen is None else rccl_seen[1]}
+
+    def leave():
+        """every rank lets go of the library's communicator at the same point (nothing collective follows; a rank must not sit
+        in ncclCommDestroy at interpreter exit while the others are already gone)"""
+        if world > 1:
+            torch.cuda.synchronize()
+            if exchange.startswith("pg_allreduce"):
+                tree.commDestroy()
+            dist.barrier()
+
+    if not args.full:  # a plain run: the headline figure and nothing else
+        leave()
+        if world > 1:
+            dist.destroy_process_group()
+        return None if rank != 0 else dict(head, config=dict(workload=workload, **head_config),
+                                          roofline=None, cpu_baseline=None, kernels={}, extra=head_extra)
     kt = tree.readKernelTiming(reset=True)
     # ---- the roofline region: the SAME passes again with the SD-tree calls of a bounce in a kernel of their own
     # (pg_render_stages(2): k_wave_guide; in the region above they are part of k_wave_shade, where they cannot be timed
@@ -843,20 +983,12 @@ def run_render(args):
     if args.full_schedule:
         full = full_schedule_leg(args, integ, ws, (rank, world, 4) if tiles else None, reduce_fn, W, H)
 
-    if world > 1:
-        # every rank lets go of the library's communicator at the same point (nothing collective follows; a rank must
-        # not sit in ncclCommDestroy at interpreter exit while the others are already gone)
-        torch.cuda.synchronize()
-        if exchange.startswith("pg_allreduce"):
-            tree.commDestroy()
-        dist.barrier()
+    leave()
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()
         return None
 
-    paths_per_step = npix * args.spp_per_pass * (1 if (tiles or world == 1) else world)  # all ranks
-    value = paths_per_step * args.steps / elapsed / 1e6
     # instrumented pass -> algorithmic bytes per pass on this rank
     # SD-tree queries: 16 B per KD level + 20 B per quadtree level; splat: per record 16*D_kd + 4 + 48 + 12 per quadtree
     # level and descent, priced with the measured mean depths over the records actually kept
@@ -871,7 +1003,6 @@ def run_render(args):
     # (the kernel table is per STEP: with group > 1 a launch of pg_render_pass holds the passes of several steps)
     passes = max(kt.passes, 1) if group == 1 else max(args.steps, 1)
     wave = kt.trace_launches > 0  # the split pipeline of pg_render_wave.hip ran (mesh scenes, or --split-pipeline)
-    step_ms = 1e3 * elapsed / args.steps
 
     def kern(ms, launches, alg_bytes_per_pass=None):
         per_pass = launches / passes
@@ -932,17 +1063,6 @@ def run_render(args):
     kernels["k_finish"] = kern(kt.finish_ms, passes)
     slowest = max((n for n in kernels if kernels[n].get("region") != "roofline"), key=lambda n: kernels[n]["ms_per_step"])
     cfg_key = f"{args.scene} res={args.res} depth={args.depth} spp={args.spp_per_pass}"
-    film = f"{W}x{H}"
-    what = {"cornell-box": "built-in scene (Mitsuba cornell-box parameters), no textures",
-            "veach-mis": "built-in scene (scenes/veach-mis/scene.xml parameters: 3 sphere lamps, 4 Beckmann rough-conductor "
-                         "plates, diffuse floor and wall)",
-            "torus": "built-in scene (scenes/torus/scene.xml parameters; its five meshes, 23614 triangles, from the package "
-                     "data torus_meshes.npz behind a BVH: diffuse donut in a frosted-glass case, aluminium brackets, "
-                     "directional light)",
-            "veach-ajar": "built-in scene (scenes/veach-ajar/scene.xml parameters; its 15 OBJ meshes present in the reference "
-                          "mount, 4482 triangles with texture coordinates, and its three bitmap textures at full "
-                          "resolution (the JPG files' bytes in the package data veach_ajar.npz, decoded with PIL as load_xml does); checkerboard GGX floor, Beckmann door handle; "
-                          "the six teapot shapes are absent: their mesh files are missing from the reference mount)"}[args.scene]
     # ---- `traffic`, measured in this run where that is possible (--pmc-in-run): the default line of one GPU, the wavefront
     # pipeline with its roofline region; otherwise, and whenever the counter passes fail, the committed figures ----
     traffic_source, traffic_in_run_note = "committed", None
@@ -1119,35 +1239,18 @@ def run_render(args):
     if args.other_configs and world == 1:
         other = other_configs_leg(local_rank)
     refine_ms_iters = [p["exchange_refine_ms"] for p in per_iter]
-    out = {
-        "metric": f"Msamples/s guided, {args.scene} {film} max_depth {args.depth}", "value": round(value, 3), "unit": "Msamples/s",
-        "n_gpus": args.n_devices, "ranks": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(step_ms, 4),
-        "higher_is_better": True, "scaling": "strong" if (tiles or world == 1) else "weak", "vs_baseline": None, "dtype": "f32",
-        "data": "no dataset: the reference's scene (parameters, meshes and textures packaged from its scene files), sampler "
-                "streams seeded per pass, SD-tree trained inside the run", "value_full_schedule": None if full_schedule is None else round(full_schedule, 3),
+    out = dict(head, **{
+        "value_full_schedule": None if full_schedule is None else round(full_schedule, 3),
         "value_spp1": None if spp1 is None else round(spp1, 3),
         "value_two_in_flight": None if two_in_flight is None else round(two_in_flight, 3),
         "value_full_schedule_12it": None if full is None else full["value"], "mse_vs_gt_full_schedule": None if full is None else full["mse_vs_gt"],
         "full_schedule": full,
         "mse_vs_gt": mse_train, "mse_vs_gt_small": mse_small, "mse_vs_gt_cpu": mse_small_cpu,
         "mse_equal": None if mse_small is None else bool(mse_small == mse_small_cpu),
-        "config": {"workload": f"{args.scene} {film}, max_depth {args.depth}, " +
-                               (f"{args.spp_per_pass} one-sample training passes (main.py:192, 218) per step in one batched launch"
-                                if batched else f"one {args.spp_per_pass}-spp pass per step") + " (the whole film"
-                               + (", sharded by interleaved 4-row bands over the ranks" if tiles else (", per GPU" if world > 1 else ""))
-                               + f"), guided iteration {k} (SD-tree trained by rendering iterations 0-{k - 1}, "
-                               f"{cumm} spp); full PathGuidingIntegrator.sample(): camera rays, NEE, "
-                               "BSDF/SD-tree MIS, record list, post-process + splat; " + what,
-                   "pixels_this_rank": my_pixels, "pixels_per_rank_min": int(pix_min), "pixels_per_rank_max": int(pix_max),
-                   "spp_per_pass": args.spp_per_pass,
-                   "paths_per_step": paths_per_step, "kd_nodes": stats.n_kd_nodes, "kd_leaves": stats.n_kd_leaves,
-                   "quad_records": stats.n_quad_records, "mean_kd_leaf_depth": round(stats.mean_kd_leaf_depth, 3),
-                   "mean_quad_leaf_depth": round(stats.mean_quad_leaf_depth, 3),
+        "config": dict(workload=workload, **head_config, **{
                    "guided_tree_queries_per_pass": int(dc.quad_queries), "paths_alive_after_bounce": live,
                    "measured_D_kd": round(d_kd, 3), "measured_D_quad": round(d_q, 3),
                    # the schedule `value` is quoted on, and the same work launched the other ways (all in this run)
-                   "pass_spp": 1 if batched else args.spp_per_pass, "passes_per_launch": (args.spp_per_pass if batched else 1) * group,
-                   "steps_per_launch": group,
                    "value_one_launch_per_1spp_pass": None if spp1 is None else round(spp1, 3),
                    ("value_one_%dspp_pass_per_step" % args.spp_per_pass if batched else "value_batched_1spp_passes"):
                        None if multi_spp is None else round(multi_spp, 3),
@@ -1157,20 +1260,18 @@ def run_render(args):
                    "mse_equal_device_vs_cpu": None if mse_small is None else bool(mse_small == mse_small_cpu),
                    "mse_vs_gt_device_320": mse_small, "mse_vs_gt_cpu_320": mse_small_cpu,
                    "exchange_refine_ms_max_over_training": max(refine_ms_iters) if refine_ms_iters else None,
-                   "refine_ms_after_steps": round(1e3 * t_refine, 3), "jump_bits": int(stats.jump_bits),
-                   "kd_grid_bits": int(stats.kd_grid_bits), "bytes_jump_tables": int(stats.bytes_jump_tables), **other},
+                   "refine_ms_after_steps": round(1e3 * t_refine, 3), **other}),
         "roofline": roof, "cpu_baseline": cpu, "kernels": kernels, "kernels_synthetic": synth_detail,
         "schedule": {"note": "value_full_schedule = film pixels x spp of the trained iterations >= 2 / their wall time incl. "
                              "accumulator exchange and refine (main.py:159,394); mse_vs_gt = the last trained iteration's "
                              f"image ({last_spp} spp) vs the ground truth" + (": " + mse_note if mse_note else ""),
                      "iterations": per_iter, "trained_spp": cumm},
-        "extra": {"library": os.path.relpath(N_LIB_PATH, ROOT), "source_hash": SRC_HASH,
-                  "allreduce_ms": round(1e3 * t_allreduce, 3), "refine_ms": round(1e3 * t_refine, 3), "exchange": exchange,
+        "extra": dict(head_extra, **{
+                  "allreduce_ms": round(1e3 * t_allreduce, 3), "refine_ms": round(1e3 * t_refine, 3),
                   "accumulator_bytes": int(tree.accumulators().numel()) * 8,
                   "exchange_bytes": int(tree.packAccumulators().numel()) * 8,
-                  "exchange_format": "24 B per accumulator (two 52-bit pieces + count<<24 | top: pgsd.h pg_exchange_pack) instead of the 32-byte device layout",
-                  "rccl_ranks": None if rccl_seen is None else rccl_seen[0], "rccl_rank": None if rccl_seen is None else rccl_seen[1]},
-    }
+                  "exchange_format": "24 B per accumulator (two 52-bit pieces + count<<24 | top: pgsd.h pg_exchange_pack) instead of the 32-byte device layout"}),
+    })
     if world > 1:
         dist.destroy_process_group()
     return out
@@ -1848,17 +1949,18 @@ def detail_path():
         return os.path.join("/tmp", "bench_detail.json")
 
 
-def emit(out, detail=None):
-    """The full record to the detail file (never to stdout: the line the driver parses must be the only JSON there), then the
-    compact line as the LAST thing this process writes -- nothing follows it on stdout or stderr."""
-    path = detail_path() if detail is None else detail
-    try:
-        with open(path, "w") as f:
-            json.dump(_finite(out), f, allow_nan=False)
-            f.write("\n")
-        print(f"[bench] full record: {path}", file=sys.stderr, flush=True)
-    except OSError as e:
-        print(f"[bench] full record not written ({e})", file=sys.stderr, flush=True)
+def emit(out, detail=None, write_detail=True):
+    """The full record to the detail file (never to stdout: the line the driver parses must be the only JSON there; none when
+    not write_detail), then the compact line as the LAST thing this process writes -- nothing follows it on stdout or stderr."""
+    if write_detail:
+        path = detail_path() if detail is None else detail
+        try:
+            with open(path, "w") as f:
+                json.dump(_finite(out), f, allow_nan=False)
+                f.write("\n")
+            print(f"[bench] full record: {path}", file=sys.stderr, flush=True)
+        except OSError as e:
+            print(f"[bench] full record not written ({e})", file=sys.stderr, flush=True)
     sys.stderr.flush()
     sys.stdout.write(format_line(out) + "\n")
     sys.stdout.flush()
@@ -1878,7 +1980,7 @@ def main():
         return
     out = run_synthetic(args) if args.synthetic else run_render(args)
     if out is not None:
-        emit(out, args.detail)
+        emit(out, args.detail, write_detail=args.full or args.detail is not None)
 
 
 if __name__ == "__main__":

@@ -131,3 +131,87 @@ def test_the_launcher_relays_exactly_that_one_line(tmp_path):
     assert B.spawn_ranks([sys.executable, "-c", child, line], 2, relay=relay) == 0
     assert relay.getvalue() == line + "\n"
     _strict(relay.getvalue().rstrip("\n"))
+
+
+def _parse(B, monkeypatch, argv):
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    return B.parse()
+
+
+LEGS = ("full_schedule", "synthetic_kernels", "other_configs", "pmc_in_run", "phase_probe", "spp1", "cpu")
+
+
+def test_a_plain_run_measures_the_headline_only_and_full_runs_every_leg(monkeypatch, capsys):
+    """Without --full every leg is off and one asked for by itself is refused; --full gives each its default (all on at N = 1 on
+    the default scene), a leg switched off stays off; --steps below 1 is refused (ms_per_step is over the timed steps)."""
+    B = _bench()
+    a = _parse(B, monkeypatch, ["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert not a.full and a.steps == 7 and a.warmup == 3 and all(getattr(a, k) == 0 for k in LEGS) and a.dump_outputs is None
+    a = _parse(B, monkeypatch, ["--full"])
+    assert a.full and all(getattr(a, k) == 1 for k in LEGS)
+    a = _parse(B, monkeypatch, ["--full", "--cpu", "0", "--phase-probe", "0"])
+    assert a.cpu == 0 and a.phase_probe == 0 and a.spp1 == 1 and a.full_schedule == 1
+    assert _parse(B, monkeypatch, ["--phase-probe", "2"]).phase_probe == 2     # (the probe child: not a leg)
+    assert _parse(B, monkeypatch, ["--dump-outputs", "d"]).dump_outputs == "d"
+    for bad in (["--cpu", "1"], ["--full-schedule", "1"], ["--steps", "0"], ["--synthetic", "--dump-outputs", "d"]):
+        with pytest.raises(SystemExit):
+            _parse(B, monkeypatch, bad)
+    capsys.readouterr()
+
+
+def test_dump_step_outputs_takes_the_last_step_of_the_launch(tmp_path):
+    """dump_step_outputs on a launch of 3 steps x 4 passes (lane = pixel * passes + pass): the pixel means and the seeded lanes
+    are those of the last step's 4 passes; the same arrays give the same files; a 4K film stays under 64 MB."""
+    import numpy as np
+    import torch
+    B = _bench()
+    npix, spp, passes = 50, 4, 12
+    L = torch.arange(3 * npix * passes, dtype=torch.float32).reshape(3, npix * passes) * 0.25
+    valid = (torch.arange(npix * passes) % 3 != 0).to(torch.uint8)
+    wrote = B.dump_step_outputs(str(tmp_path / "a"), L, valid, passes, spp)
+    assert sorted(wrote) == ["radiance_pixel_mean", "radiance_sample", "sample_lane", "valid_sample"]
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in wrote}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    Ls = L.numpy().reshape(3, npix, passes)[:, :, passes - spp:]
+    vs = valid.numpy().reshape(npix, passes)[:, passes - spp:]
+    np.testing.assert_allclose(got["radiance_pixel_mean"], Ls.mean(axis=2).T, rtol=1e-6)
+    lane = got["sample_lane"].astype(np.int64)
+    assert (np.diff(lane) > 0).all() and len(lane) == npix * spp                  # (fewer lanes than DUMP_LANES: all of them)
+    assert (got["radiance_sample"] == Ls[:, lane // spp, lane % spp].T).all() and (got["valid_sample"] == vs[lane // spp, lane % spp]).all()
+    B.dump_step_outputs(str(tmp_path / "b"), L, valid, passes, spp)
+    assert all((np.load(str(tmp_path / "b" / (k + ".npy"))) == a).all() for k, a in got.items())
+    big = B.dump_step_outputs(str(tmp_path / "c"), torch.zeros(3, 3840 * 2160 * 2), torch.ones(3840 * 2160 * 2, dtype=torch.uint8), 2, 2)
+    assert "pixel_index" in big and sum(big.values()) <= 64 << 20
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_same_outputs_run_after_run_with_and_without_full(tmp_path):
+    """`bench.py --dump-outputs`: two plain runs and a --full run of the same arguments write the same arrays, bit for bit (the
+    timed steps trace the same passes whatever else the run measures); the plain line carries ms_per_step over --steps steps."""
+    import json
+    import subprocess
+    import numpy as np
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--scene", "veach-ajar", "--res", "128", "--train-iters", "3",
+            "--spp-per-pass", "4", "--steps", "3", "--warmup", "1"]
+    full = ["--full", "--cpu", "0", "--full-schedule", "0", "--spp1", "0", "--other-configs", "0", "--synthetic-kernels", "0",
+            "--pmc-in-run", "0", "--phase-probe", "0", "--detail", str(tmp_path / "detail.json")]
+    lines = {}
+    for name, extra in (("a", []), ("b", []), ("full", full)):
+        p = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        out = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, p.stdout
+        lines[name] = _strict(out[0])
+    for c in lines.values():
+        assert c["steps"] == 3 and c["ms_per_step"] > 0 and c["metric"].startswith("Msamples/s guided, veach-ajar 128x72")
+        assert c["value"] == pytest.approx(c["config"]["paths_per_step"] / c["ms_per_step"] / 1e3, rel=2e-3)
+    assert lines["a"]["roofline"] is None and lines["a"]["cpu_baseline"] is None and lines["full"]["roofline"]["kernel"] == "k_wave_guide"
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == ["radiance_pixel_mean.npy", "radiance_sample.npy", "sample_lane.npy", "valid_sample.npy"]
+    for n in names:
+        a = np.load(str(tmp_path / "a" / n))
+        assert a.dtype in (np.float32, np.float64)
+        for other in ("b", "full"):
+            assert np.array_equal(a.view(np.uint8), np.load(str(tmp_path / other / n)).view(np.uint8)), (n, other)
+    assert np.load(str(tmp_path / "a" / "radiance_pixel_mean.npy")).shape == (128 * 72, 3)
+    assert np.load(str(tmp_path / "a" / "valid_sample.npy")).any()

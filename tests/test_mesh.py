@@ -69,8 +69,9 @@ def test_read_serialized_meshes(tmp_path, version):
 
 
 def test_torus_scene_from_its_fixture_and_from_the_xml():
-    """scene.torus() (meshes from the package data torus_meshes.npz) against the scene file itself where
-    the reference is mounted; the fixture's sizes either way."""
+    """scene.torus() (meshes from the package data torus_meshes.npz) against what load_xml reads from the reference's
+    scene file (tests/golden/scene_xml_digests.json), and the fixture's sizes."""
+    import json
     import os
     sc = S.torus(64, 48)
     assert sc.tris.shape == (23614, 16) and sc.tri_normals.shape == (23614, 9) and sc.bvh.shape[1] == 32
@@ -79,17 +80,23 @@ def test_torus_scene_from_its_fixture_and_from_the_xml():
     assert [int(m[0]) for m in sc.materials] == [S.MAT_DIFFUSE, S.MAT_DIFFUSE, S.MAT_ROUGHDIELECTRIC, S.MAT_CONDUCTOR]
     assert (sc.materials[:, 11] == 1).all()                                         # nothing is twosided in this scene
     _check_bvh(sc.bvh, sc.tris)
-    xml = "/root/reference/scenes/torus/scene.xml"
-    if not os.path.exists(xml):
-        return
-    ref = S.load_xml(xml, 64, 48)
+    # the reference's scene file, as load_xml reads it: recorded in tests/golden/scene_xml_digests.json by
+    # tests/golden/make_scene_xml_digests.py
+    ref = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "scene_xml_digests.json")))["torus 64x48"]
     for k in ("bvh", "tri_normals", "dir_lights", "bbox_min", "bbox_max"):
-        assert np.array_equal(getattr(sc, k), getattr(ref, k)), k
-    assert np.array_equal(sc.tris[:, :12], ref.tris[:, :12])
-    assert np.array_equal(sc.materials[sc.tris[:, 12].astype(int)], ref.materials[ref.tris[:, 12].astype(int)])
-    assert sc.camera.width == ref.camera.width and ref.rfilter == "gaussian" and ref.max_depth == 30
+        assert _digest(getattr(sc, k)) == ref["arrays"][k], k
+    assert _digest(sc.tris[:, :12]) == ref["arrays"]["tris_geometry"]
+    assert _digest(sc.materials[sc.tris[:, 12].astype(int)]) == ref["arrays"]["material_of_each_triangle"]
+    assert sc.camera.width == ref["width"] and ref["rfilter"] == "gaussian" and ref["max_depth"] == 30
     for k in ("origin", "axis_x", "axis_y", "axis_z"):
-        assert np.array_equal(getattr(sc.camera, k), getattr(ref.camera, k))
+        assert _digest(getattr(sc.camera, k)) == ref["camera"][k], k
+
+
+def _digest(a):
+    """as tests/golden/make_scene_xml_digests.py: dtype, shape and SHA-256 of the bytes"""
+    import hashlib
+    a = np.ascontiguousarray(a)
+    return {"dtype": a.dtype.str, "shape": list(a.shape), "sha256": hashlib.sha256(a.tobytes()).hexdigest()}
 
 
 def _check_bvh(nodes, tris):

@@ -3,7 +3,7 @@
 # the SD-tree kernel of a bounce waits on.  Separate --pmc passes (at most two counters of a block each),
 # never combined with tracing; every pass under its own timeout.
 export TMPDIR=/tmp; R=$PWD; D=$R/gpurun_out/pmc_guide; mkdir -p $D; cd /tmp
-ARGS="--steps 2 --warmup 1 --cpu 0 --train-iters 4"
+ARGS="--full --steps 2 --warmup 1 --cpu 0 --train-iters 4"
 pass() { # name, counters...
 	local n=$1; shift
 	echo "pass $n: $@" >> $D/progress.log

@@ -3,7 +3,7 @@
 # work is fp64 (the deterministic series), fp32 arithmetic, integer / address arithmetic.  Two bounded passes
 # (eight counters each, nothing traced beside them).
 export TMPDIR=/tmp; R=$PWD; D=$R/gpurun_out/pmc_valu; mkdir -p $D; cd /tmp
-ARGS="--steps 3 --warmup 1 --cpu 0 --full-schedule 0 --spp1 0 --synthetic-kernels 0 --other-configs 0 --pmc-in-run 0"
+ARGS="--full --steps 3 --warmup 1 --cpu 0 --full-schedule 0 --spp1 0 --synthetic-kernels 0 --other-configs 0 --pmc-in-run 0"
 timeout -k 5 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_TRANS_F32 --kernel-include-regex "k_wave_" --output-format csv -d $D/a -- python3 $R/bench.py $ARGS > /dev/null 2> $D/a.err &&
 timeout -k 5 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_CVT --kernel-include-regex "k_wave_" --output-format csv -d $D/b -- python3 $R/bench.py $ARGS > /dev/null 2> $D/b.err
 echo rc=$?

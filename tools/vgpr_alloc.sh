@@ -2,7 +2,7 @@
 # Dev tool (GPU box, repo root): what the hardware ALLOCATES per kernel -- rocprofv3's VGPR_Count / LDS_Block_Size columns of a
 # kernel trace -- beside what the compiler reported (csrc/*.remarks).  bash tools/vgpr_alloc.sh OUT [bench args]
 export TMPDIR=/tmp; R=$PWD; D=$R/gpurun_out/$1; shift; mkdir -p $D; cd /tmp
-timeout -k 5 200 rocprofv3 --kernel-trace --output-format csv -d $D/t -- python3 $R/bench.py --steps 2 --warmup 1 --train-iters 3 --cpu 0 --full-schedule 0 --spp1 0 --synthetic-kernels 0 --other-configs 0 --pmc-in-run 0 --phase-probe 0 "$@" > /dev/null 2> $D/err.txt
+timeout -k 5 200 rocprofv3 --kernel-trace --output-format csv -d $D/t -- python3 $R/bench.py --full --steps 2 --warmup 1 --train-iters 3 --cpu 0 --full-schedule 0 --spp1 0 --synthetic-kernels 0 --other-configs 0 --pmc-in-run 0 --phase-probe 0 "$@" > /dev/null 2> $D/err.txt
 echo rc=$?
 python3 - <<PY
 import csv, glob
