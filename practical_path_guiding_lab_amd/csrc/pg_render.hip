@@ -651,6 +651,10 @@ struct PassBuf {
 // pg_render_sort: a bounce is sorted when at least 3/10 of the pass's lanes were alive going into it (last pass's counts)
 constexpr uint64_t kSortMinLiveNum = 3, kSortMinLiveDen = 10;
 
+// What an interval of pg_enable_kernel_timing is credited to (pg_read_kernel_timing): a quad scene's bounce (k_bounce_tail and
+// k_bounce as one), the kernels of the split pipeline (timer_of) and its sorts, k_splat_list, and k_layout_L with k_finish
+enum class Timer { Bounce, Trace, ShadeA, Shadow, Guide, ShadeB, Tail, Sort, Splat, Finish };
+
 // library-owned renderer state
 struct pg_render_state {
 	DevBuf<float> quads, spheres, mats, boxes, tris, dir_lights, ior, tri_normals, tri_uvs, srgb_lut;
@@ -671,7 +675,7 @@ struct pg_render_state {
 	int last_slot = 0;         // of the most recent pass (pg_render_live_counts)
 	// optional per-kernel timing: (kind, start, stop) event triples still to be read
 	bool timing_on = false;
-	struct Ev { int kind; hipEvent_t a, b; };
+	struct Ev { Timer kind; hipEvent_t a, b; };
 	std::vector<Ev> events;
 	pg_kernel_timing acc = {};
 };
@@ -680,9 +684,9 @@ namespace {
 struct Timed { // records an event pair around a launch when timing is enabled
 	pg_render_state *r;
 	hipStream_t s;
-	int kind;
+	Timer kind;
 	hipEvent_t a = nullptr, b = nullptr;
-	Timed(pg_render_state *r_, hipStream_t s_, int kind_) : r(r_), s(s_), kind(kind_)
+	Timed(pg_render_state *r_, hipStream_t s_, Timer kind_) : r(r_), s(s_), kind(kind_)
 	{
 		if (!r->timing_on) return;
 		if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
@@ -751,6 +755,260 @@ static int ensure_pass_buffers(pg_context *ctx, int slot, uint64_t N, bool recor
 		// (pg_list_records: 60 B per entry -- no position, no directions, one plane of radiance_nee)
 		PG_HIP(ctx, b.r_nee.ensure(S));
 		PG_HIP(ctx, b.r_slot.ensure(S)); PG_HIP(ctx, b.r_tree.ensure(S));
+	}
+	return PG_OK;
+}
+
+// The checks of pg_render_pass's arguments, and the pass's pixel count P: the range, or this rank's rows of the stripes
+// (P = 0: nothing to render)
+static int check_pass(pg_context *ctx, const pg_pass_params *prm, const float *L_out, const float *sumL, const float *sumL2, uint64_t &P)
+{
+	if (!ctx) return PG_ERR_INVALID;
+	if (!ctx->configured) return fail(ctx, PG_ERR_INVALID, "call pg_setup or pg_import first");
+	if (!ctx->render || !ctx->render->have_scene) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: call pg_scene_set first");
+	if (!prm || !L_out) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: NULL pointer");
+	if (prm->spp <= 0 || ctx->max_depth <= 0) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: spp and max_depth must be > 0");
+	if ((sumL == nullptr) != (sumL2 == nullptr)) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: sumL and sumL2 go together");
+	PG_HIP(ctx, hipSetDevice(ctx->device));
+	const pg_camera &cam = ctx->render->cam;
+	const uint64_t film = (uint64_t)cam.width * (uint64_t)cam.height;
+	if (prm->pixel_begin > film || prm->pixel_count > film - prm->pixel_begin)
+		return fail(ctx, PG_ERR_INVALID, "pg_render_pass: pixel range outside the film");
+	P = prm->pixel_count ? prm->pixel_count : film - prm->pixel_begin; // 0 = to the end
+	if (prm->stripe_count > 1) { // bands of stripe_rows rows dealt round-robin: this rank's rows
+		if (prm->stripe_rows == 0 || prm->stripe_index >= prm->stripe_count || prm->pixel_begin != 0)
+			return fail(ctx, PG_ERR_INVALID, "pg_render_pass: bad stripe parameters");
+		uint64_t rows = 0;
+		for (uint64_t row = 0; row < (uint64_t)cam.height; ++row)
+			rows += (row / prm->stripe_rows) % prm->stripe_count == prm->stripe_index;
+		if (prm->pixel_count && prm->pixel_count != rows * (uint64_t)cam.width)
+			return fail(ctx, PG_ERR_INVALID, "pg_render_pass: pixel_count does not match the stripes of this rank");
+		P = rows * (uint64_t)cam.width;
+	}
+	if (P == 0) return PG_OK;
+	if (P * (uint64_t)prm->spp * (uint64_t)ctx->max_depth > 0xffffffffull)
+		return fail(ctx, PG_ERR_INVALID, "pg_render_pass: more than 2^32 record slots in one pass");
+	if (prm->slot < 0 || prm->slot > 1) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: slot must be 0 or 1");
+	return PG_OK;
+}
+
+// The kernels' argument block of a pass of P pixels in buffer set b, but for what changes per bounce
+static RenderArgs pass_args(pg_context *ctx, const pg_pass_params *prm, PassBuf &b, uint64_t P, float *L_out)
+{
+	const pg_render_state *r = ctx->render;
+	const int D = ctx->max_depth;
+	RenderArgs a;
+	a.tree = ctx->view();
+	// the scene
+	a.shapes.quads = r->quads.p; a.shapes.spheres = r->spheres.p; a.shapes.boxes = r->boxes.p; a.shapes.tris = r->tris.p;
+	a.shapes.tri_normals = r->have_tri_normals ? r->tri_normals.p : nullptr;
+	a.shapes.tri_uvs = r->have_tri_uvs ? r->tri_uvs.p : nullptr;
+	a.shapes.textures = r->textures.p; a.shapes.texels = r->texels.p; a.shapes.srgb_lut = r->srgb_lut.p;
+	a.shapes.bvh = r->bvh.p; a.shapes.n_bvh_nodes = r->n_bvh_nodes;
+	a.shapes.n_quads = r->n_quads; a.shapes.n_spheres = r->n_spheres; a.shapes.n_boxes = r->n_boxes;
+	a.mats = r->mats.p; a.emitters = r->emitters.p; a.n_emitters = r->n_emitters; a.ior = r->ior.p;
+	a.dir_lights.lights = r->dir_lights.p;
+	for (int c = 0; c < 4; ++c) a.dir_lights.bsphere[c] = r->bsphere[c];
+	a.cam = r->cam;
+	// the pass
+	a.n_lanes = P * (uint64_t)prm->spp; a.n_pixels = P; a.pixel_begin = prm->pixel_begin;
+	a.stripe_rows = prm->stripe_rows; a.stripe_index = prm->stripe_index; a.stripe_count = prm->stripe_count;
+	a.film_pixels = (uint64_t)r->cam.width * (uint64_t)r->cam.height;
+	a.spp = prm->spp; a.max_depth = D; a.rr_depth = prm->rr_depth; a.seed = prm->seed; a.batched = prm->batched ? 1 : 0;
+	a.guided = ctx->iteration > 1 ? 1 : 0; // :223, 250, 283
+	a.record = ctx->is_final ? 0 : 1; a.store_nee = ctx->store_nee; a.frac = ctx->bsdf_fraction;
+	a.dc = ctx->dc_on ? ctx->dc : nullptr;
+	a.ph = ctx->ph_on ? ctx->ph_buf.p : nullptr;
+	// pg_render_stages: the SD-tree calls in k_wave_shade / k_wave_shade_a, or in k_wave_guide of their own -- which
+	// pg_render_overlap needs, to run them beside the shadow rays
+	const bool wave = r->general >= 2; // mesh scenes: the split pipeline
+	a.fuse_guide = wave && r->stages < 2 && !(r->overlap & 1) ? 1 : 0;
+	// the buffer set
+	a.ray_d = b.ray_d.p; a.thr = b.thr.p; a.L = L_out; a.prev_p = b.prev_p.p;
+	a.prev_pdf = b.prev_pdf.p; a.prev_quad = b.prev_quad.p; a.hit0 = b.hit0.p;
+	a.rng_state = b.rng_state.p; a.rng_inc = b.rng_inc.p; a.live_count = b.live_count.p;
+	a.ray_of = b.ray_of.p; a.r_bsdf = b.r_bsdf.p; a.r_tb = b.r_tb.p;
+	a.r_tr = b.r_tr.p; a.r_nee = b.r_nee.p; a.r_wp = b.r_wp.p;
+	a.r_slot = b.r_slot.p; a.r_tree = b.r_tree.p;
+	a.Lq = wave ? b.Lq.p : nullptr;
+	a.ws = b.ws.p; a.bvh_ovf = b.bvh_ovf.p; a.shadow_list = b.shadow_list.p;
+	a.cast_count = b.live_count.p + (D + 1);
+	a.shadow_count = b.live_count.p + (D + 1) + 2 * D;
+	a.st_in = nullptr; a.st_out = nullptr; a.inc_in = nullptr; a.inc_out = nullptr; // (set per bounce: wave_bounce)
+	a.sort_key = nullptr; a.perm = nullptr; a.carry_in = nullptr; a.carry_out = nullptr; a.n_sort = 0;
+	return a;
+}
+
+// Bounce `it` of a scene of the fused kernels: k_bounce, behind k_bounce_tail at a checkpoint, timed as one
+static void quad_bounce(pg_render_state *r, const RenderArgs &a, int it, hipStream_t s)
+{
+	Timed t(r, s, Timer::Bounce);
+	if (tail_checkpoint(it, a.max_depth)) { // finishes every path in one launch once few are left (see k_bounce_tail)
+		const dim3 tgrid((unsigned)((kTailPaths + kRBlock - 1) / kRBlock));
+		if (r->general == 1) hipLaunchKernelGGL((k_bounce_tail<1>), tgrid, dim3(kRBlock), 0, s, a);
+		else hipLaunchKernelGGL((k_bounce_tail<0>), tgrid, dim3(kRBlock), 0, s, a);
+	}
+	// every launch is sized for the whole wavefront: the live count is only known on the device,
+	// and workgroups past it retire on their first instruction
+	const dim3 grid((unsigned)((a.n_lanes + kRBlock - 1) / kRBlock));
+	if (r->general == 1) {
+		if (it == 0) hipLaunchKernelGGL((k_bounce<true, 1>), grid, dim3(kRBlock), 0, s, a);
+		else hipLaunchKernelGGL((k_bounce<false, 1>), grid, dim3(kRBlock), 0, s, a);
+	} else {
+		if (it == 0) hipLaunchKernelGGL((k_bounce<true, 0>), grid, dim3(kRBlock), 0, s, a);
+		else hipLaunchKernelGGL((k_bounce<false, 0>), grid, dim3(kRBlock), 0, s, a);
+	}
+}
+
+// pg_render_sort: is bounce `bounce` of a pass of N lanes in set b sorted?  Those from the second one to sort_until, when enough
+// lanes were alive going into it in the set's last pass (the choice changes no result: without counts every one is sorted)
+static bool worth_sorting(const PassBuf &b, int bounce, int sort_until, uint64_t N)
+{
+	if (bounce < 1 || bounce >= sort_until) return false;
+	return !b.live_known || (uint64_t)b.live_prev[bounce - 1] * kSortMinLiveDen >= N * kSortMinLiveNum;
+}
+
+// the timer of a wave stage's interval (the joint k_wave_shade counts as k_wave_shade_a: shade_ms and shade_a_ms)
+static Timer timer_of(WaveStage stage)
+{
+	switch (stage) {
+	case WaveStage::Trace: return Timer::Trace;
+	case WaveStage::ShadeA: case WaveStage::Shade: return Timer::ShadeA;
+	case WaveStage::Cast: return Timer::Shadow;
+	case WaveStage::Guide: return Timer::Guide;
+	case WaveStage::ShadeB: return Timer::ShadeB;
+	case WaveStage::Tail: break;
+	}
+	return Timer::Tail;
+}
+
+// Bounce `it` of a mesh scene: the split pipeline's kernels (pg_render_wave.hip), each timed on its own -- the tail launch at
+// a checkpoint; the closest hits (a sorted bounce: with the keys cleared before and the sort after); then the joint shading
+// kernel, or ShadeA, Cast, Guide (unless fused into ShadeA) and ShadeB.  pg_render_overlap runs Guide beside Cast on the
+// set's side stream -- both read what ShadeA left and write planes of their own, one bound by divergent gathers into the
+// tree, the other by the BVH walk's dependent loads -- except in a sorted bounce, where it runs after Cast on s.
+static int wave_bounce(pg_context *ctx, PassBuf &b, RenderArgs &a, int it, int sort_until, hipStream_t s)
+{
+	pg_render_state *r = ctx->render;
+	const uint64_t N = a.n_lanes;
+	const unsigned blocks = (unsigned)((N + kRBlock - 1) / kRBlock);
+	auto launch = [&](WaveStage stage, hipStream_t on, unsigned grid_blocks) {
+		Timed t(r, on, timer_of(stage));
+		launch_wave_stage(stage, r->general, it == 0, a, grid_blocks, (unsigned)ctx->n_cus, on);
+	};
+	// the state set this bounce reads and the one its survivors are written to; the camera rays of the first
+	// launch go to the set the first bounce reads
+	a.st_in = b.st[it & 1].p; a.inc_in = b.inc[it & 1].p;
+	a.st_out = b.st[(it + 1) & 1].p; a.inc_out = b.inc[(it + 1) & 1].p;
+	const bool sorted = worth_sorting(b, it, sort_until, N);
+	// (the state of a sorted bounce is in the paths' records: the tail launch reads it there)
+	a.carry_in = sorted ? b.carry[it & 1].p : nullptr;
+	a.sort_key = nullptr; a.perm = nullptr; a.carry_out = nullptr;
+	if (tail_checkpoint(it, a.max_depth)) launch(WaveStage::Tail, s, (unsigned)((kTailPaths + kRBlock - 1) / kRBlock));
+	a.sort_key = sorted ? b.sort_key.p : nullptr;
+	a.carry_out = worth_sorting(b, it + 1, sort_until, N) ? b.carry[(it + 1) & 1].p : nullptr;
+	const bool fork = (r->overlap & 1) && !sorted;
+	if (fork && !b.side) {
+		PG_HIP(ctx, hipStreamCreateWithFlags(&b.side, hipStreamNonBlocking));
+		PG_HIP(ctx, hipEventCreateWithFlags(&b.ev_fork, hipEventDisableTiming));
+		PG_HIP(ctx, hipEventCreateWithFlags(&b.ev_join, hipEventDisableTiming));
+	}
+	if (sorted) { // closest hits in list order (they write every live place's key), the sort, then everything else at k
+		// the sort covers the first n_sort places: all N without counts of a previous pass, else a little more than
+		// were alive then (a radix sort costs what its n costs).  Places beyond n_sort -- none, unless this pass keeps
+		// more paths alive than the last -- are served in list order (k_wave_shade_a): correct either way.
+		const uint64_t n_sort = b.live_known ? (uint64_t)b.live_prev[it - 1] + (uint64_t)b.live_prev[it - 1] / 32 + 65536 : N;
+		a.n_sort = (uint32_t)(n_sort < N ? n_sort : N);
+		PG_HIP(ctx, hipMemsetAsync(b.sort_key.p, 0xff, (size_t)a.n_sort * sizeof(uint16_t), s)); // (0xffff: a place without a path)
+	}
+	launch(WaveStage::Trace, s, blocks);
+	if (sorted) {
+		Timed t(r, s, Timer::Sort);
+		PG_HIP(ctx, sort_places16(b.sort_tmp.p, b.sort_tmp_bytes, b.sort_key.p, b.sort_key_out.p, b.sort_perm.p, a.n_sort,
+		                            a.live_count + (it - 1), s));
+		a.perm = b.sort_perm.p;
+	}
+	if (r->stages == 0 && !(r->overlap & 1)) {
+		launch(WaveStage::Shade, s, blocks);
+		return PG_OK;
+	}
+	launch(WaveStage::ShadeA, s, blocks);
+	if (fork) {
+		PG_HIP(ctx, hipEventRecord(b.ev_fork, s));
+		PG_HIP(ctx, hipStreamWaitEvent(b.side, b.ev_fork, 0));
+		launch(WaveStage::Guide, b.side, blocks);
+		PG_HIP(ctx, hipEventRecord(b.ev_join, b.side));
+	}
+	launch(WaveStage::Cast, s, blocks);
+	if (fork) PG_HIP(ctx, hipStreamWaitEvent(s, b.ev_join, 0));
+	else if (!a.fuse_guide) launch(WaveStage::Guide, s, blocks);
+	launch(WaveStage::ShadeB, s, blocks);
+	return PG_OK;
+}
+
+// Behind the bounces of a pass in buffer set `slot`: the splat of its records into sdTree_current, the output column of
+// the split pipeline (k_layout_L), the valid flags and the per-pixel sums (k_finish)
+static int finish_pass(pg_context *ctx, int slot, const RenderArgs &a, uint8_t *valid_out, float *sumL, float *sumL2, hipStream_t s)
+{
+	pg_render_state *r = ctx->render;
+	PassBuf &b = r->pb[slot];
+	if (a.record) {
+		Timed t(r, s, Timer::Splat);
+		// the depth counters of an instrumented pass describe the bounce kernels only
+		pg_list_records lr;
+		lr.ray_of = b.ray_of.p; lr.bsdf = b.r_bsdf.p; lr.throughput_bsdf = b.r_tb.p; lr.throughput_radiance = b.r_tr.p;
+		lr.nee_lum = b.r_nee.p; lr.wo_pdf = b.r_wp.p; lr.slot = b.r_slot.p; lr.tree = b.r_tree.p;
+		launch_splat_list(ctx->view(), ctx->f.accum_view(), ctx->store_nee, a.n_lanes, a.max_depth, a.L, a.Lq, lr, b.live_count.p, s);
+		PG_HIP(ctx, hipGetLastError());
+	}
+	if (r->general >= 2) {
+		Timed t(r, s, Timer::Finish);
+		hipLaunchKernelGGL(k_layout_L, dim3((unsigned)((a.n_lanes + kRBlock - 1) / kRBlock)), dim3(kRBlock), 0, s, b.Lq.p, a.L, a.n_lanes);
+	}
+	if (valid_out || sumL) {
+		// the per-pixel sums are read, added to and written back (fp32: the order of the passes is part of the result,
+		// :400-429): a pass of the other buffer set that was issued before this one finishes its sums first
+		PassBuf &other = r->pb[1 - slot];
+		if (sumL && other.finish_recorded) PG_HIP(ctx, hipStreamWaitEvent(s, other.ev_finish, 0));
+		Timed t(r, s, Timer::Finish);
+		hipLaunchKernelGGL(k_finish, dim3((unsigned)((a.n_pixels + kRBlock - 1) / kRBlock)), dim3(kRBlock), 0, s, a, valid_out,
+		                   sumL, sumL2);
+		PG_HIP(ctx, hipGetLastError());
+		if (sumL) {
+			if (!b.ev_finish) PG_HIP(ctx, hipEventCreateWithFlags(&b.ev_finish, hipEventDisableTiming));
+			PG_HIP(ctx, hipEventRecord(b.ev_finish, s));
+			b.finish_recorded = true;
+		}
+	}
+	return PG_OK;
+}
+
+// pg_render_sort decides which bounces to sort by the live counts of the set's previous pass (worth_sorting): they come
+// back to the host behind a pass (pinned memory, an event) and are taken up by a later pass of the same size once there
+static void take_live_counts(PassBuf &b, uint64_t N, int D)
+{
+	if (b.live_pending && hipEventQuery(b.ev_live) == hipSuccess) { // the previous pass's live counts have arrived
+		b.live_prev.assign(b.h_live, b.h_live + b.h_live_n);
+		b.live_pending = false;
+		b.live_known = true;
+	}
+	if (b.live_known && (b.live_prev_lanes != N || (int)b.live_prev.size() != D)) b.live_known = false; // (another pass size)
+}
+
+static int send_live_counts(pg_context *ctx, PassBuf &b, uint64_t N, int D, hipStream_t s)
+{
+	if (!b.h_live || b.h_live_n != D) {
+		if (b.h_live) (void)hipHostFree(b.h_live);
+		b.h_live = nullptr;
+		PG_HIP(ctx, hipHostMalloc((void **)&b.h_live, (size_t)D * sizeof(uint32_t)));
+		b.h_live_n = D;
+	}
+	if (!b.ev_live) PG_HIP(ctx, hipEventCreateWithFlags(&b.ev_live, hipEventDisableTiming));
+	if (!b.live_pending) {
+		PG_HIP(ctx, hipMemcpyAsync(b.h_live, b.live_count.p, (size_t)D * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+		PG_HIP(ctx, hipEventRecord(b.ev_live, s));
+		b.live_pending = true;
+		b.live_prev_lanes = N;
 	}
 	return PG_OK;
 }
@@ -961,286 +1219,38 @@ int pg_scene_set_ex(pg_context *ctx, const pg_scene_desc *sc, const pg_camera *c
 int pg_render_pass(pg_context *ctx, const pg_pass_params *prm, float *L_out, uint8_t *valid_out, float *sumL,
                    float *sumL2, void *stream)
 {
-	if (!ctx) return PG_ERR_INVALID;
-	if (!ctx->configured) return fail(ctx, PG_ERR_INVALID, "call pg_setup or pg_import first");
-	if (!ctx->render || !ctx->render->have_scene) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: call pg_scene_set first");
-	if (!prm || !L_out) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: NULL pointer");
-	if (prm->spp <= 0 || ctx->max_depth <= 0) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: spp and max_depth must be > 0");
-	if ((sumL == nullptr) != (sumL2 == nullptr)) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: sumL and sumL2 go together");
-	PG_HIP(ctx, hipSetDevice(ctx->device));
+	uint64_t P = 0;
+	int rc = check_pass(ctx, prm, L_out, sumL, sumL2, P);
+	if (rc != PG_OK || P == 0) return rc;
 	hipStream_t s = (hipStream_t)stream;
 	pg_render_state *r = ctx->render;
-	const uint64_t film = (uint64_t)r->cam.width * (uint64_t)r->cam.height;
-	if (prm->pixel_begin > film || prm->pixel_count > film - prm->pixel_begin)
-		return fail(ctx, PG_ERR_INVALID, "pg_render_pass: pixel range outside the film");
-	uint64_t P = prm->pixel_count ? prm->pixel_count : film - prm->pixel_begin; // 0 = to the end
-	if (prm->stripe_count > 1) { // bands of stripe_rows rows dealt round-robin: this rank's rows
-		if (prm->stripe_rows == 0 || prm->stripe_index >= prm->stripe_count || prm->pixel_begin != 0)
-			return fail(ctx, PG_ERR_INVALID, "pg_render_pass: bad stripe parameters");
-		uint64_t rows = 0;
-		for (uint64_t row = 0; row < (uint64_t)r->cam.height; ++row)
-			rows += (row / prm->stripe_rows) % prm->stripe_count == prm->stripe_index;
-		if (prm->pixel_count && prm->pixel_count != rows * (uint64_t)r->cam.width)
-			return fail(ctx, PG_ERR_INVALID, "pg_render_pass: pixel_count does not match the stripes of this rank");
-		P = rows * (uint64_t)r->cam.width;
-	}
-	if (P == 0) return PG_OK;
+	const int D = ctx->max_depth, slot = prm->slot;
 	const uint64_t N = P * (uint64_t)prm->spp;
-	const int D = ctx->max_depth;
-	const uint64_t S = N * (uint64_t)D;
-	if (S > 0xffffffffull) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: more than 2^32 record slots in one pass");
-	const bool record = !ctx->is_final;
-	const bool wave = r->general >= 2; // mesh scenes: the split pipeline
-	if (prm->slot < 0 || prm->slot > 1) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: slot must be 0 or 1");
-	const int slot = prm->slot;
 	PassBuf &b = r->pb[slot];
 	r->last_slot = slot;
-	if (sumL && film > ctx->num_rays)
+	if (sumL && (uint64_t)r->cam.width * (uint64_t)r->cam.height > ctx->num_rays)
 		return fail(ctx, PG_ERR_INVALID, "pg_render_pass: sumL/sumL2 are sized by pg_setup's num_rays, which is smaller than the film");
-	{
-		const int rc = ensure_pass_buffers(ctx, slot, N, record);
-		if (rc != PG_OK) return rc;
-	}
+	if ((rc = ensure_pass_buffers(ctx, slot, N, !ctx->is_final)) != PG_OK) return rc;
 	// counters of a pass, zeroed together: live_count[D + 1] ([D]: entries handed out by the tail launch), then for
 	// mesh scenes cast_count[2 D] and shadow_count[D] of the persistent ray-casting kernels
-	const size_t n_counters = (size_t)D + 1 + 3 * (size_t)D;
-	PG_HIP(ctx, hipMemsetAsync(b.live_count.p, 0, n_counters * sizeof(uint32_t), s));
-	RenderArgs a;
-	a.tree = ctx->view();
-	a.shapes.quads = r->quads.p;
-	a.shapes.spheres = r->spheres.p;
-	a.shapes.boxes = r->boxes.p;
-	a.shapes.tris = r->tris.p;
-	a.shapes.tri_normals = r->have_tri_normals ? r->tri_normals.p : nullptr;
-	a.shapes.tri_uvs = r->have_tri_uvs ? r->tri_uvs.p : nullptr;
-	a.shapes.textures = r->textures.p;
-	a.shapes.texels = r->texels.p;
-	a.shapes.srgb_lut = r->srgb_lut.p;
-	a.st_in = nullptr; a.st_out = nullptr; a.inc_in = nullptr; a.inc_out = nullptr; // (set per bounce below)
-	a.sort_key = nullptr; a.perm = nullptr; a.carry_in = nullptr; a.carry_out = nullptr; a.n_sort = 0;
-	a.Lq = wave ? b.Lq.p : nullptr;
+	PG_HIP(ctx, hipMemsetAsync(b.live_count.p, 0, ((size_t)D + 1 + 3 * (size_t)D) * sizeof(uint32_t), s));
+	RenderArgs a = pass_args(ctx, prm, b, P, L_out);
+	const bool wave = r->general >= 2; // mesh scenes: the split pipeline
 	// sorted bounces (pg_render_sort): from the second bounce (camera rays find neighbouring vertices by themselves) to
 	// the depth at which Russian roulette thins the list out (:375: a sort costs what 33 M pairs cost however few are alive)
 	const int sort_until = wave && r->sort ? (prm->rr_depth < D ? prm->rr_depth : D) : 0;
-	if (sort_until > 1) {
-		if (b.live_pending && hipEventQuery(b.ev_live) == hipSuccess) { // the previous pass's live counts have arrived
-			b.live_prev.assign(b.h_live, b.h_live + b.h_live_n);
-			b.live_pending = false;
-			b.live_known = true;
-		}
-		if (b.live_known && (b.live_prev_lanes != N || (int)b.live_prev.size() != D)) b.live_known = false; // (another pass size)
-	}
-	a.ws = b.ws.p;
-	a.bvh_ovf = b.bvh_ovf.p;
-	a.cast_count = b.live_count.p + (D + 1);
-	a.shadow_count = b.live_count.p + (D + 1) + 2 * D;
-	a.shadow_list = b.shadow_list.p;
-	a.shapes.bvh = r->bvh.p;
-	a.shapes.n_bvh_nodes = r->n_bvh_nodes;
-	a.shapes.n_quads = r->n_quads;
-	a.shapes.n_spheres = r->n_spheres;
-	a.shapes.n_boxes = r->n_boxes;
-	a.mats = r->mats.p;
-	a.emitters = r->emitters.p;
-	a.n_emitters = r->n_emitters;
-	a.dir_lights.lights = r->dir_lights.p;
-	for (int c = 0; c < 4; ++c) a.dir_lights.bsphere[c] = r->bsphere[c];
-	a.ior = r->ior.p;
-	a.cam = r->cam;
-	a.n_lanes = N;
-	a.n_pixels = P;
-	a.pixel_begin = prm->pixel_begin;
-	a.stripe_rows = prm->stripe_rows; a.stripe_index = prm->stripe_index; a.stripe_count = prm->stripe_count;
-	a.film_pixels = film;
-	a.spp = prm->spp;
-	a.max_depth = D;
-	a.rr_depth = prm->rr_depth;
-	a.guided = ctx->iteration > 1 ? 1 : 0; // :223, 250, 283
-	a.record = record ? 1 : 0;
-	a.store_nee = ctx->store_nee;
-	a.frac = ctx->bsdf_fraction;
-	a.seed = prm->seed;
-	a.batched = prm->batched ? 1 : 0;
-	a.dc = ctx->dc_on ? ctx->dc : nullptr;
-	a.ph = ctx->ph_on ? ctx->ph_buf.p : nullptr;
-	a.ray_d = b.ray_d.p; a.thr = b.thr.p; a.L = L_out; a.prev_p = b.prev_p.p;
-	a.prev_pdf = b.prev_pdf.p; a.prev_quad = b.prev_quad.p; a.hit0 = b.hit0.p;
-	a.rng_state = b.rng_state.p; a.rng_inc = b.rng_inc.p; a.live_count = b.live_count.p;
-	a.ray_of = b.ray_of.p; a.r_bsdf = b.r_bsdf.p; a.r_tb = b.r_tb.p;
-	a.r_tr = b.r_tr.p; a.r_nee = b.r_nee.p; a.r_wp = b.r_wp.p;
-	a.r_slot = b.r_slot.p; a.r_tree = b.r_tree.p;
-	const dim3 grid((unsigned)((N + kRBlock - 1) / kRBlock));
-	// pg_render_stages: one shading kernel per bounce (k_wave_shade), or k_wave_shade_a with the SD-tree calls in it |
-	// k_wave_cast | k_wave_shade_b, or those with k_wave_guide on its own -- which pg_render_overlap needs, to run it beside
-	// the shadow rays
-	const int stages = (r->overlap & 1) ? 2 : r->stages;
-	a.fuse_guide = wave && stages < 2 ? 1 : 0;
-	const bool joint = wave && stages == 0;
+	if (sort_until > 1) take_live_counts(b, N, D);
 	for (int it = 0; it < D; ++it) {
 		a.bounce = it;
 		a.last = it + 1 == D ? 1 : 0;
 		a.order_in = b.order[it & 1].p;
 		a.order_out = b.order[(it + 1) & 1].p;
-		if (wave) { // pg_render_wave.hip: the kernels of a bounce (pg_render_stages), each timed on its own (kinds 5-9; 10 = tail; k_wave_shade: kind 6)
-			// the state set this bounce reads and the one its survivors are written to; the camera rays of the first
-			// launch go to the set the first bounce reads
-			a.st_in = b.st[it & 1].p; a.inc_in = b.inc[it & 1].p;
-			a.st_out = b.st[(it + 1) & 1].p; a.inc_out = b.inc[(it + 1) & 1].p;
-			// (the choice changes no result: without counts of a previous pass every bounce below rr_depth is sorted)
-			auto worth_sorting = [&](int bounce) {
-				if (bounce < 1 || bounce >= sort_until) return false;
-				return !b.live_known || (uint64_t)b.live_prev[bounce - 1] * kSortMinLiveDen >= N * kSortMinLiveNum;
-			};
-			if (tail_checkpoint(it, D)) {
-				Timed t(r, s, 10);
-				// (the state of a sorted bounce is in the paths' records: the tail launch reads it there)
-				a.sort_key = nullptr; a.perm = nullptr; a.carry_out = nullptr;
-				a.carry_in = worth_sorting(it) ? b.carry[it & 1].p : nullptr;
-				launch_wave_stage(5, r->general, false, a, (unsigned)((kTailPaths + kRBlock - 1) / kRBlock), (unsigned)ctx->n_cus, s);
-			}
-			const bool sorted = worth_sorting(it), next_sorted = worth_sorting(it + 1);
-			a.sort_key = sorted ? b.sort_key.p : nullptr;
-			a.carry_in = sorted ? b.carry[it & 1].p : nullptr;
-			a.carry_out = next_sorted ? b.carry[(it + 1) & 1].p : nullptr;
-			a.perm = nullptr;
-			if (sorted) { // closest hits in list order (they write every live place's key), the sort, then everything else at k
-				// the sort covers the first n_sort places: all N without counts of a previous pass, else a little more than
-				// were alive then (a radix sort costs what its n costs).  Places beyond n_sort -- none, unless this pass keeps
-				// more paths alive than the last -- are served in list order (k_wave_shade_a): correct either way.
-				uint64_t n_sort = N;
-				if (b.live_known) {
-					n_sort = (uint64_t)b.live_prev[it - 1] + (uint64_t)b.live_prev[it - 1] / 32 + 65536;
-					if (n_sort > N) n_sort = N;
-				}
-				a.n_sort = (uint32_t)n_sort;
-				PG_HIP(ctx, hipMemsetAsync(b.sort_key.p, 0xff, n_sort * sizeof(uint16_t), s)); // (0xffff: a place without a path)
-				{
-					Timed t(r, s, 5);
-					launch_wave_stage(0, r->general, false, a, grid.x, (unsigned)ctx->n_cus, s);
-				}
-				{
-					Timed t(r, s, 11);
-					PG_HIP(ctx, sort_places16(b.sort_tmp.p, b.sort_tmp_bytes, b.sort_key.p, b.sort_key_out.p, b.sort_perm.p, (uint32_t)n_sort,
-					                            a.live_count + (it - 1), s));
-				}
-				a.perm = b.sort_perm.p;
-				if (joint) {
-					Timed t(r, s, 6);
-					launch_wave_stage(6, r->general, false, a, grid.x, (unsigned)ctx->n_cus, s);
-					continue;
-				}
-				for (int stage = 1; stage < 5; ++stage) {
-					if (stage == 3 && a.fuse_guide) continue;
-					Timed t(r, s, 5 + stage);
-					launch_wave_stage(stage, r->general, false, a, grid.x, (unsigned)ctx->n_cus, s);
-				}
-				continue;
-			}
-			if (r->overlap & 1) {
-				if (!b.side) {
-					PG_HIP(ctx, hipStreamCreateWithFlags(&b.side, hipStreamNonBlocking));
-					PG_HIP(ctx, hipEventCreateWithFlags(&b.ev_fork, hipEventDisableTiming));
-					PG_HIP(ctx, hipEventCreateWithFlags(&b.ev_join, hipEventDisableTiming));
-				}
-				// the SD-tree queries (stage 3) and the shadow rays (stage 2) both read what k_wave_shade_a left and
-				// write planes of their own: one is bound by divergent gathers into the tree, the other by the BVH
-				// walk's dependent loads -- side by side they fill each other's stalls
-				for (int stage = 0; stage < 2; ++stage) {
-					Timed t(r, s, 5 + stage);
-					launch_wave_stage(stage, r->general, it == 0, a, grid.x, (unsigned)ctx->n_cus, s);
-				}
-				PG_HIP(ctx, hipEventRecord(b.ev_fork, s));
-				PG_HIP(ctx, hipStreamWaitEvent(b.side, b.ev_fork, 0));
-				{
-					Timed t(r, b.side, 8);
-					launch_wave_stage(3, r->general, it == 0, a, grid.x, (unsigned)ctx->n_cus, b.side);
-				}
-				PG_HIP(ctx, hipEventRecord(b.ev_join, b.side));
-				{
-					Timed t(r, s, 7);
-					launch_wave_stage(2, r->general, it == 0, a, grid.x, (unsigned)ctx->n_cus, s);
-				}
-				PG_HIP(ctx, hipStreamWaitEvent(s, b.ev_join, 0));
-				Timed t(r, s, 9);
-				launch_wave_stage(4, r->general, it == 0, a, grid.x, (unsigned)ctx->n_cus, s);
-				continue;
-			}
-			if (joint) {
-				{
-					Timed t(r, s, 5);
-					launch_wave_stage(0, r->general, it == 0, a, grid.x, (unsigned)ctx->n_cus, s);
-				}
-				Timed t(r, s, 6);
-				launch_wave_stage(6, r->general, it == 0, a, grid.x, (unsigned)ctx->n_cus, s);
-				continue;
-			}
-			for (int stage = 0; stage < 5; ++stage) {
-				if (stage == 3 && a.fuse_guide) continue;
-				Timed t(r, s, 5 + stage);
-				launch_wave_stage(stage, r->general, it == 0, a, grid.x, (unsigned)ctx->n_cus, s);
-			}
-			continue;
-		}
-		Timed t(r, s, 1);
-		if (tail_checkpoint(it, D)) { // finishes every path in one launch once few are left (see k_bounce_tail)
-			const dim3 tgrid((unsigned)((kTailPaths + kRBlock - 1) / kRBlock));
-			if (r->general == 1) hipLaunchKernelGGL((k_bounce_tail<1>), tgrid, dim3(kRBlock), 0, s, a);
-			else hipLaunchKernelGGL((k_bounce_tail<0>), tgrid, dim3(kRBlock), 0, s, a);
-		}
-		// every launch is sized for the whole wavefront: the live count is only known on the device,
-		// and workgroups past it retire on their first instruction
-		if (r->general == 1) {
-			if (it == 0) hipLaunchKernelGGL((k_bounce<true, 1>), grid, dim3(kRBlock), 0, s, a);
-			else hipLaunchKernelGGL((k_bounce<false, 1>), grid, dim3(kRBlock), 0, s, a);
-		} else {
-			if (it == 0) hipLaunchKernelGGL((k_bounce<true, 0>), grid, dim3(kRBlock), 0, s, a);
-			else hipLaunchKernelGGL((k_bounce<false, 0>), grid, dim3(kRBlock), 0, s, a);
-		}
+		if (!wave) quad_bounce(r, a, it, s);
+		else if ((rc = wave_bounce(ctx, b, a, it, sort_until, s)) != PG_OK) return rc;
 	}
 	PG_HIP(ctx, hipGetLastError());
-	if (record) {
-		Timed t(r, s, 2);
-		// the depth counters of an instrumented pass describe the bounce kernels only
-		pg_list_records lr;
-		lr.ray_of = b.ray_of.p; lr.bsdf = b.r_bsdf.p; lr.throughput_bsdf = b.r_tb.p; lr.throughput_radiance = b.r_tr.p;
-		lr.nee_lum = b.r_nee.p; lr.wo_pdf = b.r_wp.p; lr.slot = b.r_slot.p; lr.tree = b.r_tree.p;
-		launch_splat_list(ctx->view(), ctx->f.accum_view(), ctx->store_nee, N, D, L_out, a.Lq, lr, b.live_count.p, s);
-		PG_HIP(ctx, hipGetLastError());
-	}
-	if (wave) {
-		Timed t(r, s, 3);
-		hipLaunchKernelGGL(k_layout_L, grid, dim3(kRBlock), 0, s, b.Lq.p, L_out, N);
-	}
-	if (valid_out || sumL) {
-		// the per-pixel sums are read, added to and written back (fp32: the order of the passes is part of the result,
-		// :400-429): a pass of the other buffer set that was issued before this one finishes its sums first
-		PassBuf &other = r->pb[1 - slot];
-		if (sumL && other.finish_recorded) PG_HIP(ctx, hipStreamWaitEvent(s, other.ev_finish, 0));
-		Timed t(r, s, 3);
-		hipLaunchKernelGGL(k_finish, dim3((unsigned)((P + kRBlock - 1) / kRBlock)), dim3(kRBlock), 0, s, a, valid_out,
-		                   sumL, sumL2);
-		PG_HIP(ctx, hipGetLastError());
-		if (sumL) {
-			if (!b.ev_finish) PG_HIP(ctx, hipEventCreateWithFlags(&b.ev_finish, hipEventDisableTiming));
-			PG_HIP(ctx, hipEventRecord(b.ev_finish, s));
-			b.finish_recorded = true;
-		}
-	}
-	if (sort_until > 1) { // this pass's live counts, for the next pass of this set to decide by
-		if (!b.h_live || b.h_live_n != D) {
-			if (b.h_live) (void)hipHostFree(b.h_live);
-			b.h_live = nullptr;
-			PG_HIP(ctx, hipHostMalloc((void **)&b.h_live, (size_t)D * sizeof(uint32_t)));
-			b.h_live_n = D;
-		}
-		if (!b.ev_live) PG_HIP(ctx, hipEventCreateWithFlags(&b.ev_live, hipEventDisableTiming));
-		if (!b.live_pending) {
-			PG_HIP(ctx, hipMemcpyAsync(b.h_live, b.live_count.p, (size_t)D * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-			PG_HIP(ctx, hipEventRecord(b.ev_live, s));
-			b.live_pending = true;
-			b.live_prev_lanes = N;
-		}
-	}
+	if ((rc = finish_pass(ctx, slot, a, valid_out, sumL, sumL2, s)) != PG_OK) return rc;
+	if (sort_until > 1 && (rc = send_live_counts(ctx, b, N, D, s)) != PG_OK) return rc;
 	if (r->timing_on) ++r->acc.passes;
 	return PG_OK;
 }
@@ -1343,8 +1353,7 @@ static int film_launch(pg_context *ctx, int32_t filter, bool batched, uint32_t s
 	// by tiles with the samples' film positions staged in LDS where those fit (k_film_tiled), else pixel by pixel
 	const int side = kFilmTile + 2 * (filter == PG_FILTER_GAUSSIAN ? 2 : 1);
 	const size_t lds = (size_t)side * side * (size_t)spp * sizeof(float2);
-	static const bool no_tiles = getenv("PGSD_FILM_TILES") && atoi(getenv("PGSD_FILM_TILES")) == 0; // (A/B switch)
-	if (lds <= 64 * 1024 && !no_tiles) {
+	if (lds <= 64 * 1024) {
 		const dim3 tgrid((unsigned)(((cam.width + kFilmTile - 1) / kFilmTile) * ((cam.height + kFilmTile - 1) / kFilmTile))), tblock(kFilmTile * kFilmTile);
 #define PG_FILM_T(F, B)                                                                                                              \
 	do {                                                                                                                             \
@@ -1430,18 +1439,16 @@ int pg_read_kernel_timing(pg_context *ctx, pg_kernel_timing *out, int32_t reset)
 		PG_HIP(ctx, hipEventSynchronize(e.b));
 		PG_HIP(ctx, hipEventElapsedTime(&ms, e.a, e.b));
 		switch (e.kind) {
-		case 0: r->acc.generate_ms += ms; break;
-		case 1: r->acc.bounce_ms += ms; ++r->acc.bounce_launches; break;
-		case 5: r->acc.trace_ms += ms; r->acc.bounce_ms += ms; ++r->acc.trace_launches; ++r->acc.bounce_launches; break;
-		case 6: r->acc.shade_ms += ms; r->acc.shade_a_ms += ms; r->acc.bounce_ms += ms; break;
-		case 7: r->acc.shadow_ms += ms; r->acc.bounce_ms += ms; break;
-		case 8: r->acc.guide_ms += ms; r->acc.bounce_ms += ms; ++r->acc.guide_launches; break;
-		case 9: r->acc.shade_ms += ms; r->acc.shade_b_ms += ms; r->acc.bounce_ms += ms; break;
-		case 10: r->acc.tail_ms += ms; r->acc.bounce_ms += ms; break;
-		case 11: r->acc.sort_ms += ms; r->acc.bounce_ms += ms; break;
-		case 2: r->acc.splat_ms += ms; ++r->acc.splat_launches; break;
-		case 4: r->acc.compact_ms += ms; break;
-		default: r->acc.finish_ms += ms; break;
+		case Timer::Bounce: r->acc.bounce_ms += ms; ++r->acc.bounce_launches; break;
+		case Timer::Trace: r->acc.trace_ms += ms; r->acc.bounce_ms += ms; ++r->acc.trace_launches; ++r->acc.bounce_launches; break;
+		case Timer::ShadeA: r->acc.shade_ms += ms; r->acc.shade_a_ms += ms; r->acc.bounce_ms += ms; break;
+		case Timer::Shadow: r->acc.shadow_ms += ms; r->acc.bounce_ms += ms; break;
+		case Timer::Guide: r->acc.guide_ms += ms; r->acc.bounce_ms += ms; ++r->acc.guide_launches; break;
+		case Timer::ShadeB: r->acc.shade_ms += ms; r->acc.shade_b_ms += ms; r->acc.bounce_ms += ms; break;
+		case Timer::Tail: r->acc.tail_ms += ms; r->acc.bounce_ms += ms; break;
+		case Timer::Sort: r->acc.sort_ms += ms; r->acc.bounce_ms += ms; break;
+		case Timer::Splat: r->acc.splat_ms += ms; ++r->acc.splat_launches; break;
+		case Timer::Finish: r->acc.finish_ms += ms; break;
 		}
 		(void)hipEventDestroy(e.a);
 		(void)hipEventDestroy(e.b);

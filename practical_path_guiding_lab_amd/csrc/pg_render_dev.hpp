@@ -1300,10 +1300,11 @@ __device__ __forceinline__ uint64_t global_pixel(const RenderArgs &a, uint64_t i
 	return grow * W + col;
 }
 
-// pg_render_wave.hip: one stage (0 trace, 1 shade_a, 2 shadow, 3 guide, 4 shade_b, 5 tail) of one bounce of
-// the split pipeline, feature level 2 or 3; the number of 32-bit planes of its workspace
-// n_cus: compute units of the device (the two ray-casting stages are persistent kernels sized by it)
-void launch_wave_stage(int stage, int level, bool first, const RenderArgs &a, unsigned grid_blocks, unsigned n_cus, hipStream_t s);
+// pg_render_wave.hip: one kernel of one bounce of the split pipeline, feature level 2 or 3 -- k_wave_trace, k_wave_shade_a,
+// k_wave_cast (the shadow rays: a persistent kernel sized by n_cus, the compute units of the device), k_wave_guide, k_wave_shade_b,
+// k_wave_tail, or the joint k_wave_shade (pg_render_stages(0)) for ShadeA .. ShadeB; the number of 32-bit planes of its workspace
+enum class WaveStage { Trace, ShadeA, Cast, Guide, ShadeB, Tail, Shade };
+void launch_wave_stage(WaveStage stage, int level, bool first, const RenderArgs &a, unsigned grid_blocks, unsigned n_cus, hipStream_t s);
 constexpr int kCastBlocksPerCU = 8; // upper bound of the resident 256-thread workgroups of a ray-casting kernel per compute unit
 int wave_workspace_planes();
 

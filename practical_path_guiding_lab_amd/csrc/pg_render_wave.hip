@@ -31,9 +31,6 @@
 // hits and the sort still on their own.  What a path carries from bounce to bounce travels with its place in the
 // live list (st_load below).  Arithmetic and sampler draw order are those of oracle/pg_oracle_render.c, operation
 // by operation, in every form.
-#include <stdio.h>
-#include <stdlib.h>
-
 #include "pg_render_dev.hpp"
 
 namespace pg {
@@ -1368,45 +1365,36 @@ static dim3 persistent_grid(K kernel, unsigned &cached_per_cu, unsigned n_cus, u
 
 // ---- launcher: one stage of one bounce (pg_render_pass wraps each in its timing events) ----
 template <int kLevel>
-static void launch_stage_level(int stage, bool first, const RenderArgs &a, dim3 grid, unsigned n_cus, hipStream_t s)
+static void launch_stage_level(WaveStage stage, bool first, const RenderArgs &a, dim3 grid, unsigned n_cus, hipStream_t s)
 {
 	const dim3 block(kRBlock);
 	static unsigned occ[2] = {0, 0}; // resident workgroups per CU of the two shadow-ray instantiations of this level
 	switch (stage) {
-	case 0:
+	case WaveStage::Trace:
 		if (first) hipLaunchKernelGGL((k_wave_trace<kLevel, true>), grid, block, 0, s, a);
 		else hipLaunchKernelGGL((k_wave_trace<kLevel, false>), grid, block, 0, s, a);
 		break;
-	case 1:
+	case WaveStage::ShadeA:
 		if (a.fuse_guide) {
 			if (first) hipLaunchKernelGGL((k_wave_shade_a<kLevel, true, true>), grid, block, 0, s, a);
 			else hipLaunchKernelGGL((k_wave_shade_a<kLevel, false, true>), grid, block, 0, s, a);
 		} else if (first) hipLaunchKernelGGL((k_wave_shade_a<kLevel, true, false>), grid, block, 0, s, a);
 		else hipLaunchKernelGGL((k_wave_shade_a<kLevel, false, false>), grid, block, 0, s, a);
 		break;
-	case 2:
+	case WaveStage::Cast:
 		if (first) hipLaunchKernelGGL((k_wave_cast<kLevel, true>), persistent_grid(k_wave_cast<kLevel, true>, occ[0], n_cus, a.n_lanes), block, 0, s, a);
 		else hipLaunchKernelGGL((k_wave_cast<kLevel, false>), persistent_grid(k_wave_cast<kLevel, false>, occ[1], n_cus, a.n_lanes), block, 0, s, a);
 		break;
-	case 3: hipLaunchKernelGGL(k_wave_guide, grid, block, 0, s, a); break;
-	case 4: {
+	case WaveStage::Guide: hipLaunchKernelGGL(k_wave_guide, grid, block, 0, s, a); break;
+	case WaveStage::ShadeB: {
 		const size_t lds = a.carry_out ? (size_t)kRBlock * 8 * sizeof(uint4) : 0; // (the survivors' records of a sorted next bounce)
 		if (first) hipLaunchKernelGGL((k_wave_shade_b<kLevel, true>), grid, block, lds, s, a);
 		else hipLaunchKernelGGL((k_wave_shade_b<kLevel, false>), grid, block, lds, s, a);
 		break;
 	}
-	case 6: {
-		// (dev switch: $PGSD_SHADE_LDS_PAD bytes of extra dynamic LDS per workgroup, to see what one resident wave fewer costs)
-		static const size_t pad = getenv("PGSD_SHADE_LDS_PAD") ? (size_t)atol(getenv("PGSD_SHADE_LDS_PAD")) : 0;
-		const size_t lds = (size_t)kShadeLdsQuads * sizeof(uint4) + pad;
-		static bool told = false;
-		if (!told && getenv("PGSD_TRACE_OCC")) { // (dev switch: how many workgroups of this kernel a compute unit holds)
-			told = true;
-			int nb = 0;
-			if constexpr (kLevel == 3) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_wave_shade_l3<false>, kRBlock, lds);
-			else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_wave_shade<kLevel, false>, kRBlock, lds);
-			fprintf(stderr, "[pgsd] k_wave_shade<%d>: %d workgroups of %d threads per compute unit with %zu bytes of dynamic LDS\n", kLevel, nb, kRBlock, lds);
-		}
+	case WaveStage::Tail: hipLaunchKernelGGL((k_wave_tail<kLevel>), grid, block, 0, s, a); break;
+	case WaveStage::Shade: {
+		const size_t lds = (size_t)kShadeLdsQuads * sizeof(uint4);
 		if constexpr (kLevel == 3) {
 			if (first) hipLaunchKernelGGL((k_wave_shade_l3<true>), grid, block, lds, s, a);
 			else hipLaunchKernelGGL((k_wave_shade_l3<false>), grid, block, lds, s, a);
@@ -1416,11 +1404,10 @@ static void launch_stage_level(int stage, bool first, const RenderArgs &a, dim3 
 		}
 		break;
 	}
-	default: hipLaunchKernelGGL((k_wave_tail<kLevel>), grid, block, 0, s, a); break;
 	}
 }
 
-void launch_wave_stage(int stage, int level, bool first, const RenderArgs &a, unsigned grid_blocks, unsigned n_cus, hipStream_t s)
+void launch_wave_stage(WaveStage stage, int level, bool first, const RenderArgs &a, unsigned grid_blocks, unsigned n_cus, hipStream_t s)
 {
 	if (level >= 3) launch_stage_level<3>(stage, first, a, dim3(grid_blocks), n_cus, s);
 	else launch_stage_level<2>(stage, first, a, dim3(grid_blocks), n_cus, s);

@@ -578,6 +578,10 @@ def test_two_passes_in_flight_equal_one_at_a_time(which):
         kt = g.sdTree.readKernelTiming()
         if kt.trace_launches:  # the split pipeline ran: k_wave_guide exactly when asked for (or implied by the overlap)
             assert (kt.guide_launches > 0) == bool(stages == 2 or overlap)
+            # the timers of the bounce kernels: one bounce per k_wave_trace; the joint k_wave_shade is timed as k_wave_shade_a
+            assert kt.bounce_launches == kt.trace_launches
+            if stages == 0 and not overlap:
+                assert kt.shadow_ms == kt.guide_ms == kt.shade_b_ms == 0 and kt.shade_ms == kt.shade_a_ms
         return out
 
     def same(a, b):
