@@ -324,19 +324,12 @@ __global__ __launch_bounds__(kRBlock) void k_bounce(RenderArgs a)
 	__shared__ uint32_t s_wave[kRBlock / 64];
 	__shared__ uint32_t s_base;
 	__shared__ float s_stash[kBounceStash][kRBlock];
-	const uint64_t tid = (uint64_t)blockIdx.x * kRBlock + threadIdx.x;
-	const uint64_t live = kFirst ? a.n_lanes : (uint64_t)live_final(a, a.bounce - 1);
-	if ((uint64_t)blockIdx.x * kRBlock >= live) return; // whole workgroup past the list
-	if (!kFirst && tail_took_over(a, a.bounce)) return;  // a tail launch is finishing these paths
+	uint64_t tid;
+	bool alive;
+	if (!wave_entry<kFirst>(a, tid, alive)) return; // whole workgroup past the list, or a tail launch is finishing these paths
 	if (a.guided || a.record) stage_kd_planes(s_planes, a.tree); // (a recorded vertex descends the KD tree too: its accumulators)
-	const bool alive = tid < live;
 	const uint64_t lane = alive ? (kFirst ? tid : (uint64_t)a.order_in[tid]) : 0;
-	// records of the earlier bounces: all paths for the first, the survivors of bounce j for bounce j+1
-	uint64_t rec_base = 0;
-	if (!kFirst) {
-		rec_base = a.n_lanes;
-		for (int j = 0; j + 1 < a.bounce; ++j) rec_base += live_final(a, j);
-	}
+	const uint64_t rec_base = kFirst ? 0 : records_before(a);
 	bool cont = false;
 	if (alive) cont = bounce_lane<kFirst, kGeneral, true>(a, s_kd, lane, rec_base + tid, (uint32_t)a.bounce, (LdsFloat *)&s_stash[0][threadIdx.x]);
 	if (a.last) return; // nothing survives the last bounce
@@ -376,23 +369,12 @@ __global__ __launch_bounds__(kRBlock) void k_bounce_tail(RenderArgs a)
 	if (a.guided || a.record) stage_kd_planes(s_planes, a.tree); // (a recorded vertex descends the KD tree too: its accumulators)
 	bool alive = tid < live;
 	const uint64_t lane = alive ? (uint64_t)a.order_in[tid] : 0;
-	uint64_t rec_base = a.n_lanes; // entries of the bounces before a.bounce
-	for (int j = 0; j + 1 < a.bounce; ++j) rec_base += live_final(a, j);
+	const uint64_t rec_base = records_before(a);
 	const uint64_t tail_base = rec_base + live; // behind the entries of bounce a.bounce
 	uint64_t slot = rec_base + tid;
-	const unsigned wl = threadIdx.x & 63u;
 	for (int depth = a.bounce; depth < a.max_depth; ++depth) {
 		if (alive) alive = bounce_lane<false, kGeneral>(a, s_kd, lane, slot, (uint32_t)depth);
-		const unsigned long long ballot = __ballot(alive);
-		if (ballot == 0ull) break; // (nothing survives the last bounce)
-		const uint32_t n = (uint32_t)__popcll(ballot);
-		uint32_t off = 0;
-		if (wl == (unsigned)__builtin_ctzll(ballot)) {
-			atomicAdd(&a.live_count[depth], n);
-			off = atomicAdd(&a.live_count[a.max_depth], n);
-		}
-		off = __shfl(off, __builtin_ctzll(ballot), 64);
-		slot = tail_base + off + (uint32_t)__popcll(ballot & ((1ull << wl) - 1ull));
+		if (!tail_next_slot(a, depth, alive, tail_base, slot)) break;
 	}
 }
 

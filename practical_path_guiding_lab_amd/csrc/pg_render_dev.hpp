@@ -1204,10 +1204,9 @@ struct RenderArgs {
 	uint2 *r_slot;
 	uint32_t *r_tree;
 	// mesh scenes (the split pipeline of pg_render_wave.hip): the state of a path between two bounces travels with
-	// its place in the live list (pg_render_wave.hip, st_load): five 16-byte entries st[q * n_lanes + place] and the
-	// sampler increment, read from st_in / inc_in and written -- survivors only, to their places in the next list --
-	// to st_out / inc_out; the two sets swap per bounce.  L is the OUTPUT column (written once per path, where it
-	// ends); ray_d, thr, prev_p, prev_pdf, prev_quad, rng_state, rng_inc, ior and the order lists are not used.
+	// its place in the live list (the path-state table of pg_render_wave.hip, PS_*), read from st_in / inc_in and written
+	// -- survivors only, to their places in the next list -- to st_out / inc_out; the two sets swap per bounce.  L is the
+	// OUTPUT column (written once per path, where it ends); ray_d, thr, prev_p, prev_pdf, prev_quad, rng_state, rng_inc, ior and the order lists are not used.
 	// `ws` is the per-bounce workspace -- planes of n_lanes 32-bit words indexed by the place in the live list --
 	// and bvh_ovf the overflow strips of the BVH stacks (kOvfStack entries per list position)
 	const uint4 *st_in;
@@ -1219,9 +1218,8 @@ struct RenderArgs {
 	uint16_t *sort_key;
 	const uint32_t *perm;
 	uint32_t n_sort; // perm covers the places [0, n_sort); a live place beyond it is served in list order
-	// ... and the 128-byte records of the paths (8 entries of 16 bytes per place: the five state entries, the sampler
-	// increment, the hit): carry_in = this bounce is sorted (k_wave_trace adds the hit, k_wave_shade_a reads the record
-	// through perm), carry_out = the next one is (k_wave_shade_b writes the survivors' records)
+	// ... and the 128-byte records of the paths (the same table's record form): carry_in = this bounce is sorted (k_wave_trace
+	// adds the hit, k_wave_shade_a reads the record through perm), carry_out = the next one is (k_wave_shade_b writes the survivors' records)
 	uint4 *carry_in, *carry_out;
 	// the split pipeline writes a path's radiance where the path ends, by lane -- scattered -- as ONE 16-byte entry of
 	// Lq; k_finish lays the output column L out from it (nullptr: the fused kernels keep L itself up to date)
@@ -1260,7 +1258,9 @@ __device__ __forceinline__ uint32_t live_final(const RenderArgs &a, int j)
 {
 	return reinterpret_cast<ConstU32Ptr>(reinterpret_cast<uintptr_t>(a.live_count))[j];
 }
-// entries of the record list ahead of bounce a.bounce's: the camera rays' and the earlier bounces' survivors
+// entries of the record list ahead of bounce a.bounce's: the camera rays' and the earlier bounces' survivors (all paths
+// for the first bounce, the survivors of bounce j for bounce j + 1).  For a.bounce > 0: the first bounce's entries start at 0,
+// which every caller knows from its kFirst / a.bounce test.
 __device__ __forceinline__ uint64_t records_before(const RenderArgs &a)
 {
 	uint64_t r = a.n_lanes;
@@ -1277,6 +1277,44 @@ __device__ __forceinline__ bool tail_took_over(const RenderArgs &a, int bounce)
 	for (int c = 4; c <= bounce; ++c)
 		if (tail_checkpoint(c, a.max_depth) && live_final(a, c - 1) <= kTailPaths) return true;
 	return false;
+}
+
+// which live-list entry does this thread serve, if any: false for a whole workgroup past the list or
+// when a tail launch is finishing the paths (both uniform over the workgroup).  Tile = workgroup: the hardware deals workgroups
+// b, b + 8, b + 16, ... to ONE of the chip's eight XCDs (MI355X_MICROARCH.md "Workgroup dispatch"), so every XCD's L2 sees every
+// eighth tile of the (sorted) list.  XCD-aware assignments were measured in round 5 and are not here any more: contiguous eighths
+// of the list per XCD lose 5 ms per step (the regions of a sorted list cost unequal amounts and a workgroup can only go to its own
+// XCD: seven wait for the eighth), runs of 4 / 16 / 160 tiles per XCD change nothing -- these kernels' time is not in L2 capacity
+// (profiles/r05/ab_xcd_tile_mapping_rejected.txt).
+template <bool kFirst>
+__device__ __forceinline__ bool wave_entry(const RenderArgs &a, uint64_t &tid, bool &alive)
+{
+	const uint64_t live = kFirst ? a.n_lanes : (uint64_t)live_final(a, a.bounce - 1);
+	const uint32_t tile = blockIdx.x;
+	tid = (uint64_t)tile * kRBlock + threadIdx.x;
+	if ((uint64_t)tile * kRBlock >= live) return false;
+	if (!kFirst && tail_took_over(a, a.bounce)) return false;
+	alive = tid < live;
+	return true;
+}
+
+// The end of a tail kernel's depth loop (k_bounce_tail, k_wave_tail): the survivors of a wave take the next record entries
+// behind tail_base, wave by wave (live_count[max_depth] counts them), and are added to live_count[depth] as the per-bounce
+// launch would have.  False when nothing of the wave survives.
+__device__ __forceinline__ bool tail_next_slot(const RenderArgs &a, int depth, bool alive, uint64_t tail_base, uint64_t &slot)
+{
+	const unsigned long long ballot = __ballot(alive);
+	if (ballot == 0ull) return false; // (nothing survives the last bounce)
+	const unsigned wl = threadIdx.x & 63u;
+	const uint32_t n = (uint32_t)__popcll(ballot);
+	uint32_t off = 0;
+	if (wl == (unsigned)__builtin_ctzll(ballot)) {
+		atomicAdd(&a.live_count[depth], n);
+		off = atomicAdd(&a.live_count[a.max_depth], n);
+	}
+	off = __shfl(off, __builtin_ctzll(ballot), 64);
+	slot = tail_base + off + (uint32_t)__popcll(ballot & ((1ull << wl) - 1ull));
+	return true;
 }
 
 

@@ -53,10 +53,10 @@ enum : int {
 	WS_OCC,
 	WS_PDF_NEE, WS_PDF_TREE,
 	// sorted bounces (pg_render_sort): k_wave_shade_a is the one kernel that reads the state through the permutation; what
-	// k_wave_guide and k_wave_shade_b need of it travels on in ten planes -- throughput (3), ior word, radiance (3), lane,
-	// sampler increment (2)
-	WS_FWD,
-	WS_COUNT = WS_FWD + 10
+	// k_wave_guide and k_wave_shade_b need of it travels on in ten planes (ws_fwd_store and its loads, below the path-state
+	// table): entry PS_THR's four words, entry PS_L's four, the two words of the sampler increment
+	WS_FWD, WS_FWD_THR = WS_FWD, WS_FWD_L = WS_FWD_THR + 4, WS_FWD_INC = WS_FWD_L + 4,
+	WS_COUNT = WS_FWD_INC + 2
 };
 
 // lane classes and switches a bounce decides in stage_a
@@ -86,14 +86,15 @@ struct StageA {
 	uint32_t flags;
 };
 
-struct GuideOut {
-	float nee_cx, nee_cy, wo_cx, wo_cy, pdf_nee, pdf_tree;
+struct GuideOut { // (as it is made: a vertex no SD-tree call has looked at -- unit pdfs, no accumulators)
+	float nee_cx = 0.0f, nee_cy = 0.0f, wo_cx = 0.0f, wo_cy = 0.0f, pdf_nee = 1.0f, pdf_tree = 1.0f;
 	v3 wo;
 	// the record's accumulators in sdTree_current (kSlotNone / kSlotRoot / rec * 4 + child, pg_descent.hpp), found by
 	// the walks of sdTree_prev this stage makes anyway; tree_flags = the KD leaf's quadtree, bit 31 = the vertex
 	// lies inside the root box and is counted (kdtree.py:193)
-	uint32_t slot_path, slot_nee, tree_flags;
+	uint32_t slot_path = kSlotNone, slot_nee = kSlotNone, tree_flags = 0u;
 };
+__device__ __forceinline__ GuideOut guide_none(v3 wo) { GuideOut g; g.wo = wo; return g; } // ... with the direction the caller has
 
 __device__ __forceinline__ Material material_of(const RenderArgs &a, int mat, v3 refl, int level)
 {
@@ -221,10 +222,7 @@ __device__ __forceinline__ void stage_guide(const RenderArgs &a, const float *s_
 	uint32_t tree_id = 0;
 	uint32_t lv;
 	unsigned c_kd = 0, c_kdq = 0, c_q = 0, c_qq = 0; // descent statistics for the byte model
-	g.nee_cx = 0.0f; g.nee_cy = 0.0f; g.wo_cx = 0.0f; g.wo_cy = 0.0f;
-	g.pdf_nee = 1.0f; g.pdf_tree = 1.0f;
-	g.wo = wo_in;
-	g.slot_path = kSlotNone; g.slot_nee = kSlotNone; g.tree_flags = 0u;
+	g = guide_none(wo_in);
 	if (active_sd_em || (do_record && a.store_nee)) dir_to_canonical(ds_d.x, ds_d.y, ds_d.z, g.nee_cx, g.nee_cy);
 	if (active_sd_em || smp_tree || bsdf_mis || do_record) { // one KD descent serves every query of the vertex
 		KdNode leaf;
@@ -404,43 +402,55 @@ __device__ __forceinline__ void camera_ray(const RenderArgs &a, uint64_t lane, P
 	ray_o = ld3(a.cam.origin);
 }
 
-// which live-list entry does this thread serve, if any: false for a whole workgroup past the list or
-// when a tail launch is finishing the paths (both uniform over the workgroup).  Tile = workgroup: the hardware deals workgroups
-// b, b + 8, b + 16, ... to ONE of the chip's eight XCDs (MI355X_MICROARCH.md "Workgroup dispatch"), so every XCD's L2 sees every
-// eighth tile of the (sorted) list.  XCD-aware assignments were measured in round 5 and are not here any more: contiguous eighths
-// of the list per XCD lose 5 ms per step (the regions of a sorted list cost unequal amounts and a workgroup can only go to its own
-// XCD: seven wait for the eighth), runs of 4 / 16 / 160 tiles per XCD change nothing -- these kernels' time is not in L2 capacity
-// (profiles/r05/ab_xcd_tile_mapping_rejected.txt).
-template <bool kFirst>
-__device__ __forceinline__ bool wave_entry(const RenderArgs &a, uint64_t &tid, bool &alive)
-{
-	const uint64_t live = kFirst ? a.n_lanes : (uint64_t)live_final(a, a.bounce - 1);
-	const uint32_t tile = blockIdx.x;
-	tid = (uint64_t)tile * kRBlock + threadIdx.x;
-	if ((uint64_t)tile * kRBlock >= live) return false;
-	if (!kFirst && tail_took_over(a, a.bounce)) return false;
-	alive = tid < live;
-	return true;
-}
-
 // The state of a path TRAVELS WITH ITS PLACE IN THE LIVE LIST: the survivor that k_wave_shade_b appends at
 // place `off` of the next bounce's list gets its state written to place `off` of the other state set (two sets,
 // swapped per bounce), so that every kernel of the next bounce reads state[place] -- whole cache lines, no
-// gather through a list of lane numbers, no dependent load before the first useful one.  Six entries per path:
-//   q 0 {ray origin, sampler state low word}   q 1 {ray direction, sampler state high word}
-//   q 2 {throughput, ior with its sign bit = "the previous lobe was a delta"}
-//   q 3 {previous vertex, previous bsdf pdf}   q 4 {radiance so far, the path's lane (pixel * spp + s)}
-//   and the sampler's increment (8 bytes)
+// gather through a list of lane numbers, no dependent load before the first useful one.  16-byte entries, in TWO FORMS with
+// one numbering: PLANES st[entry * n_lanes + place] (st_load / st_store; entries 0-4, the sampler's increment beside them in
+// inc_in / inc_out) and, on a sorted bounce, ONE 128-byte RECORD per place, carry[place * 8 + entry] (st_rec; all eight):
+//   entry        three floats       fourth word
+//   PS_RAY_O     ray origin         sampler state, low word
+//   PS_RAY_D     ray direction      sampler state, high word
+//   PS_THR       throughput         index of refraction (positive), its sign bit = "the previous lobe was a delta"
+//   PS_PREV      previous vertex    previous bsdf pdf (a float)
+//   PS_L         radiance so far    the path's lane (pixel * spp + s)
+//   PS_INC       record only: {sampler increment low word, high word, 0, 0}
+//   PS_HIT       record only: {primitive, t, u, v} of the closest hit -- zero from append_survivors, filled by k_wave_trace
+//   PS_SPARE     record only: unused, written as zero (a line written in part is read, merged and written back)
 // The radiance is written to L_out[lane] once, where the path ends.  (Round 2 kept the state in place, indexed by
 // lane: scattered 16-byte accesses whose share of each cache line shrank with every bounce's survivors.)
+enum : int { PS_RAY_O = 0, PS_RAY_D, PS_THR, PS_PREV, PS_L, PS_INC, PS_HIT, PS_SPARE, PS_ENTRIES = 8 };
 __device__ __forceinline__ uint4 st_load(const uint4 *st, const RenderArgs &a, int q, uint64_t i) { return st[(uint64_t)q * a.n_lanes + i]; }
-__device__ __forceinline__ void st_store(uint4 *st, const RenderArgs &a, int q, uint64_t i, v3 v, uint32_t w)
-{
-	st[(uint64_t)q * a.n_lanes + i] = make_uint4(__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), w);
-}
+__device__ __forceinline__ void st_store(uint4 *st, const RenderArgs &a, int q, uint64_t i, uint4 v) { st[(uint64_t)q * a.n_lanes + i] = v; }
+__device__ __forceinline__ uint4 *st_rec(uint4 *carry, uint64_t place, int entry = 0) { return carry + place * PS_ENTRIES + entry; }
+// an entry from its three floats and its fourth word, and the fields back out of it, one value each
+__device__ __forceinline__ uint4 st_q(v3 v, uint32_t w) { return make_uint4(__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), w); }
 __device__ __forceinline__ v3 st_v3(uint4 q) { return V(__uint_as_float(q.x), __uint_as_float(q.y), __uint_as_float(q.z)); }
-// q 2's fourth word: the ior (positive) with the delta bit in its sign
+__device__ __forceinline__ float st_wf(uint4 q) { return __uint_as_float(q.w); }
+__device__ __forceinline__ uint64_t st_u64(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
 __device__ __forceinline__ uint32_t st_pack_ior(float ior, bool delta) { return __float_as_uint(ior) | (delta ? 0x80000000u : 0u); }
+__device__ __forceinline__ float st_ior(uint4 q_thr) { return __uint_as_float(q_thr.w & 0x7fffffffu); }
+__device__ __forceinline__ bool st_delta(uint4 q_thr) { return (q_thr.w >> 31) != 0u; }
+__device__ __forceinline__ uint64_t st_lane(uint4 q_l) { return q_l.w; }
+__device__ __forceinline__ uint4 st_q_hit(const HitRec &h) { return make_uint4((uint32_t)h.prim, __float_as_uint(h.t), __float_as_uint(h.u), __float_as_uint(h.v)); }
+__device__ __forceinline__ HitRec st_hit(uint4 q_hit) { return HitRec{(int)q_hit.x, __uint_as_float(q_hit.y), __uint_as_float(q_hit.z), __uint_as_float(q_hit.w)}; }
+// (the hit of an unsorted bounce: k_wave_trace's four planes)
+__device__ __forceinline__ HitRec ws_hit(const RenderArgs &a, uint64_t i) { return HitRec{(int)wsu(a, WS_HIT_PRIM, i), wsf(a, WS_HIT_T, i), wsf(a, WS_HIT_U, i), wsf(a, WS_HIT_V, i)}; }
+// WS_FWD: what k_wave_shade_a read through the permutation goes on, word by word, to the kernels behind it (ws4 reads an entry back)
+__device__ __forceinline__ void wsput4(const RenderArgs &a, int plane, uint64_t i, uint4 q)
+{
+	wsputu(a, plane, i, q.x); wsputu(a, plane + 1, i, q.y); wsputu(a, plane + 2, i, q.z); wsputu(a, plane + 3, i, q.w);
+}
+__device__ __forceinline__ uint4 ws4(const RenderArgs &a, int plane, uint64_t i) { return make_uint4(wsu(a, plane, i), wsu(a, plane + 1, i), wsu(a, plane + 2, i), wsu(a, plane + 3, i)); }
+__device__ __forceinline__ void ws_fwd_store(const RenderArgs &a, uint64_t i, uint4 q_thr, uint4 q_l, uint4 q_inc)
+{
+	wsput4(a, WS_FWD_THR, i, q_thr); wsput4(a, WS_FWD_L, i, q_l);
+	wsputu(a, WS_FWD_INC, i, q_inc.x); wsputu(a, WS_FWD_INC + 1, i, q_inc.y);
+}
+// the sampler's increment of place i: forwarded on a sorted bounce (a.perm), else beside the planes
+__device__ __forceinline__ uint64_t ws_fwd_inc(const RenderArgs &a, uint64_t i) { return a.perm ? st_u64(wsu(a, WS_FWD_INC, i), wsu(a, WS_FWD_INC + 1, i)) : a.inc_in[i]; }
+// the radiance of a path that ends here (:431), written once -- one 16-byte store (k_finish lays the output column out)
+__device__ __forceinline__ void end_path(const RenderArgs &a, uint64_t lane, v3 L) { a.Lq[lane] = st_q(L, 0u); }
 
 // The sort key of a vertex (pg_sort.hip), 16 bits: the Morton code of its cell in a 32^3 grid over the SD-tree's root box
 // (15 bits) and, below it, which half of that cell along the box's longest axis (measured: 12 / 15 / 16 key bits ->
@@ -538,9 +548,9 @@ __global__ __launch_bounds__(kRBlock) void k_wave_trace(RenderArgs a)
 		// lanes ask for consecutive lines, and the detour through LDS cost 11.5 -> 12.8 ms per step:
 		// profiles/r05/ab_trace_coop_record_load_rejected.txt.)
 		const uint64_t it = alive ? tid : 0;
-		const uint4 *p0 = a.carry_in ? a.carry_in + it * 8 : a.st_in + it;
-		const uint4 *p1 = a.carry_in ? a.carry_in + it * 8 + 1 : a.st_in + a.n_lanes + it;
-		const uint4 *p5 = a.carry_in ? a.carry_in + it * 8 + 5 : p0;
+		const uint4 *p0 = a.carry_in ? st_rec(a.carry_in, it, PS_RAY_O) : a.st_in + it;
+		const uint4 *p1 = a.carry_in ? st_rec(a.carry_in, it, PS_RAY_D) : a.st_in + a.n_lanes + it;
+		const uint4 *p5 = a.carry_in ? st_rec(a.carry_in, it, PS_INC) : p0;
 		q0 = *p0; q1 = *p1; q5 = *p5;
 	}
 	__shared__ u32x4_t s_top[kBvhTopNodes * 8];
@@ -554,21 +564,21 @@ __global__ __launch_bounds__(kRBlock) void k_wave_trace(RenderArgs a)
 		camera_ray(a, tid, rng, ray_o, ray_d);
 		// (this launch FILLS the set the first bounce reads: the only writer of an "in" set)
 		const_cast<uint64_t *>(a.inc_in)[tid] = rng.inc;
-		st_store(const_cast<uint4 *>(a.st_in), a, 0, tid, ray_o, (uint32_t)rng.state);
-		st_store(const_cast<uint4 *>(a.st_in), a, 1, tid, ray_d, (uint32_t)(rng.state >> 32));
+		st_store(const_cast<uint4 *>(a.st_in), a, PS_RAY_O, tid, st_q(ray_o, (uint32_t)rng.state));
+		st_store(const_cast<uint4 *>(a.st_in), a, PS_RAY_D, tid, st_q(ray_d, (uint32_t)(rng.state >> 32)));
 	} else {
 		ray_o = st_v3(q0);
 		ray_d = st_v3(q1);
 		// (the class bit of the sort key is made HERE, ahead of the walk, from the sampler state in the two entries just read: one
 		// register through the walk instead of the state's four)
 		if (want_cls && tid < (uint64_t)a.n_sort)
-			cls_ahead = (int)lane_class_ahead((uint64_t)q0.w | ((uint64_t)q1.w << 32), (uint64_t)q5.x | ((uint64_t)q5.y << 32), a.frac);
+			cls_ahead = (int)lane_class_ahead(st_u64(q0.w, q1.w), st_u64(q5.x, q5.y), a.frac);
 	}
 	HitRec h;
 	h.u = 0.0f; h.v = 0.0f;
 	h.prim = intersect<kLevel, false>(a.shapes, ray_o, ray_d, __builtin_huge_valf(), h.t, stk, h.u, h.v);
-	if (a.carry_in) { // a sorted bounce: the hit joins the path's 128-byte record, which k_wave_shade_a reads through the permutation
-		a.carry_in[tid * 8 + 6] = make_uint4((uint32_t)h.prim, __float_as_uint(h.t), __float_as_uint(h.u), __float_as_uint(h.v));
+	if (a.carry_in) { // a sorted bounce: the hit joins the path's record (PS_HIT), which k_wave_shade_a reads through the permutation
+		*st_rec(a.carry_in, tid, PS_HIT) = st_q_hit(h);
 		if (tid < (uint64_t)a.n_sort) a.sort_key[tid] = (uint16_t)(h.prim >= 0 ? vertex_sort_key(a, vadd(ray_o, vscale(ray_d, h.t)), cls_ahead) : 0xfffeu);
 		return;
 	}
@@ -680,57 +690,11 @@ __global__ __launch_bounds__(kRBlock) __attribute__((amdgpu_waves_per_eu(7))) vo
 	}
 }
 
-
-// ---- :189-220, 272-297 ----
-// kGuide: the SD-tree calls of the bounce (stage_guide, otherwise k_wave_guide's) follow in the same kernel
-template <int kLevel, bool kFirst, bool kGuide>
-__global__ __launch_bounds__(kRBlock) void k_wave_shade_a(RenderArgs a)
+// ---- what k_wave_shade_a hands k_wave_guide, k_wave_cast and k_wave_shade_b through the workspace: stage_a's results, and which
+// lane class finds what in which plane.  ws_load_stage_a is k_wave_shade_b's side of ws_store_stage_a, condition by condition ----
+template <int kLevel, bool kGuide>
+__device__ __forceinline__ void ws_store_stage_a(const RenderArgs &a, uint64_t tid, const StageA &A)
 {
-	__shared__ float s_planes[kGuide ? 3 * kKdGridPlanes : 1];
-	uint64_t tid;
-	bool alive;
-	if (!wave_entry<kFirst>(a, tid, alive)) return;
-	if (kGuide) stage_kd_planes(s_planes, a.tree);
-	if (!alive) return;
-	Pcg32 rng;
-	v3 ray_o, ray_d, thr = V(1, 1, 1), prev_p = V(0, 0, 0);
-	float prev_pdf = 1.0f;
-	bool prev_delta = true;
-	HitRec h;
-	if (!kFirst && a.perm) {
-		// a sorted bounce: this thread serves the place the sort put k-th.  The one random pass over the state: the
-		// path's 128-byte record (k_wave_shade_b and k_wave_trace filled it) is one cache line; what k_wave_guide and
-		// k_wave_shade_b need of it travels on at k (WS_FWD), so that nothing after this kernel looks through the permutation
-		const uint4 *rec = a.carry_in + (tid < (uint64_t)a.n_sort ? (uint64_t)a.perm[tid] : tid) * 8;
-		const uint4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4], q5 = rec[5], q6 = rec[6];
-		rng.state = (uint64_t)q0.w | ((uint64_t)q1.w << 32);
-		rng.inc = (uint64_t)q5.x | ((uint64_t)q5.y << 32);
-		ray_o = st_v3(q0); ray_d = st_v3(q1);
-		thr = st_v3(q2);
-		prev_delta = (q2.w >> 31) != 0u;
-		prev_p = st_v3(q3);
-		prev_pdf = __uint_as_float(q3.w);
-		h.prim = (int)q6.x; h.t = __uint_as_float(q6.y); h.u = __uint_as_float(q6.z); h.v = __uint_as_float(q6.w);
-		wsputu(a, WS_FWD + 0, tid, q2.x); wsputu(a, WS_FWD + 1, tid, q2.y); wsputu(a, WS_FWD + 2, tid, q2.z); wsputu(a, WS_FWD + 3, tid, q2.w);
-		wsputu(a, WS_FWD + 4, tid, q4.x); wsputu(a, WS_FWD + 5, tid, q4.y); wsputu(a, WS_FWD + 6, tid, q4.z); wsputu(a, WS_FWD + 7, tid, q4.w);
-		wsputu(a, WS_FWD + 8, tid, q5.x); wsputu(a, WS_FWD + 9, tid, q5.y);
-	} else {
-		const uint4 q0 = st_load(a.st_in, a, 0, tid), q1 = st_load(a.st_in, a, 1, tid);
-		rng.state = (uint64_t)q0.w | ((uint64_t)q1.w << 32);
-		rng.inc = a.inc_in[tid];
-		ray_o = st_v3(q0); ray_d = st_v3(q1);
-		if (!kFirst) {
-			const uint4 q2 = st_load(a.st_in, a, 2, tid), q3 = st_load(a.st_in, a, 3, tid);
-			thr = st_v3(q2);
-			prev_delta = (q2.w >> 31) != 0u;
-			prev_p = st_v3(q3);
-			prev_pdf = __uint_as_float(q3.w);
-		}
-		h.prim = (int)wsu(a, WS_HIT_PRIM, tid);
-		h.t = wsf(a, WS_HIT_T, tid); h.u = wsf(a, WS_HIT_U, tid); h.v = wsf(a, WS_HIT_V, tid);
-	}
-	StageA A;
-	stage_a<kLevel>(a, rng, ray_o, ray_d, thr, prev_p, prev_pdf, prev_delta, h, (uint32_t)a.bounce, A);
 	// (storing a value for some lanes of a wave only saves nothing by itself -- the partial store touches the same
 	// sectors -- which is why the two classes of lanes share planes instead: WS_U; making every lane store so that no
 	// line is written in part was measured too: no different, 84.0 vs 84.8 ms per step)
@@ -752,17 +716,84 @@ __global__ __launch_bounds__(kRBlock) void k_wave_shade_a(RenderArgs a)
 		wsput3(a, WS_SH_O, tid, A.sh_o); wsput3(a, WS_SH_D, tid, A.sh_d); wsput(a, WS_SH_T, tid, A.sh_tmax);
 	}
 	if (kLevel >= 3) wsput(a, WS_ETA, tid, A.eta); // (:357: only the dielectrics of level 3 have an eta other than 1)
+}
+template <int kLevel>
+__device__ __forceinline__ void ws_load_stage_a(const RenderArgs &a, uint64_t tid, StageA &A)
+{
+	A.flags = wsu(a, WS_FLAGS, tid);
+	A.p = ws3(a, WS_P, tid); A.ng = ws3(a, WS_NG, tid);
+	A.n = V(0, 0, 1); A.wi = V(0, 0, 1); A.mat = 0; A.refl = V(0, 0, 0);
+	if (A.flags & F_SMP_TREE) { // (only these lanes evaluate their BSDF again)
+		A.n = ws3(a, WS_U, tid); A.wi = ws3(a, WS_U + 3, tid);
+		A.mat = (int)wsu(a, WS_U + 6, tid); A.refl = ws3(a, WS_U + 7, tid);
+	}
+	A.Le = (A.flags & F_HAS_LE) ? ws3(a, WS_LE, tid) : V(0, 0, 0);
+	A.ds_d = V(0, 0, 0); // (stage_b does not read it: the record takes the canonical form k_wave_guide made)
+	A.ds_pdf = 0.0f; A.em_w = V(0, 0, 0); A.bv_em = V(0, 0, 0); A.bp_em = 0.0f;
+	if (A.flags & F_NEE_LIVE) {
+		A.ds_pdf = wsf(a, WS_DS_PDF, tid); A.em_w = ws3(a, WS_EM_W, tid);
+		A.bv_em = ws3(a, WS_BV_EM, tid); A.bp_em = wsf(a, WS_BP_EM, tid);
+	}
+	// (a tree-sampling lane's own BSDF sample is not used again: its direction comes from k_wave_guide, its
+	// value and pdf from the evaluation in stage_b -- only the sample's eta is, :357)
+	A.wo = V(0, 0, 0); A.bsdf_pdf = 0.0f; A.bsdf_w = V(0, 0, 0);
+	if (A.flags & F_SMP_TREE) A.wo = ws3(a, WS_WO_T, tid);
+	else { A.wo = ws3(a, WS_U, tid); A.bsdf_w = ws3(a, WS_U + 3, tid); A.bsdf_pdf = wsf(a, WS_U + 6, tid); }
+	A.eta = kLevel >= 3 ? wsf(a, WS_ETA, tid) : 1.0f;
+}
+
+// ---- :189-220, 272-297 ----
+// kGuide: the SD-tree calls of the bounce (stage_guide, otherwise k_wave_guide's) follow in the same kernel
+template <int kLevel, bool kFirst, bool kGuide>
+__global__ __launch_bounds__(kRBlock) void k_wave_shade_a(RenderArgs a)
+{
+	__shared__ float s_planes[kGuide ? 3 * kKdGridPlanes : 1];
+	uint64_t tid;
+	bool alive;
+	if (!wave_entry<kFirst>(a, tid, alive)) return;
+	if (kGuide) stage_kd_planes(s_planes, a.tree);
+	if (!alive) return;
+	Pcg32 rng;
+	v3 ray_o, ray_d, thr = V(1, 1, 1), prev_p = V(0, 0, 0);
+	float prev_pdf = 1.0f;
+	bool prev_delta = true;
+	HitRec h;
+	if (!kFirst && a.perm) {
+		// a sorted bounce: this thread serves the place the sort put k-th.  The one random pass over the state: the
+		// path's record (k_wave_shade_b and k_wave_trace filled it) is one cache line; what k_wave_guide and
+		// k_wave_shade_b need of it travels on at k (WS_FWD), so that nothing after this kernel looks through the permutation
+		const uint4 *rec = st_rec(a.carry_in, tid < (uint64_t)a.n_sort ? (uint64_t)a.perm[tid] : tid);
+		const uint4 q0 = rec[PS_RAY_O], q1 = rec[PS_RAY_D], q2 = rec[PS_THR], q3 = rec[PS_PREV], q4 = rec[PS_L], q5 = rec[PS_INC], q6 = rec[PS_HIT];
+		rng.state = st_u64(q0.w, q1.w);
+		rng.inc = st_u64(q5.x, q5.y);
+		ray_o = st_v3(q0); ray_d = st_v3(q1);
+		thr = st_v3(q2);
+		prev_delta = st_delta(q2);
+		prev_p = st_v3(q3);
+		prev_pdf = st_wf(q3);
+		h = st_hit(q6);
+		ws_fwd_store(a, tid, q2, q4, q5);
+	} else {
+		const uint4 q0 = st_load(a.st_in, a, PS_RAY_O, tid), q1 = st_load(a.st_in, a, PS_RAY_D, tid);
+		rng.state = st_u64(q0.w, q1.w);
+		rng.inc = a.inc_in[tid];
+		ray_o = st_v3(q0); ray_d = st_v3(q1);
+		if (!kFirst) {
+			const uint4 q2 = st_load(a.st_in, a, PS_THR, tid), q3 = st_load(a.st_in, a, PS_PREV, tid);
+			thr = st_v3(q2);
+			prev_delta = st_delta(q2);
+			prev_p = st_v3(q3);
+			prev_pdf = st_wf(q3);
+		}
+		h = ws_hit(a, tid);
+	}
+	StageA A;
+	stage_a<kLevel>(a, rng, ray_o, ray_d, thr, prev_p, prev_pdf, prev_delta, h, (uint32_t)a.bounce, A);
+	ws_store_stage_a<kLevel, kGuide>(a, tid, A);
 	if (kGuide && guide_has_work(a, A.flags)) { // what k_wave_guide does, with its inputs still in registers
 		GuideOut g;
 		stage_guide(a, s_planes, rng, A.p, A.ds_d, (A.flags & F_SMP_TREE) ? V(0, 0, 0) : A.wo, A.flags, g);
-		if (a.record && (A.flags & F_VALID)) {
-			uint64_t rec_base = 0;
-			if (!kFirst) {
-				rec_base = a.n_lanes;
-				for (int j = 0; j + 1 < a.bounce; ++j) rec_base += live_final(a, j);
-			}
-			store_slots(a, rec_base + tid, g);
-		}
+		if (a.record && (A.flags & F_VALID)) store_slots(a, (kFirst ? 0 : records_before(a)) + tid, g);
 		wsput(a, WS_PDF_NEE, tid, g.pdf_nee); wsput(a, WS_PDF_TREE, tid, g.pdf_tree);
 		if (A.flags & F_SMP_TREE) wsput3(a, WS_WO_T, tid, g.wo);
 	}
@@ -793,20 +824,13 @@ __global__ __launch_bounds__(kRBlock) void k_wave_guide(RenderArgs a)
 	                  "+v"(u_in.z), "+v"(rng_lo), "+v"(rng_hi));
 	if (!guide_has_work(a, flags)) return;
 	Pcg32 rng;
-	rng.state = (uint64_t)rng_lo | ((uint64_t)rng_hi << 32);
-	rng.inc = a.perm ? ((uint64_t)wsu(a, WS_FWD + 8, tid) | ((uint64_t)wsu(a, WS_FWD + 9, tid) << 32)) : a.inc_in[tid];
+	rng.state = st_u64(rng_lo, rng_hi);
+	rng.inc = ws_fwd_inc(a, tid);
 	GuideOut g;
 	// (the BSDF-sampled direction of a lane that keeps it; a lane that samples the tree has none to evaluate)
 	const v3 wo_in = (flags & F_SMP_TREE) ? V(0, 0, 0) : u_in;
 	stage_guide(a, s_planes, rng, p_in, ds_in, wo_in, flags, g);
-	if (a.record && (flags & F_VALID)) { // the entry k_wave_shade_b fills for this vertex
-		uint64_t rec_base = 0;
-		if (a.bounce > 0) {
-			rec_base = a.n_lanes;
-			for (int j = 0; j + 1 < a.bounce; ++j) rec_base += live_final(a, j);
-		}
-		store_slots(a, rec_base + tid, g);
-	}
+	if (a.record && (flags & F_VALID)) store_slots(a, (a.bounce > 0 ? records_before(a) : 0) + tid, g); // the entry k_wave_shade_b fills for this vertex
 	wsput(a, WS_PDF_NEE, tid, g.pdf_nee); wsput(a, WS_PDF_TREE, tid, g.pdf_tree);
 	if (flags & F_SMP_TREE) {
 		wsput3(a, WS_WO_T, tid, g.wo);
@@ -821,6 +845,18 @@ __device__ __forceinline__ void append_survivors(const RenderArgs &a, bool cont,
                                                  float prev_pdf, v3 L, uint64_t lane, const Pcg32 &rng, uint32_t *s_wave, uint32_t &s_base,
                                                  uint32_t (*s_oct)[8], uint4 *s_rec)
 {
+	// entry k of the survivor's state (the path-state table above): the record takes all eight, the planes the first five
+	const auto entry = [&](int k) {
+		switch (k) {
+		case PS_RAY_O: return st_q(ray_o, (uint32_t)rng.state);
+		case PS_RAY_D: return st_q(ray_d, (uint32_t)(rng.state >> 32));
+		case PS_THR: return st_q(thr, st_pack_ior(ior, delta));
+		case PS_PREV: return st_q(p_here, __float_as_uint(prev_pdf));
+		case PS_L: return st_q(L, (uint32_t)lane);
+		case PS_INC: return make_uint4((uint32_t)rng.inc, (uint32_t)(rng.inc >> 32), 0u, 0u);
+		default: return make_uint4(0u, 0u, 0u, 0u); // (PS_HIT: k_wave_trace; PS_SPARE)
+		}
+	};
 	if (a.last) return; // nothing survives the last bounce
 	const unsigned long long ballot = __ballot(cont);
 	const unsigned wl = threadIdx.x & 63u, wv = threadIdx.x >> 6;
@@ -850,7 +886,7 @@ __device__ __forceinline__ void append_survivors(const RenderArgs &a, bool cont,
 		for (unsigned w = 0; w < wv; ++w) off += s_oct[w][oct];           // (this bin, the earlier waves)
 	}
 	if (a.carry_out) {
-		// the next bounce is sorted: the state goes into ONE 128-byte record per path and nowhere else -- the kernel that
+		// the next bounce is sorted: the state goes into ONE record per path and nowhere else -- the kernel that
 		// looks through the permutation reads it as one cache line; k_wave_trace takes the ray from it and adds the hit.
 		// The records are written as WHOLE lines, all 128 bytes of each, by consecutive threads, through LDS, kStage
 		// records at a time: 96 of the 128 bytes -- by the lanes themselves or through LDS alike -- cost k_wave_shade_b
@@ -858,33 +894,25 @@ __device__ __forceinline__ void append_survivors(const RenderArgs &a, bool cont,
 		uint32_t tot = 0;
 		for (int w = 0; w < kRBlock / 64; ++w) tot += s_wave[w];
 		const uint32_t idx = cont ? off - s_base : 0xffffffffu;
-		uint4 *dst = a.carry_out + (uint64_t)s_base * 8;
+		uint4 *dst = st_rec(a.carry_out, s_base);
 		for (uint32_t h = 0; h < tot; h += (uint32_t)kStage) { // (uniform over the workgroup)
 			if (h) __syncthreads(); // (the round before has been copied out)
 			if (idx >= h && idx < h + (uint32_t)kStage) {
-				uint4 *rec = s_rec + (idx - h) * 8u;
-				rec[0] = make_uint4(__float_as_uint(ray_o.x), __float_as_uint(ray_o.y), __float_as_uint(ray_o.z), (uint32_t)rng.state);
-				rec[1] = make_uint4(__float_as_uint(ray_d.x), __float_as_uint(ray_d.y), __float_as_uint(ray_d.z), (uint32_t)(rng.state >> 32));
-				rec[2] = make_uint4(__float_as_uint(thr.x), __float_as_uint(thr.y), __float_as_uint(thr.z), st_pack_ior(ior, delta));
-				rec[3] = make_uint4(__float_as_uint(p_here.x), __float_as_uint(p_here.y), __float_as_uint(p_here.z), __float_as_uint(prev_pdf));
-				rec[4] = make_uint4(__float_as_uint(L.x), __float_as_uint(L.y), __float_as_uint(L.z), (uint32_t)lane);
-				rec[5] = make_uint4((uint32_t)rng.inc, (uint32_t)(rng.inc >> 32), 0u, 0u);
-				rec[6] = make_uint4(0u, 0u, 0u, 0u); rec[7] = make_uint4(0u, 0u, 0u, 0u); // (the hit: k_wave_trace; spare)
+				uint4 *rec = st_rec(s_rec, idx - h);
+#pragma unroll
+				for (int k = 0; k < PS_ENTRIES; ++k) rec[k] = entry(k);
 			}
 			__syncthreads();
 			const uint32_t n = tot - h < (uint32_t)kStage ? tot - h : (uint32_t)kStage;
-			for (uint32_t j = threadIdx.x; j < n * 8u; j += kRBlock) { // (streaming stores: see PG_ST)
+			for (uint32_t j = threadIdx.x; j < n * PS_ENTRIES; j += kRBlock) { // (streaming stores: see PG_ST)
 				const uint4 q = s_rec[j];
 				const u32x4_t v = {q.x, q.y, q.z, q.w};
-				__builtin_nontemporal_store(v, reinterpret_cast<u32x4_t *>(dst + (uint64_t)h * 8 + j));
+				__builtin_nontemporal_store(v, reinterpret_cast<u32x4_t *>(st_rec(dst, h) + j));
 			}
 		}
 	} else if (cont) {
-		st_store(a.st_out, a, 0, off, ray_o, (uint32_t)rng.state);
-		st_store(a.st_out, a, 1, off, ray_d, (uint32_t)(rng.state >> 32));
-		st_store(a.st_out, a, 2, off, thr, st_pack_ior(ior, delta));
-		st_store(a.st_out, a, 3, off, p_here, __float_as_uint(prev_pdf));
-		st_store(a.st_out, a, 4, off, L, (uint32_t)lane);
+#pragma unroll
+		for (int k = 0; k < PS_INC; ++k) st_store(a.st_out, a, k, off, entry(k));
 		a.inc_out[off] = rng.inc;
 	}
 }
@@ -900,12 +928,7 @@ __global__ __launch_bounds__(kRBlock) void k_wave_shade_b(RenderArgs a)
 	uint64_t tid;
 	bool alive;
 	if (!wave_entry<kFirst>(a, tid, alive)) return;
-	// records of the earlier bounces: all paths for the first, the survivors of bounce j for bounce j+1
-	uint64_t rec_base = 0;
-	if (!kFirst) {
-		rec_base = a.n_lanes;
-		for (int j = 0; j + 1 < a.bounce; ++j) rec_base += live_final(a, j);
-	}
+	const uint64_t rec_base = kFirst ? 0 : records_before(a);
 	bool cont = false;
 	// what a survivor takes along to its place in the next list
 	v3 ray_o = V(0, 0, 0), ray_d = V(0, 0, 1), thr = V(1, 1, 1), L = V(0, 0, 0), p_here = V(0, 0, 0);
@@ -916,53 +939,32 @@ __global__ __launch_bounds__(kRBlock) void k_wave_shade_b(RenderArgs a)
 	rng.state = 0; rng.inc = 1;
 	if (alive) {
 		StageA A;
-		A.flags = wsu(a, WS_FLAGS, tid);
-		A.p = ws3(a, WS_P, tid); A.ng = ws3(a, WS_NG, tid);
-		A.n = V(0, 0, 1); A.wi = V(0, 0, 1); A.mat = 0; A.refl = V(0, 0, 0);
-		if (A.flags & F_SMP_TREE) { // (only these lanes evaluate their BSDF again)
-			A.n = ws3(a, WS_U, tid); A.wi = ws3(a, WS_U + 3, tid);
-			A.mat = (int)wsu(a, WS_U + 6, tid); A.refl = ws3(a, WS_U + 7, tid);
-		}
-		A.Le = (A.flags & F_HAS_LE) ? ws3(a, WS_LE, tid) : V(0, 0, 0);
-		A.ds_d = V(0, 0, 0); // (stage_b does not read it: the record takes the canonical form k_wave_guide made)
-		A.ds_pdf = 0.0f; A.em_w = V(0, 0, 0); A.bv_em = V(0, 0, 0); A.bp_em = 0.0f;
-		if (A.flags & F_NEE_LIVE) {
-			A.ds_pdf = wsf(a, WS_DS_PDF, tid); A.em_w = ws3(a, WS_EM_W, tid);
-			A.bv_em = ws3(a, WS_BV_EM, tid); A.bp_em = wsf(a, WS_BP_EM, tid);
-		}
-		// (a tree-sampling lane's own BSDF sample is not used again: its direction comes from k_wave_guide, its
-		// value and pdf from the evaluation in stage_b -- only the sample's eta is, :357)
-		A.wo = V(0, 0, 0); A.bsdf_pdf = 0.0f; A.bsdf_w = V(0, 0, 0);
-		if (A.flags & F_SMP_TREE) A.wo = ws3(a, WS_WO_T, tid);
-		else { A.wo = ws3(a, WS_U, tid); A.bsdf_w = ws3(a, WS_U + 3, tid); A.bsdf_pdf = wsf(a, WS_U + 6, tid); }
-		A.eta = kLevel >= 3 ? wsf(a, WS_ETA, tid) : 1.0f;
-		GuideOut g;
-		g.nee_cx = 0.0f; g.nee_cy = 0.0f; g.wo_cx = 0.0f; g.wo_cy = 0.0f; g.pdf_nee = 1.0f; g.pdf_tree = 1.0f;
-		g.slot_path = kSlotNone; g.slot_nee = kSlotNone; g.tree_flags = 0u; // (k_wave_guide has put them into the record list)
-		g.wo = A.wo; // (k_wave_guide's direction for the lanes that sample the tree)
+		ws_load_stage_a<kLevel>(a, tid, A);
+		// (the accumulators: k_wave_guide has put them into the record list; its direction for the lanes that sample the tree)
+		GuideOut g = guide_none(A.wo);
 		if (guide_has_work(a, A.flags)) { g.pdf_nee = wsf(a, WS_PDF_NEE, tid); g.pdf_tree = wsf(a, WS_PDF_TREE, tid); }
 		const bool occluded = (A.flags & F_NEED_SHADOW) && wsu(a, WS_OCC, tid) != 0u;
-		rng.state = (uint64_t)wsu(a, WS_RNG_LO, tid) | ((uint64_t)wsu(a, WS_RNG_HI, tid) << 32);
-		rng.inc = a.perm ? ((uint64_t)wsu(a, WS_FWD + 8, tid) | ((uint64_t)wsu(a, WS_FWD + 9, tid) << 32)) : a.inc_in[tid];
+		rng.state = st_u64(wsu(a, WS_RNG_LO, tid), wsu(a, WS_RNG_HI, tid));
+		rng.inc = ws_fwd_inc(a, tid);
 		if (!kFirst) {
 			uint4 q2, q4;
 			if (a.perm) { // (a sorted bounce: k_wave_shade_a has brought them along)
-				q2 = make_uint4(wsu(a, WS_FWD + 0, tid), wsu(a, WS_FWD + 1, tid), wsu(a, WS_FWD + 2, tid), wsu(a, WS_FWD + 3, tid));
-				q4 = make_uint4(wsu(a, WS_FWD + 4, tid), wsu(a, WS_FWD + 5, tid), wsu(a, WS_FWD + 6, tid), wsu(a, WS_FWD + 7, tid));
+				q2 = ws4(a, WS_FWD_THR, tid);
+				q4 = ws4(a, WS_FWD_L, tid);
 			} else {
-				q2 = st_load(a.st_in, a, 2, tid);
-				q4 = st_load(a.st_in, a, 4, tid);
+				q2 = st_load(a.st_in, a, PS_THR, tid);
+				q4 = st_load(a.st_in, a, PS_L, tid);
 			}
 			thr = st_v3(q2);
-			ior = __uint_as_float(q2.w & 0x7fffffffu);
+			ior = st_ior(q2);
 			L = st_v3(q4);
-			lane = q4.w;
+			lane = st_lane(q4);
 		}
 		cont = stage_b<kLevel>(a, rng, thr, L, ior, A, g, occluded, lane, rec_base + tid, (uint32_t)a.bounce, ray_o, ray_d,
 		                       prev_pdf, delta);
 		p_here = A.p;
 		if (kFirst) a.hit0[lane] = (A.flags & F_VALID) ? 1 : 0;
-		if (!cont) a.Lq[lane] = make_uint4(__float_as_uint(L.x), __float_as_uint(L.y), __float_as_uint(L.z), 0u); // the path ends here: its radiance (:431), written once -- one 16-byte store (k_finish lays the output column out)
+		if (!cont) end_path(a, lane, L);
 	}
 	append_survivors<kRBlock>(a, cont, ray_o, ray_d, thr, ior, delta, p_here, prev_pdf, L, lane, rng, s_wave, s_base, s_oct, s_rec);
 }
@@ -985,7 +987,7 @@ static_assert(kShadeStack >= kMinLdsStack && kShadeStack <= kLdsStack, "k_wave_s
 // refraction and the lane stay in registers -- rounds 4-5 measured the other splits)
 constexpr int kShadeStash = 12;
 constexpr int kShadeWalkQuads = kShadeStack * kRBlock / 2 + kShadeTopNodes * 8 + kShadeStash * kRBlock / 4;
-constexpr int kShadeLdsQuads = kShadeStage * 8 > kShadeWalkQuads ? kShadeStage * 8 : kShadeWalkQuads;
+constexpr int kShadeLdsQuads = kShadeStage * PS_ENTRIES > kShadeWalkQuads ? kShadeStage * PS_ENTRIES : kShadeWalkQuads;
 // (122 vector registers, four waves per SIMD, which is also what 33 KB of LDS per workgroup allow.  Measured: staging the
 // records 128 at a time -- 23 KB -- changes nothing by itself, and compiled for five waves on top of that the kernel spills
 // 31 registers: 35.2 -> 37.6 ms per step.)
@@ -996,7 +998,7 @@ constexpr int kShadeLdsQuads = kShadeStage * 8 > kShadeWalkQuads ? kShadeStage *
 // 64 records in eight loads of 8 lines instead of seven of 64.  The entries cross to the lanes that own them through LDS
 // ([entry][thread] planes over the bytes the walks' stacks and the stash use later: one more workgroup barrier, ahead of the
 // staging of the BVH's top).
-static_assert(7 * kRBlock <= kShadeLdsQuads, "k_wave_shade: the records' seven entries per thread must fit the dynamic LDS");
+static_assert(PS_SPARE * kRBlock <= kShadeLdsQuads, "k_wave_shade: the records' seven entries per thread must fit the dynamic LDS");
 template <int kLevel, bool kFirst>
 __device__ __forceinline__ void shade_body(const RenderArgs &a)
 {
@@ -1074,20 +1076,20 @@ __device__ __forceinline__ void shade_body(const RenderArgs &a)
 		for (uint32_t k = 0; k < 8u; ++k) {
 			const uint32_t j = k * 8u + (l >> 3);
 			const uint32_t pj = (uint32_t)__shfl((int)coop_place, (int)j, 64);
-			g[k] = gather16(a.carry_in + (uint64_t)pj * 8 + q);
+			g[k] = gather16(st_rec(a.carry_in, pj, (int)q));
 		}
 #pragma unroll
 		for (uint32_t k = 0; k < 8u; ++k)
-			if (q < 7u) s_dyn[q * kRBlock + wbase + k * 8u + (l >> 3)] = g[k];
+			if (q < (uint32_t)PS_SPARE) s_dyn[q * kRBlock + wbase + k * 8u + (l >> 3)] = g[k];
 		// (written and read by the same wave: its LDS operations complete in order, so no workgroup barrier -- but the lanes read
 		// entries OTHER lanes wrote, which the memory model only orders through a release / acquire pair at wavefront scope; the
 		// fences and the wave barrier emit no instruction, they pin the order for the compiler: ADVICE r5)
 		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 		__builtin_amdgcn_wave_barrier();
 		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-		cq0 = s_dyn[0 * kRBlock + threadIdx.x]; cq1 = s_dyn[1 * kRBlock + threadIdx.x]; cq2 = s_dyn[2 * kRBlock + threadIdx.x];
-		cq3 = s_dyn[3 * kRBlock + threadIdx.x]; cq4 = s_dyn[4 * kRBlock + threadIdx.x]; cq5 = s_dyn[5 * kRBlock + threadIdx.x];
-		cq6 = s_dyn[6 * kRBlock + threadIdx.x];
+		cq0 = s_dyn[PS_RAY_O * kRBlock + threadIdx.x]; cq1 = s_dyn[PS_RAY_D * kRBlock + threadIdx.x]; cq2 = s_dyn[PS_THR * kRBlock + threadIdx.x];
+		cq3 = s_dyn[PS_PREV * kRBlock + threadIdx.x]; cq4 = s_dyn[PS_L * kRBlock + threadIdx.x]; cq5 = s_dyn[PS_INC * kRBlock + threadIdx.x];
+		cq6 = s_dyn[PS_HIT * kRBlock + threadIdx.x];
 		__syncthreads(); // every wave has its entries: the bytes become the BVH's top, the stacks and the stash
 	}
 	uint2 *s_stack = reinterpret_cast<uint2 *>(s_dyn);
@@ -1113,8 +1115,7 @@ __device__ __forceinline__ void shade_body(const RenderArgs &a)
 	rng.state = 0; rng.inc = 1;
 	uint64_t rec_base = 0;
 	if (!kFirst) {
-		rec_base = a.n_lanes;
-		for (int j = 0; j + 1 < a.bounce; ++j) rec_base += live_final(a, j);
+		rec_base = records_before(a);
 		// (the same number in every lane, but read by vector loads -- live_count is written by this very grid -- so the
 		// compiler keeps it in two vector registers through the whole kernel unless it is told that it is uniform)
 		rec_base = (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)rec_base) |
@@ -1130,34 +1131,33 @@ __device__ __forceinline__ void shade_body(const RenderArgs &a)
 		uint32_t place = (uint32_t)tid; // (32-bit: a place in the live list; one register through the walks, not two)
 		if (!coop && from_rec && tid < (uint64_t)a.n_sort) place = a.perm[tid];
 		if (from_rec) {
-			const uint4 *rec = a.carry_in + (uint64_t)place * 8;
+			const uint4 *rec = st_rec(a.carry_in, place);
 			uint4 q0, q1, q2, q3, q5, q6;
 			if (coop) { q0 = cq0; q1 = cq1; q2 = cq2; q3 = cq3; q5 = cq5; q6 = cq6; }
-			else { q0 = rec[0]; q1 = rec[1]; q2 = rec[2]; q3 = rec[3]; q5 = rec[5]; q6 = rec[6]; }
-			rng.state = (uint64_t)q0.w | ((uint64_t)q1.w << 32);
-			rng.inc = (uint64_t)q5.x | ((uint64_t)q5.y << 32);
+			else { q0 = rec[PS_RAY_O]; q1 = rec[PS_RAY_D]; q2 = rec[PS_THR]; q3 = rec[PS_PREV]; q5 = rec[PS_INC]; q6 = rec[PS_HIT]; }
+			rng.state = st_u64(q0.w, q1.w);
+			rng.inc = st_u64(q5.x, q5.y);
 			ray_o = st_v3(q0); ray_d = st_v3(q1);
 			thr = st_v3(q2);
-			{ const uint4 q4 = coop ? cq4 : rec[4]; ior = __uint_as_float(q2.w & 0x7fffffffu); L = st_v3(q4); lane = q4.w; }
-			prev_delta = (q2.w >> 31) != 0u;
+			{ const uint4 q4 = coop ? cq4 : rec[PS_L]; ior = st_ior(q2); L = st_v3(q4); lane = st_lane(q4); }
+			prev_delta = st_delta(q2);
 			prev_p = st_v3(q3);
-			prev_pdf = __uint_as_float(q3.w);
-			h.prim = (int)q6.x; h.t = __uint_as_float(q6.y); h.u = __uint_as_float(q6.z); h.v = __uint_as_float(q6.w);
+			prev_pdf = st_wf(q3);
+			h = st_hit(q6);
 		} else {
-			const uint4 q0 = st_load(a.st_in, a, 0, tid), q1 = st_load(a.st_in, a, 1, tid);
-			rng.state = (uint64_t)q0.w | ((uint64_t)q1.w << 32);
+			const uint4 q0 = st_load(a.st_in, a, PS_RAY_O, tid), q1 = st_load(a.st_in, a, PS_RAY_D, tid);
+			rng.state = st_u64(q0.w, q1.w);
 			rng.inc = a.inc_in[tid];
 			ray_o = st_v3(q0); ray_d = st_v3(q1);
 			if (!kFirst) {
-				const uint4 q2 = st_load(a.st_in, a, 2, tid), q3 = st_load(a.st_in, a, 3, tid);
+				const uint4 q2 = st_load(a.st_in, a, PS_THR, tid), q3 = st_load(a.st_in, a, PS_PREV, tid);
 				thr = st_v3(q2);
-				{ const uint4 q4 = st_load(a.st_in, a, 4, tid); ior = __uint_as_float(q2.w & 0x7fffffffu); L = st_v3(q4); lane = q4.w; }
-				prev_delta = (q2.w >> 31) != 0u;
+				{ const uint4 q4 = st_load(a.st_in, a, PS_L, tid); ior = st_ior(q2); L = st_v3(q4); lane = st_lane(q4); }
+				prev_delta = st_delta(q2);
 				prev_p = st_v3(q3);
-				prev_pdf = __uint_as_float(q3.w);
+				prev_pdf = st_wf(q3);
 			}
-			h.prim = (int)wsu(a, WS_HIT_PRIM, tid);
-			h.t = wsf(a, WS_HIT_T, tid); h.u = wsf(a, WS_HIT_U, tid); h.v = wsf(a, WS_HIT_V, tid);
+			h = ws_hit(a, tid);
 		}
 		StageA A;
 		PG_PHASE(0)
@@ -1205,10 +1205,7 @@ __device__ __forceinline__ void shade_body(const RenderArgs &a)
 		asm volatile("" : "+v"(A.wo.x), "+v"(A.wo.y), "+v"(A.wo.z), "+v"(A.bsdf_w.x), "+v"(A.bsdf_w.y), "+v"(A.bsdf_w.z),
 		                  "+v"(A.bsdf_pdf), "+v"(A.flags));
 		if (kLevel >= 3) asm volatile("" : "+v"(A.eta));
-		GuideOut g;
-		g.nee_cx = 0.0f; g.nee_cy = 0.0f; g.wo_cx = 0.0f; g.wo_cy = 0.0f; g.pdf_nee = 1.0f; g.pdf_tree = 1.0f;
-		g.slot_path = kSlotNone; g.slot_nee = kSlotNone; g.tree_flags = 0u;
-		g.wo = A.wo;
+		GuideOut g = guide_none(A.wo);
 		PG_PHASE(3)
 		if (guide_has_work(a, A.flags)) stage_guide(a, s_planes, rng, A.p, A.ds_d, (A.flags & F_SMP_TREE) ? V(0, 0, 0) : A.wo, A.flags, g);
 		if (a.record && (A.flags & F_VALID)) store_slots(a, rec_base + tid, g);
@@ -1221,7 +1218,7 @@ __device__ __forceinline__ void shade_body(const RenderArgs &a)
 		cont = stage_b<kLevel>(a, rng, thr, L, ior, A, g, occluded, lane, rec_base + tid, (uint32_t)a.bounce, ray_o, ray_d, prev_pdf, delta);
 		p_here = A.p;
 		if (kFirst) a.hit0[lane] = (A.flags & F_VALID) ? 1 : 0;
-		if (!cont) a.Lq[lane] = make_uint4(__float_as_uint(L.x), __float_as_uint(L.y), __float_as_uint(L.z), 0u); // the path ends here
+		if (!cont) end_path(a, lane, L);
 		PG_PHASE(5)
 	}
 	// (append_survivors' first barrier comes after every walk of the workgroup: from there on the stacks' bytes hold records)
@@ -1279,11 +1276,9 @@ __global__ __launch_bounds__(kRBlock) void k_wave_tail(RenderArgs a)
 	stage_kd_planes(s_planes, a.tree);
 	bool alive = tid < live;
 	uint64_t lane = 0;
-	uint64_t rec_base = a.n_lanes; // entries of the bounces before a.bounce
-	for (int j = 0; j + 1 < a.bounce; ++j) rec_base += live_final(a, j);
+	const uint64_t rec_base = records_before(a);
 	const uint64_t tail_base = rec_base + live; // behind the entries of bounce a.bounce
 	uint64_t slot = rec_base + tid;
-	const unsigned wl = threadIdx.x & 63u;
 	const BvhStack stk = bvh_stack(&s_stack[0][threadIdx.x], a.bvh_ovf, (uint32_t)tid * (uint32_t)kOvfStack);
 	Pcg32 rng;
 	v3 ray_o = V(0, 0, 0), ray_d = V(0, 0, 1), thr = V(0, 0, 0), L = V(0, 0, 0), prev_p = V(0, 0, 0);
@@ -1293,22 +1288,22 @@ __global__ __launch_bounds__(kRBlock) void k_wave_tail(RenderArgs a)
 	if (alive) {
 		uint4 q0, q1, q2, q3, q4;
 		if (a.carry_in) { // the bounce taken over would have been a sorted one: its state is in the paths' records
-			const uint4 *rec = a.carry_in + tid * 8;
-			q0 = rec[0]; q1 = rec[1]; q2 = rec[2]; q3 = rec[3]; q4 = rec[4];
-			const uint4 q5 = rec[5];
-			rng.inc = (uint64_t)q5.x | ((uint64_t)q5.y << 32);
+			const uint4 *rec = st_rec(a.carry_in, tid);
+			q0 = rec[PS_RAY_O]; q1 = rec[PS_RAY_D]; q2 = rec[PS_THR]; q3 = rec[PS_PREV]; q4 = rec[PS_L];
+			const uint4 q5 = rec[PS_INC];
+			rng.inc = st_u64(q5.x, q5.y);
 		} else {
-			q0 = st_load(a.st_in, a, 0, tid); q1 = st_load(a.st_in, a, 1, tid); q2 = st_load(a.st_in, a, 2, tid);
-			q3 = st_load(a.st_in, a, 3, tid); q4 = st_load(a.st_in, a, 4, tid);
+			q0 = st_load(a.st_in, a, PS_RAY_O, tid); q1 = st_load(a.st_in, a, PS_RAY_D, tid); q2 = st_load(a.st_in, a, PS_THR, tid);
+			q3 = st_load(a.st_in, a, PS_PREV, tid); q4 = st_load(a.st_in, a, PS_L, tid);
 			rng.inc = a.inc_in[tid];
 		}
-		rng.state = (uint64_t)q0.w | ((uint64_t)q1.w << 32);
+		rng.state = st_u64(q0.w, q1.w);
 		ray_o = st_v3(q0); ray_d = st_v3(q1); thr = st_v3(q2); prev_p = st_v3(q3);
-		ior = __uint_as_float(q2.w & 0x7fffffffu);
-		prev_delta = (q2.w >> 31) != 0u;
-		prev_pdf = __uint_as_float(q3.w);
+		ior = st_ior(q2);
+		prev_delta = st_delta(q2);
+		prev_pdf = st_wf(q3);
 		L = st_v3(q4);
-		lane = q4.w;
+		lane = st_lane(q4);
 	}
 	for (int depth = a.bounce; depth < a.max_depth; ++depth) {
 		if (alive) {
@@ -1322,28 +1317,16 @@ __global__ __launch_bounds__(kRBlock) void k_wave_tail(RenderArgs a)
 				float th, bu, bv;
 				occluded = intersect<kLevel, true>(a.shapes, A.sh_o, A.sh_d, A.sh_tmax, th, stk, bu, bv) >= 0;
 			}
-			GuideOut g;
-			g.nee_cx = 0.0f; g.nee_cy = 0.0f; g.wo_cx = 0.0f; g.wo_cy = 0.0f; g.pdf_nee = 1.0f; g.pdf_tree = 1.0f;
-			g.slot_path = kSlotNone; g.slot_nee = kSlotNone; g.tree_flags = 0u;
-			g.wo = A.wo;
+			GuideOut g = guide_none(A.wo);
 			if (guide_has_work(a, A.flags)) stage_guide(a, s_planes, rng, A.p, A.ds_d, A.wo, A.flags, g);
 			if (a.record && (A.flags & F_VALID)) store_slots(a, slot, g);
 			bool delta;
 			alive = stage_b<kLevel>(a, rng, thr, L, ior, A, g, occluded, lane, slot, (uint32_t)depth, ray_o, ray_d, prev_pdf, delta);
 			prev_p = A.p;
 			prev_delta = delta;
-			if (!alive) a.Lq[lane] = make_uint4(__float_as_uint(L.x), __float_as_uint(L.y), __float_as_uint(L.z), 0u); // the path ends here
+			if (!alive) end_path(a, lane, L);
 		}
-		const unsigned long long ballot = __ballot(alive);
-		if (ballot == 0ull) break; // (nothing survives the last bounce)
-		const uint32_t n = (uint32_t)__popcll(ballot);
-		uint32_t off = 0;
-		if (wl == (unsigned)__builtin_ctzll(ballot)) {
-			atomicAdd(&a.live_count[depth], n);
-			off = atomicAdd(&a.live_count[a.max_depth], n);
-		}
-		off = __shfl(off, __builtin_ctzll(ballot), 64);
-		slot = tail_base + off + (uint32_t)__popcll(ballot & ((1ull << wl) - 1ull));
+		if (!tail_next_slot(a, depth, alive, tail_base, slot)) break;
 	}
 }
 
@@ -1369,42 +1352,32 @@ static void launch_stage_level(WaveStage stage, bool first, const RenderArgs &a,
 {
 	const dim3 block(kRBlock);
 	static unsigned occ[2] = {0, 0}; // resident workgroups per CU of the two shadow-ray instantiations of this level
+	// (kF: the instantiation for the first bounce or the one for the later ones)
+#define PG_BY_FIRST(launch) do { if (first) { constexpr bool kF = true; launch; } else { constexpr bool kF = false; launch; } } while (0)
 	switch (stage) {
-	case WaveStage::Trace:
-		if (first) hipLaunchKernelGGL((k_wave_trace<kLevel, true>), grid, block, 0, s, a);
-		else hipLaunchKernelGGL((k_wave_trace<kLevel, false>), grid, block, 0, s, a);
-		break;
+	case WaveStage::Trace: PG_BY_FIRST(hipLaunchKernelGGL((k_wave_trace<kLevel, kF>), grid, block, 0, s, a)); break;
 	case WaveStage::ShadeA:
-		if (a.fuse_guide) {
-			if (first) hipLaunchKernelGGL((k_wave_shade_a<kLevel, true, true>), grid, block, 0, s, a);
-			else hipLaunchKernelGGL((k_wave_shade_a<kLevel, false, true>), grid, block, 0, s, a);
-		} else if (first) hipLaunchKernelGGL((k_wave_shade_a<kLevel, true, false>), grid, block, 0, s, a);
-		else hipLaunchKernelGGL((k_wave_shade_a<kLevel, false, false>), grid, block, 0, s, a);
+		if (a.fuse_guide) PG_BY_FIRST(hipLaunchKernelGGL((k_wave_shade_a<kLevel, kF, true>), grid, block, 0, s, a));
+		else PG_BY_FIRST(hipLaunchKernelGGL((k_wave_shade_a<kLevel, kF, false>), grid, block, 0, s, a));
 		break;
 	case WaveStage::Cast:
-		if (first) hipLaunchKernelGGL((k_wave_cast<kLevel, true>), persistent_grid(k_wave_cast<kLevel, true>, occ[0], n_cus, a.n_lanes), block, 0, s, a);
-		else hipLaunchKernelGGL((k_wave_cast<kLevel, false>), persistent_grid(k_wave_cast<kLevel, false>, occ[1], n_cus, a.n_lanes), block, 0, s, a);
+		PG_BY_FIRST(hipLaunchKernelGGL((k_wave_cast<kLevel, kF>), persistent_grid(k_wave_cast<kLevel, kF>, occ[kF ? 0 : 1], n_cus, a.n_lanes), block, 0, s, a));
 		break;
 	case WaveStage::Guide: hipLaunchKernelGGL(k_wave_guide, grid, block, 0, s, a); break;
 	case WaveStage::ShadeB: {
-		const size_t lds = a.carry_out ? (size_t)kRBlock * 8 * sizeof(uint4) : 0; // (the survivors' records of a sorted next bounce)
-		if (first) hipLaunchKernelGGL((k_wave_shade_b<kLevel, true>), grid, block, lds, s, a);
-		else hipLaunchKernelGGL((k_wave_shade_b<kLevel, false>), grid, block, lds, s, a);
+		const size_t lds = a.carry_out ? (size_t)kRBlock * PS_ENTRIES * sizeof(uint4) : 0; // (the survivors' records of a sorted next bounce)
+		PG_BY_FIRST(hipLaunchKernelGGL((k_wave_shade_b<kLevel, kF>), grid, block, lds, s, a));
 		break;
 	}
 	case WaveStage::Tail: hipLaunchKernelGGL((k_wave_tail<kLevel>), grid, block, 0, s, a); break;
 	case WaveStage::Shade: {
 		const size_t lds = (size_t)kShadeLdsQuads * sizeof(uint4);
-		if constexpr (kLevel == 3) {
-			if (first) hipLaunchKernelGGL((k_wave_shade_l3<true>), grid, block, lds, s, a);
-			else hipLaunchKernelGGL((k_wave_shade_l3<false>), grid, block, lds, s, a);
-		} else {
-			if (first) hipLaunchKernelGGL((k_wave_shade<kLevel, true>), grid, block, lds, s, a);
-			else hipLaunchKernelGGL((k_wave_shade<kLevel, false>), grid, block, lds, s, a);
-		}
+		if constexpr (kLevel == 3) PG_BY_FIRST(hipLaunchKernelGGL((k_wave_shade_l3<kF>), grid, block, lds, s, a));
+		else PG_BY_FIRST(hipLaunchKernelGGL((k_wave_shade<kLevel, kF>), grid, block, lds, s, a));
 		break;
 	}
 	}
+#undef PG_BY_FIRST
 }
 
 void launch_wave_stage(WaveStage stage, int level, bool first, const RenderArgs &a, unsigned grid_blocks, unsigned n_cus, hipStream_t s)
