@@ -38,6 +38,8 @@ extern "C" {
 /* 6 (round 6): pg_refine_and_swap is a transaction (on any error both trees are exactly what they were; the context stays usable);
  * new entry points pg_debug_fail_alloc, pg_debug_fail_alloc_pending (fault injection for the tests), pg_read_shade_phases (probe
  * builds); pg_enable_depth_counters takes mode 2.  No struct changed. */
+/* (still 6): new entry point pg_set_splat_filter (the training filters of pg_splat / pg_process_and_splat); an added entry
+ * point breaks no caller and no struct changed, so the number stays. */
 #define PGSD_ABI_VERSION 6
 
 typedef struct pg_context pg_context;
@@ -179,6 +181,63 @@ int pg_process_records(pg_context *ctx, uint64_t num_rays, int32_t max_depth, co
 /* Same, fused with pg_splat: no intermediate stream (path_guiding_integrator.py:388-395). */
 int pg_process_and_splat(pg_context *ctx, uint64_t num_rays, int32_t max_depth,
                          const float *l_final, const pg_dense_records *rec, void *stream);
+
+/* ---- training filters of the record boundary (not in the reference) -------------------- */
+
+/* How pg_splat and pg_process_and_splat deposit a record.  The default, and the reference's behaviour, is nearest / nearest:
+ * a record adds to the one quadtree leaf its direction falls in, inside the one KD leaf its position falls in; those calls then
+ * run exactly the kernels they ran before this entry point existed.  The two filters of the 2019 follow-up of the method
+ * ("Path Guiding in Production", ch. 10) are extensions beyond the reference.  Context state; pg_setup resets it to
+ * nearest / nearest, seed 0.  Unknown values: PG_ERR_INVALID.  All arithmetic below is fp32, every operation rounded on its
+ * own (the arithmetic contract), in exactly the order written; names of columns are those of pg_tree_columns.
+ *
+ * PG_SPATIAL_STOCHASTIC_BOX.  For record number i with position p inside the root box (inclusive; a record outside it or
+ * with a NaN coordinate is handled exactly as without the filter): L = the KD leaf of p (KDTree.getLeafNodeIndex),
+ *     e[a]  = kd_bbox_max[L][a] - kd_bbox_min[L][a]                                   a = x, y, z
+ *     u[a]  = the first three next_f32 of the PCG32 stream pg_rng_seed(seed, lane = i) seeds, in the order x, y, z
+ *     p'[a] = min(max(p[a] + (u[a] - 0.5) * e[a], root_min[a]), root_max[a])
+ * and the whole record -- its count and both of its directional deposits -- goes to the KD leaf of p'.  i is the record's
+ * index in pg_splat's stream; in pg_process_and_splat it is the dense slot g = ray * max_depth + depth modulo 2^32.  The two
+ * routes therefore jitter the same record differently (a compacted stream numbers the survivors, the dense buffer the slots).
+ *
+ * PG_DIRECTIONAL_BOX.  For a (direction c = (cx, cy), weight w) pair of a record -- (direction, radiance / wo_pdf) and, with
+ * store_nee, (direction_nee, radiance_nee_lum / wo_pdf) -- in the quadtree of the record's KD leaf.  A direction outside the
+ * unit square is handled exactly as without the filter (fallback counter included).  Otherwise N = the leaf the nearest walk
+ * finds (QuadTree.addIrradiancePropagate's descent), d = quad_depth[N] - quad_depth[root] (at most 30, the
+ * depth limit of pg_setup), G = 2^d.  The record COUNT goes to
+ * N alone, as without the filter.  If d = 0 (the root is the leaf), N receives quantize(w): identical to nearest.  Else the
+ * footprint is the square of side 2^-d centred on c; in units of that side (every scaling by G is exact):
+ *     vx = cx * G - 0.5          jx = floor(vx)    tx = vx - jx       X0 = jx mod G (jx = -1 wraps to G - 1), X1 = (X0 + 1) mod G
+ *     vy = max(cy * G - 0.5, 0)  jy = floor(vy)    ty = vy - jy       if jy >= G - 1: jy = G - 1, ty = 0      Y0 = jy, Y1 = jy + 1
+ * i.e. in x (cx = phi / 2 pi, periodic) the footprint WRAPS modulo 1, in y (not periodic) it is SHIFTED to stay inside
+ * [0, 1]; nothing is clipped away.  The footprint meets at most the 2 x 2 block of depth-d cells (X_a, Y_b), a, b in {0, 1}.
+ * In the local frame of cell (X_a, Y_b) -- the cell is [0, 1]^2 -- the footprint is the rectangle [lx, hx] x [ly, hy] with
+ *     (lx, hx) = (tx, 1) for a = 0, (0, tx) for a = 1          (ly, hy) = (ty, 1) for b = 0, (0, ty) for b = 1.
+ * Column a is EMPTY when hx - lx <= 0 (one subtraction: 1 - tx, or tx - 0), row b likewise; cells of an empty column or row
+ * receive nothing.  Every leaf M of the tree that meets the footprint with positive area receives ONE deposit
+ *     quantize(w * (ox * oy))          (one product ox * oy, then one product with w; quantize = the fixed-point truncation)
+ * where ox, oy are M's overlap lengths with the footprint in units of the footprint's side (the division of the overlap
+ * area by the footprint's area is a scaling by a power of two: exact, and already made):
+ *   - M at depth <= d, containing one or more of the non-empty cells: ox = 1 exactly if both columns are non-empty and
+ *     both lie in M, else hx - lx of its one column; oy likewise for the rows.
+ *   - M below a non-empty cell (X_a, Y_b), with the local cell [u0, u0 + h] x [v0, v0 + h] (h a power of two, u0, v0 multiples
+ *     of h: exact): ox = min(u0 + h, hx) - max(u0, lx), oy = min(v0 + h, hy) - max(v0, ly); M receives its deposit when
+ *     ox > 0 and oy > 0.
+ * Energy is conserved up to the roundings of these products and one truncation to 2^-PG_FRAC_BITS per deposit.  A weight
+ * whose own quantize(w) is zero (0, NaN, |w| < 2^-PG_FRAC_BITS) deposits nothing anywhere, as every part of it would.
+ *
+ * Both filters may be set: the jitter first, then the directional deposits in the quadtree of the KD leaf of p'.
+ * Sums stay exact integers: filtered results do not depend on the order of the records or of the launches, and refine, the
+ * exchange format, pg_allreduce and export see nothing new.
+ * The library's own renderer does not carry a vertex's position and directions to its splat (it names the two leaves found
+ * during the bounce): while a filter other than nearest / nearest is set, a RECORDING pg_render_pass (iteration not final)
+ * fails with PG_ERR_INVALID and names the filter; it never falls back to nearest.  A final-iteration pass is unaffected.
+ * pg_enable_depth_counters: a filtered launch adds nothing to the depth counters. */
+#define PG_SPATIAL_NEAREST 0
+#define PG_SPATIAL_STOCHASTIC_BOX 1
+#define PG_DIRECTIONAL_NEAREST 0
+#define PG_DIRECTIONAL_BOX 1
+int pg_set_splat_filter(pg_context *ctx, int32_t spatial, int32_t directional, uint32_t seed);
 
 /* ---- per-iteration refinement --------------------------------------------------------- */
 

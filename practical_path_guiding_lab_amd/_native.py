@@ -17,6 +17,8 @@ CSRC = os.path.join(_PKG, "csrc")
 PG_OK = 0
 PG_ACC_LIMBS = 3
 PG_FRAC_BITS = 40
+PG_SPATIAL_NEAREST, PG_SPATIAL_STOCHASTIC_BOX = 0, 1
+PG_DIRECTIONAL_NEAREST, PG_DIRECTIONAL_BOX = 0, 1
 
 
 class PgError(RuntimeError):
@@ -118,7 +120,7 @@ EXPORTS = (
     "pg_comm_unique_id", "pg_comm_init", "pg_comm_attach", "pg_comm_destroy", "pg_allreduce", "pg_render_reserve",
     "pg_render_split_pipeline", "pg_comm_info", "pg_exchange_pack", "pg_exchange_unpack", "pg_exchange_pack_words",
     "pg_exchange_unpack_words", "pg_sort_places", "pg_debug_fail_alloc", "pg_debug_fail_alloc_pending",
-    "pg_read_shade_phases",
+    "pg_read_shade_phases", "pg_set_splat_filter",
 )
 
 
@@ -175,6 +177,7 @@ def lib() -> C.CDLL:
     L.pg_destroy.argtypes = [V]
     L.pg_setup.argtypes = [V, V, V, U64, I32, I32, I32, I32, C.c_float]
     L.pg_set_iteration.argtypes = [V, I32, I32]
+    L.pg_set_splat_filter.argtypes = [V, I32, I32, U32]
     L.pg_get_leaf_node_index.argtypes = [V, U64, V, V, V, V]
     L.pg_sample.argtypes = [V, U64, V, V, V, V, V, V, V]
     L.pg_pdf.argtypes = [V, U64, V, V, V, V, V]

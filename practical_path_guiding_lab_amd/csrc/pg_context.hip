@@ -164,6 +164,9 @@ int pg_setup(pg_context *ctx, const float bbox_min[3], const float bbox_max[3], 
 	ctx->bsdf_fraction = bsdf_fraction;
 	ctx->iteration = 0;
 	ctx->is_final = 0;
+	ctx->filter_spatial = PG_SPATIAL_NEAREST;
+	ctx->filter_directional = PG_DIRECTIONAL_NEAREST;
+	ctx->filter_seed = 0;
 	ctx->kd_max_leaf_size = 1.0; // KDTree.__init__ default (kdtree.py:118)
 	// kdtree.py:122-124, quadtree.py:355-359: one leaf KD node owning one leaf quadtree
 	HostForest h;
@@ -185,6 +188,19 @@ int pg_set_iteration(pg_context *ctx, int32_t iteration, int32_t is_final)
 	if (!ctx) return PG_ERR_INVALID;
 	ctx->iteration = iteration;
 	ctx->is_final = is_final ? 1 : 0;
+	return PG_OK;
+}
+
+int pg_set_splat_filter(pg_context *ctx, int32_t spatial, int32_t directional, uint32_t seed)
+{
+	if (!ctx) return PG_ERR_INVALID;
+	if (spatial != PG_SPATIAL_NEAREST && spatial != PG_SPATIAL_STOCHASTIC_BOX)
+		return fail(ctx, PG_ERR_INVALID, "pg_set_splat_filter: unknown spatial filter");
+	if (directional != PG_DIRECTIONAL_NEAREST && directional != PG_DIRECTIONAL_BOX)
+		return fail(ctx, PG_ERR_INVALID, "pg_set_splat_filter: unknown directional filter");
+	ctx->filter_spatial = spatial;
+	ctx->filter_directional = directional;
+	ctx->filter_seed = seed;
 	return PG_OK;
 }
 
@@ -284,8 +300,11 @@ int pg_splat(pg_context *ctx, uint64_t m, const pg_records *rec, const uint32_t 
 	          (ctx->store_nee && (!rec->direction_nee || !rec->radiance_nee_lum))))
 		return fail(ctx, PG_ERR_INVALID, "pg_splat: NULL record column");
 	if (m > 0xffffffffull) return fail(ctx, PG_ERR_INVALID, "pg_splat: more than 2^32 records in one call");
-	launch_splat(ctx->view(), ctx->f.accum_view(), ctx->store_nee, m, *rec, d_count,
-	             ctx->dc_on ? ctx->dc : nullptr, (hipStream_t)stream);
+	if (ctx->filtered_launch())
+		launch_splat_filtered(ctx->view(), ctx->f.accum_view(), ctx->filter_args(), ctx->store_nee, m, *rec, d_count, (hipStream_t)stream);
+	else
+		launch_splat(ctx->view(), ctx->f.accum_view(), ctx->store_nee, m, *rec, d_count,
+		             ctx->dc_on ? ctx->dc : nullptr, (hipStream_t)stream);
 	PG_LAUNCHED(ctx);
 	return PG_OK;
 }
@@ -319,8 +338,12 @@ int pg_process_and_splat(pg_context *ctx, uint64_t num_rays, int32_t max_depth, 
 	PG_READY(ctx);
 	if (max_depth <= 0) return fail(ctx, PG_ERR_INVALID, "pg_process_and_splat: max_depth must be > 0");
 	if (!dense_ok(rec) || !l_final) return fail(ctx, PG_ERR_INVALID, "pg_process_and_splat: NULL pointer");
-	launch_process_and_splat(ctx->view(), ctx->f.accum_view(), ctx->store_nee, num_rays, max_depth, l_final,
-	                         *rec, ctx->dc_on ? ctx->dc : nullptr, (hipStream_t)stream);
+	if (ctx->filtered_launch())
+		launch_process_and_splat_filtered(ctx->view(), ctx->f.accum_view(), ctx->filter_args(), ctx->store_nee, num_rays, max_depth,
+		                                  l_final, *rec, ctx->n_cus, (hipStream_t)stream);
+	else
+		launch_process_and_splat(ctx->view(), ctx->f.accum_view(), ctx->store_nee, num_rays, max_depth, l_final,
+		                         *rec, ctx->dc_on ? ctx->dc : nullptr, (hipStream_t)stream);
 	PG_LAUNCHED(ctx);
 	return PG_OK;
 }

@@ -131,6 +131,8 @@ struct pg_context {
 	int32_t max_depth = 0, kd_max_depth = 10, quad_max_depth = 30, store_nee = 1;
 	float bsdf_fraction = 0.5f;
 	int32_t iteration = 0, is_final = 0;
+	int32_t filter_spatial = 0, filter_directional = 0; // pg_set_splat_filter: PG_SPATIAL_* / PG_DIRECTIONAL_*
+	uint32_t filter_seed = 0;
 	double kd_max_leaf_size = 1.0;
 	pg::Forest f;
 	pg::DepthCounters *dc = nullptr; // device
@@ -164,6 +166,20 @@ struct pg_context {
 		t.n_trees = f.n_trees;
 		return t;
 	}
+	bool filtered() const { return filter_spatial != PG_SPATIAL_NEAREST || filter_directional != PG_DIRECTIONAL_NEAREST; }
+	// The filtered kernels' arguments.  (On the initial tree -- one KD leaf owning a single-leaf quadtree -- every filter is the
+	// nearest deposit bit for bit, and the callers run the nearest kernels, with their one-accumulator fast path.)
+	pg::pg_filter_args filter_args() const
+	{
+		pg::pg_filter_args a;
+		a.spatial = filter_spatial;
+		a.directional = filter_directional;
+		a.seed = filter_seed;
+		a.kd_bmin = f.kd_bmin.p;
+		a.kd_bmax = f.kd_bmax.p;
+		return a;
+	}
+	bool filtered_launch() const { return filtered() && !(f.n_rec == 0 && f.n_trees == 1); }
 };
 
 namespace pg {

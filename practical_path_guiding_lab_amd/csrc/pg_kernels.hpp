@@ -74,4 +74,16 @@ void launch_process_and_splat(const TreeView &t, const AccumView &a, int store_n
                               uint64_t num_rays, int32_t max_depth, const float *l_final,
                               const pg_dense_records &rec, DepthCounters *dc, hipStream_t s);
 
+// ---- recording through the training filters (pg_kernels_filter.hip; pg_set_splat_filter, include/pgsd.h) ----
+struct pg_filter_args {
+	int spatial, directional; // PG_SPATIAL_* / PG_DIRECTIONAL_*
+	uint32_t seed;            // of the jitter's PCG32 streams
+	const float *kd_bmin, *kd_bmax; // [n_kd][3]: the boxes of the KD nodes (the exported columns), read by the jitter
+};
+void launch_splat_filtered(const TreeView &t, const AccumView &a, const pg_filter_args &f, int store_nee, uint64_t m,
+                           const pg_records &rec, const uint32_t *d_count, hipStream_t s);
+void launch_process_and_splat_filtered(const TreeView &t, const AccumView &a, const pg_filter_args &f, int store_nee,
+                                       uint64_t num_rays, int32_t max_depth, const float *l_final, const pg_dense_records &rec,
+                                       int n_cus, hipStream_t s);
+
 } // namespace pg

@@ -751,6 +751,11 @@ static int check_pass(pg_context *ctx, const pg_pass_params *prm, const float *L
 	if (!prm || !L_out) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: NULL pointer");
 	if (prm->spp <= 0 || ctx->max_depth <= 0) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: spp and max_depth must be > 0");
 	if ((sumL == nullptr) != (sumL2 == nullptr)) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: sumL and sumL2 go together");
+	// (the pass's record list names accumulators, not positions and directions: it cannot be filtered, and must not pretend to)
+	if (!ctx->is_final && ctx->filtered())
+		return fail(ctx, PG_ERR_INVALID, std::string("pg_render_pass: a recording pass cannot apply the splat filter set by pg_set_splat_filter (spatial ") +
+		                                     (ctx->filter_spatial ? "stochastic box" : "nearest") + ", directional " +
+		                                     (ctx->filter_directional ? "box" : "nearest") + "); reset it to nearest / nearest or record through pg_splat / pg_process_and_splat");
 	PG_HIP(ctx, hipSetDevice(ctx->device));
 	const pg_camera &cam = ctx->render->cam;
 	const uint64_t film = (uint64_t)cam.width * (uint64_t)cam.height;

@@ -95,6 +95,22 @@ class SDTree:
     def setIteration(self, iteration: int, isFinalIter: bool = False):
         self._ck(self._lib.pg_set_iteration(self._h, int(iteration), int(bool(isFinalIter))))
 
+    _SPATIAL = {"nearest": N.PG_SPATIAL_NEAREST, "stochastic": N.PG_SPATIAL_STOCHASTIC_BOX}
+    _DIRECTIONAL = {"nearest": N.PG_DIRECTIONAL_NEAREST, "box": N.PG_DIRECTIONAL_BOX}
+
+    def setSplatFilter(self, spatial: str = "nearest", directional: str = "nearest", seed: int = 0):
+        """The training filters of the record boundary (pg_set_splat_filter; not in the reference): spatial "nearest" |
+        "stochastic" (the position is jittered by the extent of its KD leaf), directional "nearest" | "box" (the energy is
+        shared between the quadtree leaves a leaf-sized square around the direction overlaps).  addDataPropagate,
+        processAndSplat and prepareProcessAndSplat follow it; setup() resets it to nearest / nearest.  While a filter is
+        set, a recording render pass raises (the renderer's record list cannot be filtered)."""
+        if spatial not in self._SPATIAL:
+            raise ValueError(f"spatial filter must be one of {sorted(self._SPATIAL)}, got {spatial!r}")
+        if directional not in self._DIRECTIONAL:
+            raise ValueError(f"directional filter must be one of {sorted(self._DIRECTIONAL)}, got {directional!r}")
+        self._ck(self._lib.pg_set_splat_filter(self._h, self._SPATIAL[spatial], self._DIRECTIONAL[directional],
+                                               int(seed) & 0xFFFFFFFF))
+
     def _seed(self, sampler: PCG32Sampler, seed: int, lane0: int):
         self._ck(self._lib.pg_rng_seed(self._h, sampler.n, seed & 0xFFFFFFFF, lane0 & 0xFFFFFFFF,
                                        sampler.state.data_ptr(), sampler.inc.data_ptr(), _stream_ptr()))
