@@ -30,14 +30,6 @@ int hip_fail(pg_context *ctx, hipError_t e, const char *what)
 	            std::string(what) + ": " + hipGetErrorString(e));
 }
 
-template <class T> static hipError_t upload(DevBuf<T> &d, const std::vector<T> &h, double slack = 1.0)
-{
-	hipError_t e = d.ensure(h.size(), slack);
-	if (e != hipSuccess) return e;
-	if (h.empty()) return hipSuccess;
-	return hipMemcpy(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-}
-
 template <class T> static hipError_t download(std::vector<T> &h, const DevBuf<T> &d, size_t n)
 {
 	h.resize(n);

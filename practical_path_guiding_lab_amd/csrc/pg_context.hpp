@@ -56,6 +56,15 @@ template <class T> struct DevBuf {
 	}
 };
 
+// ensure + copy: n elements of a host array become the contents of d
+template <class T> hipError_t upload(DevBuf<T> &d, const T *h, size_t n, double slack = 1.0)
+{
+	hipError_t e = d.ensure(n, slack);
+	if (e != hipSuccess || n == 0) return e;
+	return hipMemcpy(d.p, h, n * sizeof(T), hipMemcpyHostToDevice);
+}
+template <class T> hipError_t upload(DevBuf<T> &d, const std::vector<T> &h, double slack = 1.0) { return upload(d, h.data(), h.size(), slack); }
+
 // One SD-tree topology + sampling values (sdTree_prev) + integer accumulators (sdTree_current).
 // The two reference objects always share their topology (prev <- copy of current after every
 // refine, path_guiding_integrator.py:582), so it is stored once.
@@ -118,7 +127,7 @@ struct Forest {
 
 } // namespace pg
 
-struct pg_render_state; // pg_render.hip
+struct pg_render_state; // pg_render.hip (its scene: pg_scene_state.hpp)
 
 struct pg_context {
 	pg_render_state *render = nullptr;

@@ -20,6 +20,7 @@
 // stack frame in scratch memory; inlined, k_bounce<*, 1> is 87 / 89 registers at five waves per SIMD with no scratch at
 // all -- veach-mis 2.33 -> 2.32 ms per pass, profiles/r05/ab_fused_kernel_helpers_inlined.txt.)
 #include "pg_render_dev.hpp"
+#include "pg_scene_state.hpp"
 
 namespace pg {
 
@@ -639,16 +640,8 @@ enum class Timer { Bounce, Trace, ShadeA, Shadow, Guide, ShadeB, Tail, Sort, Spl
 
 // library-owned renderer state
 struct pg_render_state {
-	DevBuf<float> quads, spheres, mats, boxes, tris, dir_lights, ior, tri_normals, tri_uvs, srgb_lut;
-	DevBuf<uint32_t> textures, texels;
-	bool have_tri_normals = false, have_tri_uvs = false;
-	float bsphere[4] = {0, 0, 0, 0};
-	DevBuf<uint32_t> bvh;
-	DevBuf<int32_t> emitters;
-	int n_quads = 0, n_spheres = 0, n_emitters = 0, n_boxes = 0, n_bvh_nodes = 0;
-	int general = 0; // feature level of the kernels to launch (0 cornell-box class, 1 veach-mis class, 2 everything)
-	pg_camera cam;
-	bool have_scene = false;
+	SceneState scene; // what pg_scene_set_ex (pg_scene.hip) made of the scene description
+	DevBuf<float> ior;
 	bool split_always = false; // pg_render_split_pipeline: quad scenes run the split pipeline too
 	int overlap = 0;           // pg_render_overlap
 	int stages = 0;            // pg_render_stages
@@ -689,6 +682,9 @@ static pg_render_state *rstate(pg_context *ctx)
 	return ctx->render;
 }
 
+SceneState &pg::scene_state(pg_context *ctx) { return rstate(ctx)->scene; }
+bool pg::split_pipeline_always(pg_context *ctx) { return rstate(ctx)->split_always; }
+
 void pg::destroy_render_state(pg_context *ctx)
 {
 	delete ctx->render;
@@ -705,7 +701,7 @@ static int ensure_pass_buffers(pg_context *ctx, int slot, uint64_t N, bool recor
 	const int D = ctx->max_depth;
 	const uint64_t S = N * (uint64_t)D;
 	PG_HIP(ctx, b.hit0.ensure(N));
-	if (r->general < 2) {
+	if (r->scene.general < 2) {
 		PG_HIP(ctx, b.ray_d.ensure(3 * N)); PG_HIP(ctx, b.thr.ensure(3 * N));
 		PG_HIP(ctx, b.prev_p.ensure(3 * N)); PG_HIP(ctx, b.prev_pdf.ensure(N));
 		PG_HIP(ctx, b.prev_quad.ensure(N)); PG_HIP(ctx, b.rng_state.ensure(N));
@@ -747,7 +743,7 @@ static int check_pass(pg_context *ctx, const pg_pass_params *prm, const float *L
 {
 	if (!ctx) return PG_ERR_INVALID;
 	if (!ctx->configured) return fail(ctx, PG_ERR_INVALID, "call pg_setup or pg_import first");
-	if (!ctx->render || !ctx->render->have_scene) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: call pg_scene_set first");
+	if (!ctx->render || !ctx->render->scene.have_scene) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: call pg_scene_set first");
 	if (!prm || !L_out) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: NULL pointer");
 	if (prm->spp <= 0 || ctx->max_depth <= 0) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: spp and max_depth must be > 0");
 	if ((sumL == nullptr) != (sumL2 == nullptr)) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: sumL and sumL2 go together");
@@ -757,7 +753,7 @@ static int check_pass(pg_context *ctx, const pg_pass_params *prm, const float *L
 		                                     (ctx->filter_spatial ? "stochastic box" : "nearest") + ", directional " +
 		                                     (ctx->filter_directional ? "box" : "nearest") + "); reset it to nearest / nearest or record through pg_splat / pg_process_and_splat");
 	PG_HIP(ctx, hipSetDevice(ctx->device));
-	const pg_camera &cam = ctx->render->cam;
+	const pg_camera &cam = ctx->render->scene.cam;
 	const uint64_t film = (uint64_t)cam.width * (uint64_t)cam.height;
 	if (prm->pixel_begin > film || prm->pixel_count > film - prm->pixel_begin)
 		return fail(ctx, PG_ERR_INVALID, "pg_render_pass: pixel range outside the film");
@@ -787,20 +783,21 @@ static RenderArgs pass_args(pg_context *ctx, const pg_pass_params *prm, PassBuf 
 	RenderArgs a;
 	a.tree = ctx->view();
 	// the scene
-	a.shapes.quads = r->quads.p; a.shapes.spheres = r->spheres.p; a.shapes.boxes = r->boxes.p; a.shapes.tris = r->tris.p;
-	a.shapes.tri_normals = r->have_tri_normals ? r->tri_normals.p : nullptr;
-	a.shapes.tri_uvs = r->have_tri_uvs ? r->tri_uvs.p : nullptr;
-	a.shapes.textures = r->textures.p; a.shapes.texels = r->texels.p; a.shapes.srgb_lut = r->srgb_lut.p;
-	a.shapes.bvh = r->bvh.p; a.shapes.n_bvh_nodes = r->n_bvh_nodes;
-	a.shapes.n_quads = r->n_quads; a.shapes.n_spheres = r->n_spheres; a.shapes.n_boxes = r->n_boxes;
-	a.mats = r->mats.p; a.emitters = r->emitters.p; a.n_emitters = r->n_emitters; a.ior = r->ior.p;
-	a.dir_lights.lights = r->dir_lights.p;
-	for (int c = 0; c < 4; ++c) a.dir_lights.bsphere[c] = r->bsphere[c];
-	a.cam = r->cam;
+	const SceneState &sc = r->scene;
+	a.shapes.quads = sc.quads.p; a.shapes.spheres = sc.spheres.p; a.shapes.boxes = sc.boxes.p; a.shapes.tris = sc.tris.p;
+	a.shapes.tri_normals = sc.have_tri_normals ? sc.tri_normals.p : nullptr;
+	a.shapes.tri_uvs = sc.have_tri_uvs ? sc.tri_uvs.p : nullptr;
+	a.shapes.textures = sc.textures.p; a.shapes.texels = sc.texels.p; a.shapes.srgb_lut = sc.srgb_lut.p;
+	a.shapes.bvh = sc.bvh.p; a.shapes.n_bvh_nodes = sc.n_bvh_nodes;
+	a.shapes.n_quads = sc.n_quads; a.shapes.n_spheres = sc.n_spheres; a.shapes.n_boxes = sc.n_boxes;
+	a.mats = sc.mats.p; a.emitters = sc.emitters.p; a.n_emitters = sc.n_emitters; a.ior = r->ior.p;
+	a.dir_lights.lights = sc.dir_lights.p;
+	for (int c = 0; c < 4; ++c) a.dir_lights.bsphere[c] = sc.bsphere[c];
+	a.cam = sc.cam;
 	// the pass
 	a.n_lanes = P * (uint64_t)prm->spp; a.n_pixels = P; a.pixel_begin = prm->pixel_begin;
 	a.stripe_rows = prm->stripe_rows; a.stripe_index = prm->stripe_index; a.stripe_count = prm->stripe_count;
-	a.film_pixels = (uint64_t)r->cam.width * (uint64_t)r->cam.height;
+	a.film_pixels = (uint64_t)r->scene.cam.width * (uint64_t)r->scene.cam.height;
 	a.spp = prm->spp; a.max_depth = D; a.rr_depth = prm->rr_depth; a.seed = prm->seed; a.batched = prm->batched ? 1 : 0;
 	a.guided = ctx->iteration > 1 ? 1 : 0; // :223, 250, 283
 	a.record = ctx->is_final ? 0 : 1; a.store_nee = ctx->store_nee; a.frac = ctx->bsdf_fraction;
@@ -808,7 +805,7 @@ static RenderArgs pass_args(pg_context *ctx, const pg_pass_params *prm, PassBuf 
 	a.ph = ctx->ph_on ? ctx->ph_buf.p : nullptr;
 	// pg_render_stages: the SD-tree calls in k_wave_shade / k_wave_shade_a, or in k_wave_guide of their own -- which
 	// pg_render_overlap needs, to run them beside the shadow rays
-	const bool wave = r->general >= 2; // mesh scenes: the split pipeline
+	const bool wave = r->scene.general >= 2; // mesh scenes: the split pipeline
 	a.fuse_guide = wave && r->stages < 2 && !(r->overlap & 1) ? 1 : 0;
 	// the buffer set
 	a.ray_d = b.ray_d.p; a.thr = b.thr.p; a.L = L_out; a.prev_p = b.prev_p.p;
@@ -832,13 +829,13 @@ static void quad_bounce(pg_render_state *r, const RenderArgs &a, int it, hipStre
 	Timed t(r, s, Timer::Bounce);
 	if (tail_checkpoint(it, a.max_depth)) { // finishes every path in one launch once few are left (see k_bounce_tail)
 		const dim3 tgrid((unsigned)((kTailPaths + kRBlock - 1) / kRBlock));
-		if (r->general == 1) hipLaunchKernelGGL((k_bounce_tail<1>), tgrid, dim3(kRBlock), 0, s, a);
+		if (r->scene.general == 1) hipLaunchKernelGGL((k_bounce_tail<1>), tgrid, dim3(kRBlock), 0, s, a);
 		else hipLaunchKernelGGL((k_bounce_tail<0>), tgrid, dim3(kRBlock), 0, s, a);
 	}
 	// every launch is sized for the whole wavefront: the live count is only known on the device,
 	// and workgroups past it retire on their first instruction
 	const dim3 grid((unsigned)((a.n_lanes + kRBlock - 1) / kRBlock));
-	if (r->general == 1) {
+	if (r->scene.general == 1) {
 		if (it == 0) hipLaunchKernelGGL((k_bounce<true, 1>), grid, dim3(kRBlock), 0, s, a);
 		else hipLaunchKernelGGL((k_bounce<false, 1>), grid, dim3(kRBlock), 0, s, a);
 	} else {
@@ -881,7 +878,7 @@ static int wave_bounce(pg_context *ctx, PassBuf &b, RenderArgs &a, int it, int s
 	const unsigned blocks = (unsigned)((N + kRBlock - 1) / kRBlock);
 	auto launch = [&](WaveStage stage, hipStream_t on, unsigned grid_blocks) {
 		Timed t(r, on, timer_of(stage));
-		launch_wave_stage(stage, r->general, it == 0, a, grid_blocks, (unsigned)ctx->n_cus, on);
+		launch_wave_stage(stage, r->scene.general, it == 0, a, grid_blocks, (unsigned)ctx->n_cus, on);
 	};
 	// the state set this bounce reads and the one its survivors are written to; the camera rays of the first
 	// launch go to the set the first bounce reads
@@ -948,7 +945,7 @@ static int finish_pass(pg_context *ctx, int slot, const RenderArgs &a, uint8_t *
 		launch_splat_list(ctx->view(), ctx->f.accum_view(), ctx->store_nee, a.n_lanes, a.max_depth, a.L, a.Lq, lr, b.live_count.p, s);
 		PG_HIP(ctx, hipGetLastError());
 	}
-	if (r->general >= 2) {
+	if (r->scene.general >= 2) {
 		Timed t(r, s, Timer::Finish);
 		hipLaunchKernelGGL(k_layout_L, dim3((unsigned)((a.n_lanes + kRBlock - 1) / kRBlock)), dim3(kRBlock), 0, s, b.Lq.p, a.L, a.n_lanes);
 	}
@@ -1002,207 +999,6 @@ static int send_live_counts(pg_context *ctx, PassBuf &b, uint64_t N, int D, hipS
 
 extern "C" {
 
-int pg_scene_set(pg_context *ctx, uint64_t n_quads, const float *h_quads, const pg_camera *cam)
-{
-	pg_scene_desc d;
-	d.n_quads = n_quads; d.quads = h_quads;
-	d.n_spheres = 0; d.spheres = nullptr;
-	d.n_materials = 0; d.materials = nullptr;
-	d.n_boxes = 0; d.boxes = nullptr;
-	d.n_tris = 0; d.tris = nullptr;
-	d.n_bvh_nodes = 0; d.bvh = nullptr;
-	d.n_dir_lights = 0; d.dir_lights = nullptr;
-	d.bsphere[0] = d.bsphere[1] = d.bsphere[2] = d.bsphere[3] = 0.0f;
-	d.tri_normals = nullptr;
-	d.tri_uvs = nullptr;
-	d.n_textures = 0; d.textures = nullptr; d.texels = nullptr; d.n_texels = 0; d.srgb_lut = nullptr;
-	return pg_scene_set_ex(ctx, &d, cam);
-}
-
-int pg_scene_set_ex(pg_context *ctx, const pg_scene_desc *sc, const pg_camera *cam)
-{
-	if (!ctx) return PG_ERR_INVALID;
-	if (!sc || !cam) return fail(ctx, PG_ERR_INVALID, "pg_scene_set: NULL pointer");
-	const uint64_t nq = sc->n_quads, ns = sc->n_spheres, nm = sc->n_materials, nb = sc->n_boxes;
-	if (nq + ns + nb + sc->n_tris == 0 || nq > 4096 || ns > 4096 || nb > 4096 || (nq && !sc->quads) || (ns && !sc->spheres) || (nb && !sc->boxes))
-		return fail(ctx, PG_ERR_INVALID, "pg_scene_set: need 1..4096 quads, spheres and/or boxes");
-	if ((nm && !sc->materials) || (!sc->materials && (ns || nb)))
-		return fail(ctx, PG_ERR_INVALID, "pg_scene_set: spheres and boxes need a material table");
-	if (cam->width <= 0 || cam->height <= 0) return fail(ctx, PG_ERR_INVALID, "pg_scene_set: bad film size");
-	// host copies: material indices checked, a material table made up for scenes that come without one,
-	// the diffuse reflectance mirrored into the quads (the quad-only kernels read it there)
-	std::vector<float> quads(sc->quads, sc->quads + nq * kQuadStride);
-	std::vector<float> mats;
-	if (sc->materials) {
-		mats.assign(sc->materials, sc->materials + nm * kMaterialStride);
-	} else {
-		mats.assign(nq * kMaterialStride, 0.0f);
-		for (uint64_t q = 0; q < nq; ++q) {
-			for (int c = 0; c < 3; ++c) mats[q * kMaterialStride + 1 + c] = quads[q * kQuadStride + 16 + c];
-			quads[q * kQuadStride + 22] = (float)q;
-		}
-	}
-	const uint64_t n_mats = mats.size() / kMaterialStride;
-	const uint64_t n_tex = sc->n_textures;
-	if (n_tex > 65536 || (n_tex && (!sc->textures || !sc->srgb_lut))) return fail(ctx, PG_ERR_INVALID, "pg_scene_set: textures need their table and the sRGB lookup table");
-	for (uint64_t t = 0; t < n_tex; ++t) { // a texture's texels must lie inside the texel array
-		const uint32_t *T = sc->textures + t * kTextureStride;
-		if (T[0] == 1u) {
-			if (T[1] == 0u || T[2] == 0u || T[1] > 65536u || T[2] > 65536u || !sc->texels || (uint64_t)T[3] + (uint64_t)T[1] * T[2] > sc->n_texels)
-				return fail(ctx, PG_ERR_INVALID, "pg_scene_set: bitmap texture outside the texel array");
-		} else if (T[0] != 2u) return fail(ctx, PG_ERR_INVALID, "pg_scene_set: unknown texture kind");
-	}
-	for (uint64_t m = 0; m < n_mats; ++m) {
-		const float type = mats[m * kMaterialStride];
-		if (type != 0.0f && type != 1.0f && type != 2.0f && type != 3.0f && type != 4.0f)
-			return fail(ctx, PG_ERR_INVALID, "pg_scene_set: unknown material type");
-		const float alpha = mats[m * kMaterialStride + 4]; // > 0: Beckmann, < 0: GGX of roughness -alpha
-		if ((type == 1.0f || type == 4.0f) && !(fabsf(alpha) > 0.0f && fabsf(alpha) < 3.0e38f))
-			return fail(ctx, PG_ERR_INVALID, "pg_scene_set: microfacet alpha must be finite and not 0");
-		if ((type == 3.0f || type == 4.0f) && !(mats[m * kMaterialStride + 5] > 0.0f))
-			return fail(ctx, PG_ERR_INVALID, "pg_scene_set: dielectric index ratio must be > 0");
-		const float tex = mats[m * kMaterialStride + 12];
-		if (!(tex >= 0.0f && tex <= (float)n_tex) || tex != (float)(uint64_t)tex)
-			return fail(ctx, PG_ERR_INVALID, "pg_scene_set: material texture index out of range");
-	}
-	// feature level of the kernels (see intersect()): decided by the materials the shapes USE
-	int general = ns > 0 ? 1 : 0;
-	auto use_material = [&](uint64_t m) {
-		const float type = mats[m * kMaterialStride];
-		if (type == 1.0f && general < 1) general = 1;                              // rough conductor
-		if (type >= 2.0f || mats[m * kMaterialStride + 11] != 0.0f) general = 3;   // transmission, delta lobes, one-sided BSDFs
-	};
-	const uint64_t nd = sc->n_dir_lights;
-	if (nd > 64 || (nd && !sc->dir_lights)) return fail(ctx, PG_ERR_INVALID, "pg_scene_set: at most 64 directional lights");
-	if (nd && !(sc->bsphere[3] > 0.0f)) return fail(ctx, PG_ERR_INVALID, "pg_scene_set: directional lights need the scene's bounding sphere");
-	if (nd) general = 3;
-	for (uint64_t q = 0; q < nq; ++q) {
-		const float mi = quads[q * kQuadStride + 22];
-		if (!(mi >= 0.0f && mi < (float)n_mats) || mi != (float)(uint64_t)mi)
-			return fail(ctx, PG_ERR_INVALID, "pg_scene_set: quad material index out of range");
-		use_material((uint64_t)mi);
-		const float *M = &mats[(uint64_t)mi * kMaterialStride];
-		if (M[0] == 0.0f)
-			for (int c = 0; c < 3; ++c) quads[q * kQuadStride + 16 + c] = M[1 + c];
-	}
-	for (uint64_t s = 0; s < ns; ++s) {
-		const float mi = sc->spheres[s * kSphereStride + 4];
-		if (!(mi >= 0.0f && mi < (float)n_mats) || mi != (float)(uint64_t)mi)
-			return fail(ctx, PG_ERR_INVALID, "pg_scene_set: sphere material index out of range");
-		use_material((uint64_t)mi);
-		if (!(sc->spheres[s * kSphereStride + 3] > 0.0f)) return fail(ctx, PG_ERR_INVALID, "pg_scene_set: sphere radius must be > 0");
-	}
-	for (uint64_t b = 0; b < nb; ++b) {
-		const float mi = sc->boxes[b * kBoxStride + 21];
-		if (!(mi >= 0.0f && mi < (float)n_mats) || mi != (float)(uint64_t)mi)
-			return fail(ctx, PG_ERR_INVALID, "pg_scene_set: box material index out of range");
-		use_material((uint64_t)mi);
-		for (int k = 0; k < 21; ++k)
-			if (!(sc->boxes[b * kBoxStride + k] == sc->boxes[b * kBoxStride + k]) || fabsf(sc->boxes[b * kBoxStride + k]) > 3.0e38f)
-				return fail(ctx, PG_ERR_INVALID, "pg_scene_set: box transform is not finite");
-	}
-	// triangle meshes: the kernels walk the BVH with a fixed-size stack and trust it, so check it here:
-	// children follow their parent (no cycles, one parent each), leaves stay inside the triangle
-	// array, and no walk can have more than kLdsStack + kOvfStack siblings waiting on its stack
-	const uint64_t nt = sc->n_tris, nn = sc->n_bvh_nodes;
-	// (the walk addresses a node by a 32-bit byte offset: 2^25 nodes of 128 bytes)
-	if ((nt == 0) != (nn == 0) || (nt && (!sc->tris || !sc->bvh)) || nt > 0x0fffffffull || nn > 0x02000000ull)
-		return fail(ctx, PG_ERR_INVALID, "pg_scene_set: triangles and BVH nodes go together");
-	if (nt && !sc->materials) return fail(ctx, PG_ERR_INVALID, "pg_scene_set: meshes need a material table");
-	if (nn) {
-		std::vector<uint8_t> waiting(nn, 0); // siblings on the stack when the walk opens node i, at most
-		std::vector<uint8_t> seen(nn, 0);
-		seen[0] = 1;
-		for (uint64_t i = 0; i < nn; ++i) {
-			if (!seen[i]) return fail(ctx, PG_ERR_INVALID, "pg_scene_set: BVH node without a parent");
-			const uint32_t *N = sc->bvh + i * kBvhStride;
-			int kids = 0;
-			for (int c = 0; c < 4; ++c) kids += N[24 + c] != 0xffffffffu;
-			if (kids == 0) return fail(ctx, PG_ERR_INVALID, "pg_scene_set: BVH node without children");
-			const int below = (int)waiting[i] + kids - 1; // its other children wait while the walk is in one of them
-			if (below > kMinLdsStack + kOvfStack) return fail(ctx, PG_ERR_INVALID, "pg_scene_set: BVH too deep for the walk's stack (32 waiting siblings)");
-			for (int c = 0; c < 4; ++c) {
-				const uint32_t ref = N[24 + c];
-				if (ref == 0xffffffffu) continue;
-				if (ref & 0x80000000u) {
-					const uint64_t first = ref & 0x0fffffffu, count = ((ref >> 28) & 7u) + 1u;
-					if (first + count > nt) return fail(ctx, PG_ERR_INVALID, "pg_scene_set: BVH leaf outside the triangle array");
-				} else {
-					if (ref <= i || ref >= nn) return fail(ctx, PG_ERR_INVALID, "pg_scene_set: BVH children must follow their parent");
-					if (seen[ref]) return fail(ctx, PG_ERR_INVALID, "pg_scene_set: BVH node with two parents");
-					seen[ref] = 1;
-					waiting[ref] = (uint8_t)below;
-				}
-			}
-		}
-		for (uint64_t t = 0; t < nt; ++t) {
-			const float mi = sc->tris[t * kTriStride + 12];
-			if (!(mi >= 0.0f && mi < (float)n_mats) || mi != (float)(uint64_t)mi)
-				return fail(ctx, PG_ERR_INVALID, "pg_scene_set: triangle material index out of range");
-			use_material((uint64_t)mi);
-		}
-		if (general < 2) general = 2;
-	}
-	// (a textured material on anything but a triangle with texture coordinates keeps its plain colour)
-	std::vector<int32_t> em;
-	for (uint64_t q = 0; q < nq; ++q)
-		if (quads[q * kQuadStride + 15] != 0.0f) em.push_back((int32_t)q);
-	for (uint64_t s = 0; s < ns; ++s)
-		if (sc->spheres[s * kSphereStride + 5] != 0.0f) em.push_back((int32_t)(nq + s));
-	for (uint64_t k = 0; k < nd; ++k) em.push_back(-1 - (int32_t)k);
-	PG_HIP(ctx, hipSetDevice(ctx->device));
-	pg_render_state *r = rstate(ctx);
-	PG_HIP(ctx, r->dir_lights.ensure(nd * 8));
-	if (nd) PG_HIP(ctx, hipMemcpy(r->dir_lights.p, sc->dir_lights, nd * 8 * sizeof(float), hipMemcpyHostToDevice));
-	for (int c = 0; c < 4; ++c) r->bsphere[c] = sc->bsphere[c];
-	PG_HIP(ctx, r->quads.ensure(nq * kQuadStride)); PG_HIP(ctx, r->spheres.ensure(ns * kSphereStride));
-	PG_HIP(ctx, r->mats.ensure(mats.size())); PG_HIP(ctx, r->emitters.ensure(em.size()));
-	PG_HIP(ctx, r->boxes.ensure(nb * kBoxStride));
-	if (nb) PG_HIP(ctx, hipMemcpy(r->boxes.p, sc->boxes, nb * kBoxStride * sizeof(float), hipMemcpyHostToDevice));
-	r->n_boxes = (int)nb;
-	PG_HIP(ctx, r->tris.ensure(nt * kTriStride)); PG_HIP(ctx, r->bvh.ensure(nn * kBvhStride));
-	if (nt) PG_HIP(ctx, hipMemcpy(r->tris.p, sc->tris, nt * kTriStride * sizeof(float), hipMemcpyHostToDevice));
-	if (nn) {
-		// an absent child gets a box no ray reaches, (+inf, -inf) on every axis, whatever the caller left there: the walk
-		// then needs no test of the reference (bvh_node_step)
-		std::vector<uint32_t> nodes(sc->bvh, sc->bvh + nn * kBvhStride);
-		for (uint64_t i = 0; i < nn; ++i)
-			for (int c = 0; c < 4; ++c)
-				if (nodes[i * kBvhStride + 24 + c] == 0xffffffffu)
-					for (int row = 0; row < 6; ++row) nodes[i * kBvhStride + row * 4 + c] = row < 3 ? 0x7f800000u : 0xff800000u;
-		PG_HIP(ctx, hipMemcpy(r->bvh.p, nodes.data(), nn * kBvhStride * sizeof(uint32_t), hipMemcpyHostToDevice));
-	}
-	r->n_bvh_nodes = (int)nn;
-	r->have_tri_normals = nt && sc->tri_normals;
-	if (r->have_tri_normals) {
-		PG_HIP(ctx, r->tri_normals.ensure(nt * 9));
-		PG_HIP(ctx, hipMemcpy(r->tri_normals.p, sc->tri_normals, nt * 9 * sizeof(float), hipMemcpyHostToDevice));
-	}
-	r->have_tri_uvs = nt && sc->tri_uvs && n_tex;
-	if (r->have_tri_uvs) {
-		PG_HIP(ctx, r->tri_uvs.ensure(nt * 6));
-		PG_HIP(ctx, hipMemcpy(r->tri_uvs.p, sc->tri_uvs, nt * 6 * sizeof(float), hipMemcpyHostToDevice));
-		PG_HIP(ctx, r->textures.ensure(n_tex * kTextureStride));
-		PG_HIP(ctx, hipMemcpy(r->textures.p, sc->textures, n_tex * kTextureStride * sizeof(uint32_t), hipMemcpyHostToDevice));
-		PG_HIP(ctx, r->texels.ensure(sc->n_texels ? sc->n_texels : 1));
-		if (sc->n_texels) PG_HIP(ctx, hipMemcpy(r->texels.p, sc->texels, sc->n_texels * sizeof(uint32_t), hipMemcpyHostToDevice));
-		PG_HIP(ctx, r->srgb_lut.ensure(256));
-		PG_HIP(ctx, hipMemcpy(r->srgb_lut.p, sc->srgb_lut, 256 * sizeof(float), hipMemcpyHostToDevice));
-	}
-	if (nq) PG_HIP(ctx, hipMemcpy(r->quads.p, quads.data(), quads.size() * sizeof(float), hipMemcpyHostToDevice));
-	if (ns) PG_HIP(ctx, hipMemcpy(r->spheres.p, sc->spheres, ns * kSphereStride * sizeof(float), hipMemcpyHostToDevice));
-	PG_HIP(ctx, hipMemcpy(r->mats.p, mats.data(), mats.size() * sizeof(float), hipMemcpyHostToDevice));
-	if (!em.empty()) PG_HIP(ctx, hipMemcpy(r->emitters.p, em.data(), em.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-	r->n_quads = (int)nq;
-	r->n_spheres = (int)ns;
-	r->n_emitters = (int)em.size();
-	if (r->split_always && general < 2) general = 2; // pg_render_split_pipeline
-	r->general = general;
-	r->cam = *cam;
-	r->have_scene = true;
-	return PG_OK;
-}
-
 int pg_render_pass(pg_context *ctx, const pg_pass_params *prm, float *L_out, uint8_t *valid_out, float *sumL,
                    float *sumL2, void *stream)
 {
@@ -1215,14 +1011,14 @@ int pg_render_pass(pg_context *ctx, const pg_pass_params *prm, float *L_out, uin
 	const uint64_t N = P * (uint64_t)prm->spp;
 	PassBuf &b = r->pb[slot];
 	r->last_slot = slot;
-	if (sumL && (uint64_t)r->cam.width * (uint64_t)r->cam.height > ctx->num_rays)
+	if (sumL && (uint64_t)r->scene.cam.width * (uint64_t)r->scene.cam.height > ctx->num_rays)
 		return fail(ctx, PG_ERR_INVALID, "pg_render_pass: sumL/sumL2 are sized by pg_setup's num_rays, which is smaller than the film");
 	if ((rc = ensure_pass_buffers(ctx, slot, N, !ctx->is_final)) != PG_OK) return rc;
 	// counters of a pass, zeroed together: live_count[D + 1] ([D]: entries handed out by the tail launch), then for
 	// mesh scenes cast_count[2 D] and shadow_count[D] of the persistent ray-casting kernels
 	PG_HIP(ctx, hipMemsetAsync(b.live_count.p, 0, ((size_t)D + 1 + 3 * (size_t)D) * sizeof(uint32_t), s));
 	RenderArgs a = pass_args(ctx, prm, b, P, L_out);
-	const bool wave = r->general >= 2; // mesh scenes: the split pipeline
+	const bool wave = r->scene.general >= 2; // mesh scenes: the split pipeline
 	// sorted bounces (pg_render_sort): from the second bounce (camera rays find neighbouring vertices by themselves) to
 	// the depth at which Russian roulette thins the list out (:375: a sort costs what 33 M pairs cost however few are alive)
 	const int sort_until = wave && r->sort ? (prm->rr_depth < D ? prm->rr_depth : D) : 0;
@@ -1276,7 +1072,7 @@ int pg_render_reserve(pg_context *ctx, uint64_t n_lanes)
 {
 	if (!ctx) return PG_ERR_INVALID;
 	if (!ctx->configured) return fail(ctx, PG_ERR_INVALID, "call pg_setup or pg_import first");
-	if (!ctx->render || !ctx->render->have_scene) return fail(ctx, PG_ERR_INVALID, "pg_render_reserve: call pg_scene_set first");
+	if (!ctx->render || !ctx->render->scene.have_scene) return fail(ctx, PG_ERR_INVALID, "pg_render_reserve: call pg_scene_set first");
 	if (ctx->max_depth <= 0 || n_lanes == 0) return fail(ctx, PG_ERR_INVALID, "pg_render_reserve: max_depth and n_lanes must be > 0");
 	if (n_lanes * (uint64_t)ctx->max_depth > 0xffffffffull) return fail(ctx, PG_ERR_INVALID, "pg_render_reserve: more than 2^32 record slots in one pass");
 	PG_HIP(ctx, hipSetDevice(ctx->device));
@@ -1328,12 +1124,12 @@ static int film_launch(pg_context *ctx, int32_t filter, bool batched, uint32_t s
                        float scale = 1.0f, int acc_set = 0)
 {
 	if (!ctx) return PG_ERR_INVALID;
-	if (!ctx->render || !ctx->render->have_scene) return fail(ctx, PG_ERR_INVALID, "pg_film: call pg_scene_set first");
+	if (!ctx->render || !ctx->render->scene.have_scene) return fail(ctx, PG_ERR_INVALID, "pg_film: call pg_scene_set first");
 	if (!L || (!image_out && !acc) || spp <= 0) return fail(ctx, PG_ERR_INVALID, "pg_film: NULL pointer or spp <= 0");
 	if (stripe_count > 1 && (stripe_rows == 0 || stripe_index >= stripe_count)) return fail(ctx, PG_ERR_INVALID, "pg_film_stripes: bad stripe parameters");
 	if (filter != PG_FILTER_TENT && filter != PG_FILTER_GAUSSIAN) return fail(ctx, PG_ERR_INVALID, "pg_film: unknown filter");
 	PG_HIP(ctx, hipSetDevice(ctx->device));
-	const pg_camera &cam = ctx->render->cam;
+	const pg_camera &cam = ctx->render->scene.cam;
 	const uint64_t npix = (uint64_t)cam.width * (uint64_t)cam.height;
 	const dim3 grid((unsigned)((npix + kRBlock - 1) / kRBlock)), block(kRBlock);
 	hipStream_t st = (hipStream_t)stream;

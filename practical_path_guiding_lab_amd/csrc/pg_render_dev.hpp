@@ -8,6 +8,7 @@
 #include "pg_context.hpp"
 #include "pg_descent.hpp"
 #include "pg_kernels.hpp"
+#include "pg_scene_layout.hpp"
 
 // The microfacet helpers are called from several places and inlined at every one of them: a call needs a stack frame in
 // scratch memory, and no kernel of the library is to use any.  (Rounds 1-4 kept them out of line in the fused kernel of
@@ -21,7 +22,6 @@ static_assert(kRBlock == kStageThreads, "stage_kd_planes copies one plane per th
 constexpr float kInvPiF = 0.31830988618379067154f;
 constexpr float kRayEps = 1e-4f;
 constexpr float kShadowEps = 1e-3f;
-constexpr int kQuadStride = 24;
 
 struct v3 {
 	float x, y, z;
@@ -72,29 +72,29 @@ constexpr float kPiF = 3.14159265358979323846f;
 constexpr float kInvTwoPiF = 0.15915494309189533577f;
 constexpr float kInvSqrtPiF = 0.56418958354775628695f;
 constexpr float kSphereEps = 8.94069671630859375e-05f; // Mitsuba's math::RayEpsilon<float> = 1500 * 2^-24
-constexpr int kSphereStride = 12;                       // PG_SPHERE_STRIDE
-constexpr int kMaterialStride = 16;                     // PG_MATERIAL_STRIDE
-constexpr int kTextureStride = 16;                      // PG_TEXTURE_STRIDE (32-bit words)
 
 __device__ __forceinline__ float safe_sqrtf(float v) { return __builtin_sqrtf(v > 0.0f ? v : 0.0f); }
 __device__ __forceinline__ v3 normalize3(v3 v) { return vdivs(v, __builtin_sqrtf(dot3(v, v))); }
 
-constexpr int kBoxStride = 32; // PG_BOX_STRIDE
-
 // The shapes of a scene: quads, then spheres, then box faces (shape number = quad index,
 // n_quads + sphere index, or n_quads + n_spheres + 6 box + 2 axis + (outward normal negative))
 // ... then the triangles of the meshes, in BVH leaf order (general scenes only)
-constexpr int kTriStride = 16; // PG_TRI_STRIDE
-constexpr int kBvhStride = 32; // PG_BVH_STRIDE
 struct Shapes {
 	const float *quads, *spheres, *boxes, *tris;
-	const float *tri_normals; // 9 per triangle, or nullptr (face normals)
-	const float *tri_uvs;     // 6 per triangle (uv0 uv1 uv2), or nullptr
+	const float *tri_normals; // kTriNormalStride per triangle, or nullptr (face normals)
+	const float *tri_uvs;     // kTriUvStride per triangle (uv0 uv1 uv2), or nullptr
 	const uint32_t *bvh;
 	const uint32_t *textures; // kTextureStride words each
 	const uint32_t *texels;   // RGBA8 sRGB texels of all bitmaps
 	const float *srgb_lut;    // 256 floats: 8-bit sRGB -> linear
 	int n_quads, n_spheres, n_boxes, n_bvh_nodes;
+	// the shape numbering, written once
+	__host__ __device__ __forceinline__ int first_box_face() const { return n_quads + n_spheres; }
+	__host__ __device__ __forceinline__ int first_tri() const { return n_quads + n_spheres + 6 * n_boxes; }
+	__host__ __device__ __forceinline__ int box_face_of(int prim) const { return prim - n_quads - n_spheres; } // prim >= first_box_face(): 6 box + face
+	__host__ __device__ __forceinline__ int tri_of(int prim) const { return prim - n_quads - n_spheres - 6 * n_boxes; } // prim >= first_tri()
+	// (term by term, not `prim - first_...()`: that form lets the compiler prove the result non-negative and changes the
+	// division by 6 of every kernel that shades a box face -- a code change, which this numbering's one definition is not)
 };
 
 // The stack of the BVH walk: no per-lane array (that would live in scratch memory).  The first
@@ -105,6 +105,7 @@ struct Shapes {
 constexpr int kLdsStack = 8;  // entries of a lane in LDS in the ray-casting kernels (k_wave_shade keeps fewer: BvhStack::n_lds)
 constexpr int kOvfStack = 28; // entries of a lane's overflow strip: 32 (what pg_scene_set_ex admits) minus the fewest any kernel keeps in LDS
 constexpr int kMinLdsStack = 4;
+static_assert(kMinLdsStack + kOvfStack == kBvhMaxWaiting, "pg_scene_set_ex admits the trees whose walks fit the smallest stack");
 typedef __attribute__((address_space(3))) uint32_t LdsWord; // an LDS pointer stays one: ds_read / ds_write, never flat
 typedef __attribute__((address_space(3))) u32x4_t LdsQuad;
 struct BvhStack {
@@ -145,7 +146,7 @@ __device__ __forceinline__ BvhStack bvh_stack(uint2 *lds_column, uint2 *ovf, uin
 
 __device__ __forceinline__ v3 box_face_normal(const float *B, int face)
 {
-	const v3 n = ld3(B + 12 + 3 * (face >> 1));
+	const v3 n = ld3(B + BOX_NORMALS + 3 * (face >> 1));
 	return (face & 1) ? V(-n.x, -n.y, -n.z) : n;
 }
 
@@ -204,25 +205,25 @@ __device__ __forceinline__ void intersect_linear(const Shapes &sh, v3 o, v3 d, f
 	const float *__restrict__ quads = sh.quads;
 	for (int q = 0; q < nq; ++q) {
 		const float *Q = quads + q * kQuadStride;
-		const v3 n = ld3(Q + 9);
+		const v3 n = ld3(Q + QUAD_NORMAL);
 		const float denom = dot3(n, d);
 		if (denom == 0.0f) continue;
-		const float num = dot3(n, vsub(ld3(Q), o));
+		const float num = dot3(n, vsub(ld3(Q + QUAD_ORIGIN), o));
 		// IEEE division keeps the sign: when the signs differ t is not > 0 and the (correctly rounded,
 		// hence long) division can be skipped without changing any result
 		if ((__float_as_uint(num) ^ __float_as_uint(denom)) >> 31) continue;
 		const float t = num / denom;
 		if (!(t > 0.0f && t < bt)) continue;
-		const v3 w = vsub(vadd(o, vscale(d, t)), ld3(Q));
-		const float u = dot3(w, ld3(Q + 3)) * Q[12];
-		const float v = dot3(w, ld3(Q + 6)) * Q[13];
+		const v3 w = vsub(vadd(o, vscale(d, t)), ld3(Q + QUAD_ORIGIN));
+		const float u = dot3(w, ld3(Q + QUAD_E1)) * Q[QUAD_INV_E1_2];
+		const float v = dot3(w, ld3(Q + QUAD_E2)) * Q[QUAD_INV_E2_2];
 		if (u >= 0.0f && u <= 1.0f && v >= 0.0f && v <= 1.0f) { bt = t; best = q; }
 	}
 	if (kGeneral) { // spheres: the quadratic in double precision, as Mitsuba's Sphere::ray_intersect_preliminary
 		for (int s = 0; s < sh.n_spheres; ++s) {
 			const float *S = sh.spheres + s * kSphereStride;
-			const double ox = (double)o.x - (double)S[0], oy = (double)o.y - (double)S[1], oz = (double)o.z - (double)S[2];
-			const double dx = (double)d.x, dy = (double)d.y, dz = (double)d.z, r = (double)S[3];
+			const double ox = (double)o.x - (double)S[SPH_CENTRE], oy = (double)o.y - (double)S[SPH_CENTRE + 1], oz = (double)o.z - (double)S[SPH_CENTRE + 2];
+			const double dx = (double)d.x, dy = (double)d.y, dz = (double)d.z, r = (double)S[SPH_RADIUS];
 			const double A = (dx * dx + dy * dy) + dz * dz;
 			const double B = 2.0 * ((ox * dx + oy * dy) + oz * dz);
 			const double C = ((ox * ox + oy * oy) + oz * oz) - r * r;
@@ -240,9 +241,10 @@ __device__ __forceinline__ void intersect_linear(const Shapes &sh, v3 o, v3 d, f
 	// instead of six quad tests (t is the same in both frames: the map is linear)
 	for (int b = 0; b < sh.n_boxes; ++b) {
 		const float *B = sh.boxes + b * kBoxStride;
-		const v3 oc = vsub(o, ld3(B + 9));
-		const float ol[3] = {dot3(ld3(B), oc), dot3(ld3(B + 3), oc), dot3(ld3(B + 6), oc)};
-		const float dl[3] = {dot3(ld3(B), d), dot3(ld3(B + 3), d), dot3(ld3(B + 6), d)};
+		const v3 oc = vsub(o, ld3(B + BOX_CENTRE));
+		const float *R = B + BOX_INV_ROWS;
+		const float ol[3] = {dot3(ld3(R), oc), dot3(ld3(R + 3), oc), dot3(ld3(R + 6), oc)};
+		const float dl[3] = {dot3(ld3(R), d), dot3(ld3(R + 3), d), dot3(ld3(R + 6), d)};
 		float tn = -__builtin_huge_valf(), tf = __builtin_huge_valf();
 		int an = 0, af = 0;
 		bool miss = false;
@@ -266,7 +268,7 @@ __device__ __forceinline__ void intersect_linear(const Shapes &sh, v3 o, v3 d, f
 		const float da = axis == 0 ? dl[0] : (axis == 1 ? dl[1] : dl[2]);
 		const int negative = entering ? (da > 0.0f) : (da < 0.0f);
 		bt = t;
-		best = nq + sh.n_spheres + 6 * b + 2 * axis + negative;
+		best = sh.first_box_face() + 6 * b + 2 * axis + negative;
 	}
 }
 
@@ -281,7 +283,6 @@ __device__ __forceinline__ void intersect_linear(const Shapes &sh, v3 o, v3 d, f
 // is the same one in both.  pg_scene_set_ex has checked the tree: children follow their parent, and no
 // root-to-node path can leave more than kLdsStack + kOvfStack siblings waiting, so the walk opens every
 // node at most once and the stack cannot overflow; the budget is a second fence.
-constexpr uint32_t kBvhNone = 0xffffffffu;
 struct BvhWalk {
 	v3 o, d, inv;
 	int row_nx, row_fx, row_ny, row_fy, row_nz, row_fz; // byte offsets of the rows of a node that hold the near / far planes for this ray
@@ -295,7 +296,10 @@ struct BvhWalk {
 __device__ __forceinline__ void bvh_rows(v3 d, int &nx, int &fx, int &ny, int &fy, int &nz, int &fz)
 {
 	const bool ngx = (__float_as_uint(d.x) >> 31) != 0u, ngy = (__float_as_uint(d.y) >> 31) != 0u, ngz = (__float_as_uint(d.z) >> 31) != 0u;
-	nx = ngx ? 48 : 0; fx = ngx ? 0 : 48; ny = ngy ? 64 : 16; fy = ngy ? 16 : 64; nz = ngz ? 80 : 32; fz = ngz ? 32 : 80;
+	constexpr int lo = BVH_BOXES * 4, hi = lo + BVH_HI_ROW * (int)kBvhRowBytes, row = (int)kBvhRowBytes;
+	nx = ngx ? hi : lo; fx = ngx ? lo : hi;
+	ny = ngy ? hi + row : lo + row; fy = ngy ? lo + row : hi + row;
+	nz = ngz ? hi + 2 * row : lo + 2 * row; fz = ngz ? lo + 2 * row : hi + 2 * row;
 }
 
 __device__ __forceinline__ void bvh_begin(BvhWalk &w, const Shapes &sh, v3 o, v3 d, float bt, int best)
@@ -327,21 +331,21 @@ __device__ __forceinline__ void bvh_node_step(BvhWalk &w, const Shapes &sh, cons
 	// address per row -- ten vector registers less, seven waves per SIMD instead of six for the closest hits (15.6 -> 15.0 ms
 	// per step, shadow rays 8.5 -> 7.8); pg_scene_set_ex keeps the table under 4 GiB
 	const char *B = reinterpret_cast<const char *>(sh.bvh);
-	const uint32_t nb = w.next * (uint32_t)(kBvhStride * 4);
+	const uint32_t nb = w.next * kBvhNodeBytes;
 	uint4 nx4, ny4, nz4, fx4, fy4, fz4, rf;
 	// The walks are bound by the texture-address path -- seven 16-byte gathers per lane and node, 16 cycles of the unit
 	// each, whether they hit the L1 or not.  The nodes most rays open (mesh.build_bvh numbers them first) are read from a
 	// copy in LDS instead: closest hits 15.1 -> 11.9 ms per step of veach-ajar, shadow rays 7.9 -> 7.0 with 32 nodes.
 	if (w.next < stk.n_top) {
-		const LdsQuad *T = stk.top + w.next * 8u;
+		const LdsQuad *T = stk.top + w.next * (uint32_t)kBvhNodeQuads;
 #define PG_Q(r) ({ const u32x4_t q_ = T[r]; make_uint4(q_.x, q_.y, q_.z, q_.w); })
 		nx4 = PG_Q(row_nx >> 4); ny4 = PG_Q(row_ny >> 4); nz4 = PG_Q(row_nz >> 4);
-		fx4 = PG_Q(row_fx >> 4); fy4 = PG_Q(row_fy >> 4); fz4 = PG_Q(row_fz >> 4); rf = PG_Q(6);
+		fx4 = PG_Q(row_fx >> 4); fy4 = PG_Q(row_fy >> 4); fz4 = PG_Q(row_fz >> 4); rf = PG_Q(BVH_REFS / BVH_WIDTH);
 #undef PG_Q
 	} else {
 		nx4 = gather16(B + (nb + (uint32_t)row_nx)); ny4 = gather16(B + (nb + (uint32_t)row_ny)); nz4 = gather16(B + (nb + (uint32_t)row_nz));
 		fx4 = gather16(B + (nb + (uint32_t)row_fx)); fy4 = gather16(B + (nb + (uint32_t)row_fy)); fz4 = gather16(B + (nb + (uint32_t)row_fz));
-		rf = gather16(B + (nb + 96u));
+		rf = gather16(B + (nb + kBvhRefsByte));
 	}
 	uint32_t r0 = rf.x, r1 = rf.y, r2 = rf.z, r3 = rf.w;
 	float t0, t1, t2, t3;
@@ -388,11 +392,11 @@ __device__ __forceinline__ void bvh_tri_test(BvhWalk &w, v3 v0, v3 e1, v3 e2, in
 
 __device__ __forceinline__ void bvh_leaf_step(BvhWalk &w, const Shapes &sh, int tri_base)
 {
-	const uint32_t first = w.next & 0x0fffffffu, count = ((w.next >> 28) & 7u) + 1u;
+	const uint32_t first = bvh_leaf_first(w.next), count = bvh_leaf_count(w.next);
 	for (uint32_t i = first; i < first + count; ++i) {
 		const float *T = sh.tris + (size_t)i * kTriStride;
-		v3 v0 = ld3(T);
-		const v3 e1 = ld3(T + 3), e2 = ld3(T + 6);
+		v3 v0 = ld3(T + TRI_V0);
+		const v3 e1 = ld3(T + TRI_E1), e2 = ld3(T + TRI_E2);
 		// (the triangle's nine floats are asked for TOGETHER: left alone the compiler sinks the load of v0 behind the test of the
 		// determinant, which only e1 and e2 enter -- two round trips per triangle where one does; round 6, from the listing)
 		asm volatile("" : "+v"(v0.x), "+v"(v0.y), "+v"(v0.z));
@@ -421,18 +425,18 @@ __device__ __forceinline__ int intersect(const Shapes &sh, v3 o, v3 d, float tma
 	float bt = tmax;
 	intersect_linear<kGeneral>(sh, o, d, bt, best);
 	if (kGeneral >= 2 && sh.n_bvh_nodes && !(kAny && best >= 0)) {
-		const int tri_base = sh.n_quads + sh.n_spheres + 6 * sh.n_boxes;
+		const int tri_base = sh.first_tri();
 		BvhWalk w;
 		bvh_begin(w, sh, o, d, bt, best);
 		while (true) {
 			// (a lane none of whose children the ray reaches takes its next candidate from the stack at once instead of
 			// idling until the other lanes of its wave have found their leaves: closest hits 16.4 -> 15.6 ms per step,
 			// shadow rays 9.5 -> 8.6; the ray's own sequence of steps is the same)
-			while (!(w.next & 0x80000000u) && w.budget > 0) {
+			while (!(w.next & kBvhLeafBit) && w.budget > 0) {
 				bvh_node_step<kSlim>(w, sh, stk);
 				if (w.next == kBvhNone) bvh_pop(w, stk);
 			}
-			if (w.next != kBvhNone && (w.next & 0x80000000u)) {
+			if (w.next != kBvhNone && (w.next & kBvhLeafBit)) {
 				bvh_leaf_step(w, sh, tri_base);
 				if (kAny && w.best >= 0) break; // a shadow ray needs one occluder, not the nearest
 			}
@@ -467,12 +471,16 @@ __device__ __forceinline__ int intersect(const Shapes &sh, v3 o, v3 d, float tma
 __device__ __forceinline__ v3 texture_eval(const Shapes &sh, int index, float u, float v)
 {
 	const uint32_t *T = sh.textures + (size_t)index * kTextureStride;
-	const uint4 t0 = *reinterpret_cast<const uint4 *>(T), t2 = *reinterpret_cast<const uint4 *>(T + 8),
-	            t3 = *reinterpret_cast<const uint4 *>(T + 12);
+	// the descriptor as its four 16-byte groups: t0 = kind, width, height, first texel; t1 = color0, color1.r; t2 = color1.gb,
+	// to_uv scale; t3 = to_uv offset
+	static_assert(TEX_KIND == 0 && TEX_WIDTH == 1 && TEX_HEIGHT == 2 && TEX_FIRST == 3 && TEX_COLOR0 == 4 && TEX_COLOR1 == 7 &&
+	              TEX_UV_SCALE == 10 && TEX_UV_OFFSET == 12, "texture_eval names the words of the groups by .x .y .z .w");
+	const uint4 t0 = *reinterpret_cast<const uint4 *>(T + TEX_KIND), t2 = *reinterpret_cast<const uint4 *>(T + TEX_COLOR1 + 1),
+	            t3 = *reinterpret_cast<const uint4 *>(T + TEX_UV_OFFSET);
 	const float uu = __uint_as_float(t2.z) * u + __uint_as_float(t3.x);
 	const float vv = __uint_as_float(t2.w) * v + __uint_as_float(t3.y);
-	if (t0.x == 2u) {
-		const uint4 t1 = *reinterpret_cast<const uint4 *>(T + 4);
+	if (t0.x == TEX_CHECKERBOARD) {
+		const uint4 t1 = *reinterpret_cast<const uint4 *>(T + TEX_COLOR0);
 		const float fu = uu - __builtin_floorf(uu), fv = vv - __builtin_floorf(vv);
 		const bool mx = fu > 0.5f, my = fv > 0.5f;
 		return mx == my ? V(__uint_as_float(t1.x), __uint_as_float(t1.y), __uint_as_float(t1.z))
@@ -503,10 +511,10 @@ __device__ __forceinline__ v3 texture_eval(const Shapes &sh, int index, float u,
 
 // ---- surface description at a hit ----
 struct Material {
-	int type;        // 0 diffuse, 1 roughconductor (Beckmann, visible normals), 2 smooth conductor, 3 smooth dielectric, 4 roughdielectric
+	int type;        // a MaterialType
 	v3 refl;         // reflectance | specular_reflectance
 	const float *M;  // the material row: alpha, eta, k are read where the BSDF needs them
-	bool one_sided;  // not wrapped in `twosided` (row word 11)
+	bool one_sided;  // not wrapped in `twosided` (MAT_ONE_SIDED)
 };
 struct Surface {
 	v3 p, n, radiance; // n: the normal of the shading frame
@@ -514,6 +522,17 @@ struct Surface {
 	bool is_em;
 	Material m;
 };
+
+// the material of a shape from its row of the table, for a kernel of feature level `level` (what a level cannot meet is not read)
+__device__ __forceinline__ Material load_material(const float *row, int level)
+{
+	Material m;
+	m.type = level ? (int)row[MAT_TYPE] : MAT_DIFFUSE; // a scene with anything but twosided diffuse runs the general kernels
+	m.one_sided = level >= 3 && row[MAT_ONE_SIDED] != 0.0f;
+	m.refl = ld3(row + MAT_REFL);
+	m.M = row;
+	return m;
+}
 
 // bu, bv: the barycentrics the closest-hit walk found for a triangle (the oracle recomputes them by
 // the intersection's own formulas: the same numbers)
@@ -523,81 +542,74 @@ __device__ __forceinline__ Surface surface_at(const Shapes &sh, const float *mat
 {
 	Surface s;
 	const float *M;
-	if (kGeneral >= 2 && prim >= sh.n_quads + sh.n_spheres + 6 * sh.n_boxes) { // a mesh triangle
+	if (kGeneral >= 2 && prim >= sh.first_tri()) { // a mesh triangle
 		// (Measured and removed, round 5: ONE 128-byte line per triangle with everything this branch reads -- face normal +
 		// material, nine vertex normals, six texture coordinates: five 16-byte gathers of one line instead of seven or eight of
 		// three arrays.  k_wave_shade 28.0 -> 28.3 ms per step: the tightly packed arrays put two to five neighbouring
 		// triangles into a cache line, and the lanes of a spatially sorted wave hit neighbouring triangles.
 		// profiles/r05/ab_triangle_shading_line_rejected.txt)
-		const size_t ti = (size_t)(prim - sh.n_quads - sh.n_spheres - 6 * sh.n_boxes);
+		const size_t ti = (size_t)sh.tri_of(prim);
 		const float *T = sh.tris + ti * kTriStride;
 		s.p = vadd(o, vscale(d, t));
-		s.n = ld3(T + 9);
+		s.n = ld3(T + TRI_NORMAL);
 		s.ng = s.n;
 		s.is_em = false;
 		s.radiance = V(0, 0, 0);
-		M = mats + (int)T[12] * kMaterialStride;
-		s.m.type = (int)M[0];
-		s.m.one_sided = kGeneral >= 3 && M[11] != 0.0f;
-		s.m.refl = ld3(M + 1);
-		s.m.M = M;
-		const int tex = (int)M[12];
+		s.m = load_material(mats + (int)T[TRI_MATERIAL] * kMaterialStride, kGeneral);
+		const int tex = (int)s.m.M[MAT_TEXTURE];
 		const bool textured = tex > 0 && sh.tri_uvs;
 		const float b0 = (1.0f - bu) - bv;
 		if (sh.tri_normals) { // interpolated vertex normals
-			const float *Nn = sh.tri_normals + ti * 9;
+			const float *Nn = sh.tri_normals + ti * kTriNormalStride;
 			const v3 ns = vadd(vadd(vscale(ld3(Nn), b0), vscale(ld3(Nn + 3), bu)), vscale(ld3(Nn + 6), bv));
 			const float l2 = dot3(ns, ns);
 			if (l2 > 0.0f) s.n = vdivs(ns, __builtin_sqrtf(l2));
 		}
 		if (textured) { // interpolated texture coordinates, then the texture in place of the reflectance
-			const float *U = sh.tri_uvs + ti * 6;
+			const float *U = sh.tri_uvs + ti * kTriUvStride;
 			const float tu = (U[0] * b0 + U[2] * bu) + U[4] * bv;
 			const float tv = (U[1] * b0 + U[3] * bu) + U[5] * bv;
 			s.m.refl = texture_eval(sh, tex - 1, tu, tv);
 		}
 		return s;
-	} else if (prim >= sh.n_quads + sh.n_spheres) { // a box face
-		const int f = prim - sh.n_quads - sh.n_spheres;
+	} else if (prim >= sh.first_box_face()) { // a box face
+		const int f = sh.box_face_of(prim);
 		const float *B = sh.boxes + (f / 6) * kBoxStride;
 		s.p = vadd(o, vscale(d, t));
 		s.n = box_face_normal(B, f % 6);
 		s.ng = s.n;
 		s.is_em = false;
 		s.radiance = V(0, 0, 0);
-		M = mats + (int)B[21] * kMaterialStride;
+		M = mats + (int)B[BOX_MATERIAL] * kMaterialStride;
 	} else if (!kGeneral || prim < sh.n_quads) {
 		const float *Q = sh.quads + prim * kQuadStride;
 		s.p = vadd(o, vscale(d, t));
-		s.n = ld3(Q + 9);
+		s.n = ld3(Q + QUAD_NORMAL);
 		s.ng = s.n;
-		s.is_em = Q[15] != 0.0f;
-		s.radiance = ld3(Q + 19);
+		s.is_em = Q[QUAD_EMITTER] != 0.0f;
+		s.radiance = ld3(Q + QUAD_RADIANCE);
 		if (!kGeneral) { // all-diffuse quad scene: the reflectance sits in the quad itself (pg_scene_set keeps it there)
-			s.m.type = 0;
-			s.m.refl = ld3(Q + 16);
+			s.m.type = MAT_DIFFUSE;
+			s.m.refl = ld3(Q + QUAD_REFL);
 			s.m.M = nullptr;
 			s.m.one_sided = false;
 			return s;
 		}
-		M = mats + (int)Q[22] * kMaterialStride;
+		M = mats + (int)Q[QUAD_MATERIAL] * kMaterialStride;
 	} else {
 		const float *S = sh.spheres + (prim - sh.n_quads) * kSphereStride;
-		const v3 c = ld3(S);
+		const v3 c = ld3(S + SPH_CENTRE);
 		// sphere.h: n = normalize(ray(t) - c), p = c + n r; the normal is then taken again from the
 		// re-projected point so that it is a function of p alone (the next bounce recomputes it)
 		const v3 n0 = normalize3(vsub(vadd(o, vscale(d, t)), c));
-		s.p = vadd(c, vscale(n0, S[3]));
+		s.p = vadd(c, vscale(n0, S[SPH_RADIUS]));
 		s.n = normalize3(vsub(s.p, c));
 		s.ng = s.n;
-		s.is_em = S[5] != 0.0f;
-		s.radiance = ld3(S + 6);
-		M = mats + (int)S[4] * kMaterialStride;
+		s.is_em = S[SPH_EMITTER] != 0.0f;
+		s.radiance = ld3(S + SPH_RADIANCE);
+		M = mats + (int)S[SPH_MATERIAL] * kMaterialStride;
 	}
-	s.m.type = kGeneral ? (int)M[0] : 0; // a scene with anything but twosided diffuse runs the general kernels
-	s.m.one_sided = kGeneral >= 3 && M[11] != 0.0f;
-	s.m.refl = ld3(M + 1);
-	s.m.M = M;
+	s.m = load_material(M, kGeneral);
 	return s;
 }
 
@@ -605,14 +617,13 @@ __device__ __forceinline__ Surface surface_at(const Shapes &sh, const float *mat
 template <int kGeneral>
 __device__ __forceinline__ v3 normal_at(const Shapes &sh, int prim, v3 p)
 {
-	if (kGeneral >= 2 && prim >= sh.n_quads + sh.n_spheres + 6 * sh.n_boxes)
-		return ld3(sh.tris + (size_t)(prim - sh.n_quads - sh.n_spheres - 6 * sh.n_boxes) * kTriStride + 9);
-	if (prim >= sh.n_quads + sh.n_spheres) {
-		const int f = prim - sh.n_quads - sh.n_spheres;
+	if (kGeneral >= 2 && prim >= sh.first_tri()) return ld3(sh.tris + (size_t)sh.tri_of(prim) * kTriStride + TRI_NORMAL);
+	if (prim >= sh.first_box_face()) {
+		const int f = sh.box_face_of(prim);
 		return box_face_normal(sh.boxes + (f / 6) * kBoxStride, f % 6);
 	}
-	if (!kGeneral || prim < sh.n_quads) return ld3(sh.quads + prim * kQuadStride + 9);
-	return normalize3(vsub(p, ld3(sh.spheres + (prim - sh.n_quads) * kSphereStride)));
+	if (!kGeneral || prim < sh.n_quads) return ld3(sh.quads + prim * kQuadStride + QUAD_NORMAL);
+	return normalize3(vsub(p, ld3(sh.spheres + (prim - sh.n_quads) * kSphereStride + SPH_CENTRE)));
 }
 
 // scene.pdf_emitter_direction(prev, ds) for a hit on emitter shape `prim` at p (normal n) seen from
@@ -627,14 +638,14 @@ __device__ __forceinline__ float emitter_hit_pdf(const Shapes &sh, int prim, v3 
 	if (!(dp < 0.0f)) return 0.0f;
 	float pdf;
 	if (!kGeneral || prim < sh.n_quads) {
-		pdf = d2 / (fabs_(dp) * sh.quads[prim * kQuadStride + 14]);
+		pdf = d2 / (fabs_(dp) * sh.quads[prim * kQuadStride + QUAD_AREA]);
 	} else { // Sphere::pdf_direction
 		const float *S = sh.spheres + (prim - sh.n_quads) * kSphereStride;
-		const v3 cv = vsub(ld3(S), ref);
-		const float sin_alpha = S[3] / __builtin_sqrtf(dot3(cv, cv));
+		const v3 cv = vsub(ld3(S + SPH_CENTRE), ref);
+		const float sin_alpha = S[SPH_RADIUS] / __builtin_sqrtf(dot3(cv, cv));
 		const float cos_alpha = safe_sqrtf(1.0f - sin_alpha * sin_alpha);
 		if (sin_alpha < 0.99999994f) pdf = kInvTwoPiF / (1.0f - cos_alpha);
-		else pdf = (d2 / fabs_(dp)) / ((4.0f * kPiF) * (S[3] * S[3]));
+		else pdf = (d2 / fabs_(dp)) / ((4.0f * kPiF) * (S[SPH_RADIUS] * S[SPH_RADIUS]));
 	}
 	return pdf * inv_count;
 }
@@ -713,7 +724,8 @@ __device__ __forceinline__ float fresnel_conductor(float cos_i, float eta_r, flo
 
 __device__ __forceinline__ v3 rc_fresnel(const float *M, float cos_i)
 {
-	return V(fresnel_conductor(cos_i, M[5], M[8]), fresnel_conductor(cos_i, M[6], M[9]), fresnel_conductor(cos_i, M[7], M[10]));
+	return V(fresnel_conductor(cos_i, M[MAT_ETA], M[MAT_K]), fresnel_conductor(cos_i, M[MAT_ETA + 1], M[MAT_K + 1]),
+	         fresnel_conductor(cos_i, M[MAT_ETA + 2], M[MAT_K + 2]));
 }
 
 __device__ PG_OUTLINE float erfinv_call(float x) { return erfinv_f32(x); }
@@ -783,7 +795,7 @@ __device__ __forceinline__ void rc_eval_pdf(const Material &mt, v3 wi, v3 wo, v3
 	value = V(0, 0, 0);
 	pdf = 0.0f;
 	if (!(wi.z > 0.0f && wo.z > 0.0f)) return;
-	const float alpha = mt.M[4];
+	const float alpha = mt.M[MAT_ALPHA];
 	const v3 H = normalize3(vadd(wo, wi));
 	const float D = rc_D(H, alpha);
 	if (D == 0.0f) return;
@@ -797,7 +809,7 @@ __device__ __forceinline__ void rc_eval_pdf(const Material &mt, v3 wi, v3 wo, v3
 __device__ __forceinline__ void rc_sample(const Material &mt, v3 wi, float u1, float u2, v3 &wo, float &pdf, v3 &weight) // wi.z > 0
 {
 	wo = V(0, 0, 0); pdf = 0.0f; weight = V(0, 0, 0);
-	const float alpha = mt.M[4];
+	const float alpha = mt.M[MAT_ALPHA];
 	float pdf_m;
 	const v3 m = rc_sample_m(wi, alpha, u1, u2, pdf_m);
 	const float wim = dot3(wi, m);
@@ -831,14 +843,14 @@ __device__ __forceinline__ float fresnel_dielectric(float cos_i, float eta, floa
 
 // ---- roughdielectric (Beckmann, isotropic, sample_visible) after Mitsuba 3's roughdielectric.cpp:
 // reflection and transmission through a rough interface, radiance transport; wi on either side,
-// M[4] = alpha, M[5] = int_ior / ext_ior.  Out of line: only scenes with such a material get here.
+// MAT_ALPHA, MAT_ETA = int_ior / ext_ior.  Out of line: only scenes with such a material get here.
 __device__ __forceinline__ v3 vflip_if(v3 v, bool c) { return c ? V(-v.x, -v.y, -v.z) : v; }
 
 __device__ PG_OUTLINE void rd_eval_pdf(const float *M, v3 wi, v3 wo, v3 &value, float &pdf)
 {
 	value = V(0, 0, 0);
 	pdf = 0.0f;
-	const float alpha = M[4], eta_m = M[5];
+	const float alpha = M[MAT_ALPHA], eta_m = M[MAT_ETA];
 	const float ci = wi.z, co = wo.z;
 	if (ci == 0.0f) return;
 	const bool reflect = ci * co > 0.0f;
@@ -869,7 +881,7 @@ __device__ PG_OUTLINE void rd_eval_pdf(const float *M, v3 wi, v3 wo, v3 &value, 
 __device__ PG_OUTLINE void rd_sample(const float *M, v3 wi, float u1, float u, float v, v3 &wo, float &pdf, v3 &weight, float &eta_out)
 {
 	wo = V(0, 0, 0); pdf = 0.0f; weight = V(0, 0, 0); eta_out = 0.0f;
-	const float alpha = M[4], eta_m = M[5];
+	const float alpha = M[MAT_ALPHA], eta_m = M[MAT_ETA];
 	const float ci = wi.z;
 	if (ci == 0.0f) return;
 	float pdf_m;
@@ -903,7 +915,7 @@ __device__ PG_OUTLINE void rd_sample(const float *M, v3 wi, float u1, float u, f
 }
 
 // BSDFFlags.Smooth (:210): does the material have a non-delta lobe?
-__device__ __forceinline__ bool material_is_smooth(const Material &mt) { return mt.type != 2 && mt.type != 3; }
+__device__ __forceinline__ bool material_is_smooth(const Material &mt) { return mt.type != MAT_CONDUCTOR && mt.type != MAT_DIELECTRIC; }
 
 // bsdf.eval_pdf (twosided unless the material says otherwise): value includes cos(theta_o)
 template <int kGeneral>
@@ -912,13 +924,13 @@ __device__ __forceinline__ void bsdf_eval_pdf(const Material &mt, v3 wi, v3 wo, 
 	value = V(0, 0, 0);
 	pdf = 0.0f;
 	if (!active) return;
-	if (kGeneral >= 3 && (mt.type == 2 || mt.type == 3)) return; // smooth conductor / dielectric: delta lobes only
-	if (kGeneral >= 3 && mt.type == 4) {
+	if (kGeneral >= 3 && (mt.type == MAT_CONDUCTOR || mt.type == MAT_DIELECTRIC)) return; // smooth conductor / dielectric: delta lobes only
+	if (kGeneral >= 3 && mt.type == MAT_ROUGH_DIELECTRIC) {
 		rd_eval_pdf(mt.M, wi, wo, value, pdf);
 		return;
 	}
 	if (wi.z < 0.0f && !(kGeneral >= 3 && mt.one_sided)) { wi.z = -wi.z; wo.z = -wo.z; }
-	if (kGeneral && mt.type == 1) {
+	if (kGeneral && mt.type == MAT_ROUGH_CONDUCTOR) {
 		rc_eval_pdf(mt, wi, wo, value, pdf);
 		return;
 	}
@@ -936,9 +948,9 @@ __device__ __forceinline__ void bsdf_sample(const Material &mt, v3 wi, float u1,
 {
 	wo = V(0, 0, 0); pdf = 0.0f; weight = V(0, 0, 0); eta = 0.0f; delta = false;
 	if (!active) return;
-	if (kGeneral >= 3 && mt.type == 3) { // smooth dielectric (dielectric.cpp), radiance transport
+	if (kGeneral >= 3 && mt.type == MAT_DIELECTRIC) { // smooth dielectric (dielectric.cpp), radiance transport
 		float cos_t, eta_it, eta_ti;
-		const float r_i = fresnel_dielectric(wi.z, mt.M[5], cos_t, eta_it, eta_ti);
+		const float r_i = fresnel_dielectric(wi.z, mt.M[MAT_ETA], cos_t, eta_it, eta_ti);
 		const bool reflect = u1 <= r_i;
 		const float sc = eta_ti * eta_ti;
 		delta = true;
@@ -948,14 +960,14 @@ __device__ __forceinline__ void bsdf_sample(const Material &mt, v3 wi, float u1,
 		weight = reflect ? V(1, 1, 1) : V(sc, sc, sc);
 		return;
 	}
-	if (kGeneral >= 3 && mt.type == 4) {
+	if (kGeneral >= 3 && mt.type == MAT_ROUGH_DIELECTRIC) {
 		rd_sample(mt.M, wi, u1, u, v, wo, pdf, weight, eta);
 		return;
 	}
 	const bool flip = wi.z < 0.0f && !(kGeneral >= 3 && mt.one_sided);
 	const float cos_i = flip ? -wi.z : wi.z;
 	if (!(cos_i > 0.0f)) return;
-	if (kGeneral >= 3 && mt.type == 2) { // smooth conductor (conductor.cpp): the mirror direction, weighted by Fresnel
+	if (kGeneral >= 3 && mt.type == MAT_CONDUCTOR) { // smooth conductor (conductor.cpp): the mirror direction, weighted by Fresnel
 		delta = true;
 		pdf = 1.0f;
 		eta = 1.0f;
@@ -963,7 +975,7 @@ __device__ __forceinline__ void bsdf_sample(const Material &mt, v3 wi, float u1,
 		weight = vmul(rc_fresnel(mt.M, cos_i), mt.refl);
 		return;
 	}
-	if (kGeneral && mt.type == 1) {
+	if (kGeneral && mt.type == MAT_ROUGH_CONDUCTOR) {
 		v3 o;
 		rc_sample(mt, V(wi.x, wi.y, cos_i), u, v, o, pdf, weight);
 		eta = 1.0f;
@@ -981,93 +993,18 @@ __device__ __forceinline__ void bsdf_sample(const Material &mt, v3 wi, float u1,
 	wo = w;
 }
 
-// scene.sample_emitter_direction(si, (e1, e2), test_visibility=True): uniform choice of one emitter
-// (e1 is reused after the choice), then a point on it; returns ds.d, ds.pdf and radiance / pdf
-// (zero when occluded, facing away, or from inside a sphere)
 // Directional emitters of a scene (scenes/torus/scene.xml) and the bounding sphere their samples sit on
 struct DirLights {
-	const float *lights; // 8 floats each: 0-2 unit direction the light travels in, 3-5 irradiance
+	const float *lights; // kDirLightStride floats each: DL_DIRECTION, DL_IRRADIANCE
 	float bsphere[4];    // centre, radius
 };
 
-template <int kGeneral>
-__device__ __forceinline__ void sample_emitter(const Shapes &sh, const DirLights &dls, const int32_t *__restrict__ emitters,
-                                               int n_em, v3 p, v3 n, float e1, float e2, v3 &ds_d, float &ds_pdf,
-                                               v3 &em_weight, bool &ds_delta)
-{
-	ds_d = V(0, 0, 0);
-	ds_pdf = 0.0f;
-	em_weight = V(0, 0, 0);
-	ds_delta = false;
-	if (n_em <= 0) return;
-	const float count = (float)n_em, inv_count = 1.0f / count;
-	uint32_t idx = (uint32_t)(e1 * count);
-	if (idx > (uint32_t)(n_em - 1)) idx = (uint32_t)(n_em - 1);
-	e1 = e1 * count - (float)idx;
-	const int prim = emitters[idx];
-	v3 pl, ln, radiance;
-	float pdf_cone = 0.0f, area = 1.0f;
-	const bool is_sphere = kGeneral && prim >= sh.n_quads;
-	if (!is_sphere) {
-		const float *E = sh.quads + prim * kQuadStride;
-		pl = vadd(vadd(ld3(E), vscale(ld3(E + 3), e1)), vscale(ld3(E + 6), e2));
-		ln = ld3(E + 9);
-		radiance = ld3(E + 19);
-		area = E[14];
-	} else { // Sphere::sample_direction, reference point outside
-		const float *S = sh.spheres + (prim - sh.n_quads) * kSphereStride;
-		const v3 c = ld3(S);
-		const float r = S[3];
-		const v3 dc_v = vsub(c, p);
-		const float dc_2 = dot3(dc_v, dc_v);
-		const float radius_adj = r * (1.0f - kSphereEps);
-		if (!(dc_2 > radius_adj * radius_adj)) return;
-		const float inv_dc = 1.0f / __builtin_sqrtf(dc_2);
-		const float sin_max = r * inv_dc, sin_max2 = sin_max * sin_max, inv_sin_max = 1.0f / sin_max;
-		const float cos_max = safe_sqrtf(1.0f - sin_max2);
-		float sin_theta_2;
-		if (sin_max2 > 0.00068523f) { // sin^2(1.5 deg)
-			const float tt = 1.0f + (cos_max - 1.0f) * e1;
-			sin_theta_2 = 1.0f - tt * tt;
-		} else sin_theta_2 = sin_max2 * e1; // small-angle Taylor expansion
-		const float cos_theta = safe_sqrtf(1.0f - sin_theta_2);
-		const float cos_alpha = sin_theta_2 * inv_sin_max +
-		                        cos_theta * safe_sqrtf(1.0f - sin_theta_2 * (inv_sin_max * inv_sin_max));
-		const float sin_alpha = safe_sqrtf(1.0f - cos_alpha * cos_alpha);
-		float sin_phi, cos_phi;
-		sincos_f32(e2 * (2.0f * kPiF), sin_phi, cos_phi);
-		const Frame fr = make_frame(vscale(dc_v, -inv_dc));
-		const v3 dl = to_world(fr, V(cos_phi * sin_alpha, sin_phi * sin_alpha, cos_alpha));
-		pl = vadd(c, vscale(dl, r));
-		ln = dl;
-		radiance = ld3(S + 6);
-		pdf_cone = kInvTwoPiF / (1.0f - cos_max);
-	}
-	const v3 dir0 = vsub(pl, p);
-	// si.spawn_ray_to(pl): offset origin, then aim at the light point
-	float mag = (1.0f + max3(V(fabs_(p.x), fabs_(p.y), fabs_(p.z)))) * kRayEps;
-	if (dot3(n, dir0) < 0.0f) mag = -mag;
-	const v3 so = vadd(p, vscale(n, mag));
-	const float d2 = dot3(dir0, dir0), dist = __builtin_sqrtf(d2);
-	ds_d = vdivs(dir0, dist);
-	const float dp = dot3(ds_d, ln);
-	float pdf = 0.0f;
-	if (dp < 0.0f) pdf = is_sphere ? (dist == 0.0f ? 0.0f : pdf_cone) : d2 / (fabs_(dp) * area);
-	if (!(pdf == pdf) || pdf == __builtin_huge_valf()) pdf = 0.0f;
-	ds_pdf = pdf * inv_count;
-	if (pdf > 0.0f) {
-		const v3 sd = vsub(pl, so);
-		const float sdist = __builtin_sqrtf(dot3(sd, sd));
-		const v3 sdn = vdivs(sd, sdist);
-		float th;
-		const bool occ = intersect<kGeneral, true>(sh, so, sdn, sdist * (1.0f - kShadowEps), th) >= 0;
-		if (!occ) em_weight = vscale(vdivs(radiance, pdf), count);
-	}
-}
-
-// sample_emitter without the visibility test, for the split pipeline: returns the shadow ray
-// (origin, unit direction, length to test) and em_weight as if unoccluded; `need_shadow` says whether
-// the caller has to trace it (and zero em_weight when it is occluded).  Same arithmetic otherwise.
+// scene.sample_emitter_direction(si, (e1, e2), test_visibility=True): uniform choice of one emitter
+// (e1 is reused after the choice), then a point on it; returns ds.d, ds.pdf and radiance / pdf
+// (zero when occluded, facing away, or from inside a sphere)
+// The emitter sample without its visibility test: returns the shadow ray (origin, unit direction, length to test) and
+// em_weight as if unoccluded; `need_shadow` says whether the caller has to trace it (and zero em_weight when it is
+// occluded) -- the split pipeline does that in a kernel of its own, sample_emitter below in place.
 template <int kGeneral>
 __device__ __forceinline__ void sample_emitter_ray(const Shapes &sh, const DirLights &dls, const int32_t *__restrict__ emitters,
                                                    int n_em, v3 p, v3 n, float e1, float e2, v3 &ds_d, float &ds_pdf,
@@ -1087,8 +1024,8 @@ __device__ __forceinline__ void sample_emitter_ray(const Shapes &sh, const DirLi
 	e1 = e1 * count - (float)idx;
 	const int prim = emitters[idx];
 	if (kGeneral >= 3 && prim < 0) { // directional.cpp sample_direction: a point two radii up the light's direction, pdf 1, delta
-		const float *Dl = dls.lights + (size_t)(-1 - prim) * 8;
-		const v3 dl = ld3(Dl);
+		const float *Dl = dls.lights + (size_t)(-1 - prim) * kDirLightStride;
+		const v3 dl = ld3(Dl + DL_DIRECTION);
 		const v3 cd = vsub(p, V(dls.bsphere[0], dls.bsphere[1], dls.bsphere[2]));
 		const float dc = __builtin_sqrtf(dot3(cd, cd));
 		const float dist = 2.0f * (dls.bsphere[3] > dc ? dls.bsphere[3] : dc);
@@ -1103,22 +1040,22 @@ __device__ __forceinline__ void sample_emitter_ray(const Shapes &sh, const DirLi
 		const float sdist = __builtin_sqrtf(dot3(sd, sd));
 		need_shadow = true;
 		sh_o = so; sh_d = vdivs(sd, sdist); sh_tmax = sdist * (1.0f - kShadowEps);
-		em_weight = vscale(ld3(Dl + 3), count);
+		em_weight = vscale(ld3(Dl + DL_IRRADIANCE), count);
 		return;
 	}
 	v3 pl, ln, radiance;
 	float pdf_cone = 0.0f, area = 1.0f;
-	const bool is_sphere = prim >= sh.n_quads;
+	const bool is_sphere = kGeneral && prim >= sh.n_quads; // (folds the sphere branch away at level 0)
 	if (!is_sphere) {
 		const float *E = sh.quads + prim * kQuadStride;
-		pl = vadd(vadd(ld3(E), vscale(ld3(E + 3), e1)), vscale(ld3(E + 6), e2));
-		ln = ld3(E + 9);
-		radiance = ld3(E + 19);
-		area = E[14];
+		pl = vadd(vadd(ld3(E + QUAD_ORIGIN), vscale(ld3(E + QUAD_E1), e1)), vscale(ld3(E + QUAD_E2), e2));
+		ln = ld3(E + QUAD_NORMAL);
+		radiance = ld3(E + QUAD_RADIANCE);
+		area = E[QUAD_AREA];
 	} else { // Sphere::sample_direction, reference point outside
 		const float *S = sh.spheres + (prim - sh.n_quads) * kSphereStride;
-		const v3 c = ld3(S);
-		const float r = S[3];
+		const v3 c = ld3(S + SPH_CENTRE);
+		const float r = S[SPH_RADIUS];
 		const v3 dc_v = vsub(c, p);
 		const float dc_2 = dot3(dc_v, dc_v);
 		const float radius_adj = r * (1.0f - kSphereEps);
@@ -1141,7 +1078,7 @@ __device__ __forceinline__ void sample_emitter_ray(const Shapes &sh, const DirLi
 		const v3 dl = to_world(fr, V(cos_phi * sin_alpha, sin_phi * sin_alpha, cos_alpha));
 		pl = vadd(c, vscale(dl, r));
 		ln = dl;
-		radiance = ld3(S + 6);
+		radiance = ld3(S + SPH_RADIANCE);
 		pdf_cone = kInvTwoPiF / (1.0f - cos_max);
 	}
 	const v3 dir0 = vsub(pl, p);
@@ -1163,6 +1100,19 @@ __device__ __forceinline__ void sample_emitter_ray(const Shapes &sh, const DirLi
 		sh_o = so; sh_d = vdivs(sd, sdist); sh_tmax = sdist * (1.0f - kShadowEps);
 		em_weight = vscale(vdivs(radiance, pdf), count);
 	}
+}
+
+// ... with the visibility test made here (the fused kernels of pg_render.hip, feature levels 0 and 1: no BVH, no stack)
+template <int kGeneral>
+__device__ __forceinline__ void sample_emitter(const Shapes &sh, const DirLights &dls, const int32_t *__restrict__ emitters,
+                                               int n_em, v3 p, v3 n, float e1, float e2, v3 &ds_d, float &ds_pdf,
+                                               v3 &em_weight, bool &ds_delta)
+{
+	bool need_shadow;
+	v3 sh_o, sh_d;
+	float sh_tmax, th;
+	sample_emitter_ray<kGeneral>(sh, dls, emitters, n_em, p, n, e1, e2, ds_d, ds_pdf, em_weight, ds_delta, need_shadow, sh_o, sh_d, sh_tmax);
+	if (need_shadow && intersect<kGeneral, true>(sh, sh_o, sh_d, sh_tmax, th) >= 0) em_weight = V(0, 0, 0);
 }
 
 struct RenderArgs {

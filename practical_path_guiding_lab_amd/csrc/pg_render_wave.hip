@@ -98,12 +98,8 @@ __device__ __forceinline__ GuideOut guide_none(v3 wo) { GuideOut g; g.wo = wo; r
 
 __device__ __forceinline__ Material material_of(const RenderArgs &a, int mat, v3 refl, int level)
 {
-	Material m;
-	const float *M = a.mats + (size_t)mat * kMaterialStride;
-	m.type = (int)M[0];
-	m.refl = refl;
-	m.M = M;
-	m.one_sided = level >= 3 && M[11] != 0.0f;
+	Material m = load_material(a.mats + (size_t)mat * kMaterialStride, level);
+	m.refl = refl; // (as the surface left it: a texture's colour where there is one)
 	return m;
 }
 
@@ -505,18 +501,18 @@ __device__ __forceinline__ void stage_bvh_top(u32x4_t *s_top, const RenderArgs &
 	const uint32_t n = a.shapes.n_bvh_nodes < kNodes ? (uint32_t)a.shapes.n_bvh_nodes : (uint32_t)kNodes;
 	// (every load of a thread is asked for before the first is stored: as a loop -- load, wait, store, again -- the second
 	// 16 bytes of a thread began their round trip when the first had ended)
-	constexpr int kLoads = (kNodes * 8 + kRBlock - 1) / kRBlock;
+	constexpr int kLoads = (kNodes * kBvhNodeQuads + kRBlock - 1) / kRBlock;
 	if (n) { // (uniform; a scene without meshes has no table: nothing is read)
 		u32x4_t v[kLoads];
 #pragma unroll
 		for (int k = 0; k < kLoads; ++k) { // (unconditional, so that nothing ties a load to its store: a lane past the nodes reads entry 0)
 			const uint32_t i = threadIdx.x + (uint32_t)k * kRBlock;
-			v[k] = reinterpret_cast<const u32x4_t *>(a.shapes.bvh)[i < n * 8u ? i : 0u];
+			v[k] = reinterpret_cast<const u32x4_t *>(a.shapes.bvh)[i < n * (uint32_t)kBvhNodeQuads ? i : 0u];
 		}
 #pragma unroll
 		for (int k = 0; k < kLoads; ++k) {
 			const uint32_t i = threadIdx.x + (uint32_t)k * kRBlock;
-			if (i < n * 8u) s_top[i] = v[k];
+			if (i < n * (uint32_t)kBvhNodeQuads) s_top[i] = v[k];
 		}
 	}
 	__syncthreads();
@@ -553,7 +549,7 @@ __global__ __launch_bounds__(kRBlock) void k_wave_trace(RenderArgs a)
 		const uint4 *p5 = a.carry_in ? st_rec(a.carry_in, it, PS_INC) : p0;
 		q0 = *p0; q1 = *p1; q5 = *p5;
 	}
-	__shared__ u32x4_t s_top[kBvhTopNodes * 8];
+	__shared__ u32x4_t s_top[kBvhTopNodes * kBvhNodeQuads];
 	BvhStack stk = bvh_stack(&s_stack[0][threadIdx.x], a.bvh_ovf, (uint32_t)tid * (uint32_t)kOvfStack);
 	stage_bvh_top<kBvhTopNodes>(s_top, a, stk);
 	if (!alive) return;
@@ -612,10 +608,10 @@ __global__ __launch_bounds__(kRBlock) __attribute__((amdgpu_waves_per_eu(7))) vo
 	if (blockIdx.x * kRBlock >= total) return; // (uniform) not even a first entry for this workgroup
 	const unsigned wl = threadIdx.x & 63u;
 	const Shapes &sh = a.shapes;
-	__shared__ u32x4_t s_top[kBvhTopNodes * 8];
+	__shared__ u32x4_t s_top[kBvhTopNodes * kBvhNodeQuads];
 	BvhStack stk = bvh_stack(&s_stack[0][threadIdx.x], a.bvh_ovf, gtid * (uint32_t)kOvfStack);
 	stage_bvh_top<kBvhTopNodes>(s_top, a, stk);
-	const int tri_base = sh.n_quads + sh.n_spheres + 6 * sh.n_boxes;
+	const int tri_base = sh.first_tri();
 	BvhWalk w;
 	w.next = kBvhNone; w.sp = 0; w.budget = 0; w.best = -1; w.bt = 0.0f; w.bu = 0.0f; w.bv = 0.0f;
 	bool has = false, first_round = true;
@@ -670,11 +666,11 @@ __global__ __launch_bounds__(kRBlock) __attribute__((amdgpu_waves_per_eu(7))) vo
 		// next candidate from the stack ----
 		if (has) {
 			bool done = false;
-			while (!(w.next & 0x80000000u) && w.budget > 0) { // (see intersect)
+			while (!(w.next & kBvhLeafBit) && w.budget > 0) { // (see intersect)
 				bvh_node_step(w, sh, stk);
 				if (w.next == kBvhNone) bvh_pop(w, stk);
 			}
-			if (w.next != kBvhNone && (w.next & 0x80000000u)) {
+			if (w.next != kBvhNone && (w.next & kBvhLeafBit)) {
 				bvh_leaf_step(w, sh, tri_base);
 				if (w.best >= 0) done = true; // a shadow ray needs one occluder, not the nearest
 			}
@@ -986,7 +982,7 @@ static_assert(kShadeStack >= kMinLdsStack && kShadeStack <= kLdsStack, "k_wave_s
 // (the stash: the nine values of stage_a1 that only stage_b reads and the path's throughput; the radiance so far, the index of
 // refraction and the lane stay in registers -- rounds 4-5 measured the other splits)
 constexpr int kShadeStash = 12;
-constexpr int kShadeWalkQuads = kShadeStack * kRBlock / 2 + kShadeTopNodes * 8 + kShadeStash * kRBlock / 4;
+constexpr int kShadeWalkQuads = kShadeStack * kRBlock / 2 + kShadeTopNodes * kBvhNodeQuads + kShadeStash * kRBlock / 4;
 constexpr int kShadeLdsQuads = kShadeStage * PS_ENTRIES > kShadeWalkQuads ? kShadeStage * PS_ENTRIES : kShadeWalkQuads;
 // (122 vector registers, four waves per SIMD, which is also what 33 KB of LDS per workgroup allow.  Measured: staging the
 // records 128 at a time -- 23 KB -- changes nothing by itself, and compiled for five waves on top of that the kernel spills
@@ -1045,7 +1041,7 @@ __device__ __forceinline__ void shade_body(const RenderArgs &a)
 	// are in flight while the records make their own two round trips (the permutation, then the entries), instead of being
 	// two more round trips behind them, each with a barrier of its own (an instrumented pass showed a quarter of a wave's life
 	// gone before stage_a1 began: profiles/r05/shade_phases.txt).
-	constexpr int kPlaneLoads = 1, kTopLoads = (kShadeTopNodes * 8 + kRBlock - 1) / kRBlock;
+	constexpr int kPlaneLoads = 1, kTopLoads = (kShadeTopNodes * kBvhNodeQuads + kRBlock - 1) / kRBlock;
 	float pl_pre[kPlaneLoads];
 	u32x4_t top_pre[kTopLoads];
 #pragma unroll

@@ -1,0 +1,29 @@
+// pg_scene_state.hpp -- the scene a context renders, as the library keeps it: the device copies of pg_scene_desc's tables
+// (pg_scene_layout.hpp), their counts, the feature level of the kernels, the camera.  pg_scene.hip writes it (pg_scene_set_ex),
+// pg_render.hip owns it (the first block of its renderer state) and hands it to the kernels (pass_args).
+#pragma once
+
+#include "pg_context.hpp"
+
+namespace pg {
+
+struct SceneState {
+	DevBuf<float> quads, spheres, mats, boxes, tris, dir_lights, tri_normals, tri_uvs, srgb_lut;
+	DevBuf<uint32_t> textures, texels, bvh;
+	DevBuf<int32_t> emitters;
+	// Everything below is assigned together, behind the last upload of a pg_scene_set_ex that went through; have_scene is false
+	// from the first device call of an attempt on, so a failed one leaves a context WITHOUT a scene ("call pg_scene_set first"),
+	// never one whose counts speak of tables that are gone.
+	bool have_scene = false;
+	bool have_tri_normals = false, have_tri_uvs = false;
+	float bsphere[4] = {0, 0, 0, 0};
+	int n_quads = 0, n_spheres = 0, n_emitters = 0, n_boxes = 0, n_bvh_nodes = 0;
+	int general = 0; // feature level of the kernels to launch (0 cornell-box class, 1 veach-mis class, 2 meshes, 3 everything)
+	pg_camera cam;
+};
+
+// pg_render.hip: the scene of the context's renderer state (made on first use), and its pg_render_split_pipeline switch
+SceneState &scene_state(pg_context *ctx);
+bool split_pipeline_always(pg_context *ctx);
+
+} // namespace pg

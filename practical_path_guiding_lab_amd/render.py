@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .scene import Scene
+from .scene import TEXTURE_STRIDE, Scene
 
 
 class IndependentSampler:
@@ -120,7 +120,7 @@ class WavefrontScene:
             assert tu.shape == (t.shape[0], 6)
             d.tri_uvs = tu.ctypes.data
         if tex.shape[0]:
-            assert tex.shape[1] == 16 and lut.shape == (256,)
+            assert tex.shape[1] == TEXTURE_STRIDE and lut.shape == (256,)
             d.n_textures, d.textures = tex.shape[0], tex.ctypes.data
             d.n_texels, d.texels = txl.shape[0], (txl.ctypes.data if txl.size else None)
             d.srgb_lut = lut.ctypes.data

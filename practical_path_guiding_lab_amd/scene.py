@@ -20,12 +20,15 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
+from .mesh import BVH_STRIDE, TRI_STRIDE
+
 QUAD_STRIDE = 24  # floats per quad, layout documented in include/pgsd.h (pg_scene_desc)
 SPHERE_STRIDE = 12    # centre 0-2, radius 3, material 4, emitter flag 5, radiance 6-8
 MATERIAL_STRIDE = 16  # type 0, reflectance 1-3, alpha 4, eta 5-7, k 8-10, one-sided 11, texture index + 1 (0: none) 12
 TEXTURE_STRIDE = 16   # 32-bit words: kind 0 (1 bitmap, 2 checkerboard), width 1, height 2, first texel 3 (u32);
                       # color0 4-6, color1 7-9, to_uv scale 10-11 and offset 12-13 (f32 bit patterns)
 TEX_BITMAP, TEX_CHECKERBOARD = 1, 2
+DIRLIGHT_STRIDE = 8   # unit direction the light travels in 0-2, irradiance 3-5
 BOX_STRIDE = 32       # rows of the inverse linear map 0-8, centre 9-11, +x/+y/+z face normals 12-20, material 21
 MAT_DIFFUSE, MAT_ROUGHCONDUCTOR, MAT_CONDUCTOR, MAT_DIELECTRIC, MAT_ROUGHDIELECTRIC = 0, 1, 2, 3, 4
 # RGB indices of refraction Mitsuba's `material` presets resolve to in an RGB variant
@@ -57,9 +60,9 @@ class Scene:
     spheres: np.ndarray = field(default_factory=lambda: np.zeros((0, SPHERE_STRIDE), np.float32))  # (S, 12)
     materials: Optional[np.ndarray] = None  # (M, 12); None: quad i is diffuse with quads[i, 16:19]
     boxes: np.ndarray = field(default_factory=lambda: np.zeros((0, BOX_STRIDE), np.float32))        # (B, 32)
-    tris: np.ndarray = field(default_factory=lambda: np.zeros((0, 16), np.float32))                 # (T, 16), in BVH leaf order
-    bvh: np.ndarray = field(default_factory=lambda: np.zeros((0, 32), np.uint32))                   # (M, 32) four-wide nodes, mesh.py
-    dir_lights: np.ndarray = field(default_factory=lambda: np.zeros((0, 8), np.float32))            # (K, 8): direction, irradiance
+    tris: np.ndarray = field(default_factory=lambda: np.zeros((0, TRI_STRIDE), np.float32))         # (T, 16), in BVH leaf order
+    bvh: np.ndarray = field(default_factory=lambda: np.zeros((0, BVH_STRIDE), np.uint32))           # (M, 32) four-wide nodes, mesh.py
+    dir_lights: np.ndarray = field(default_factory=lambda: np.zeros((0, DIRLIGHT_STRIDE), np.float32))  # (K, 8): direction, irradiance
     tri_normals: Optional[np.ndarray] = None  # (T, 9) vertex normals per triangle in `tris` order; None: face normals
     tri_uvs: Optional[np.ndarray] = None      # (T, 6) texture coordinates uv0 uv1 uv2 per triangle in `tris` order
     textures: np.ndarray = field(default_factory=lambda: np.zeros((0, TEXTURE_STRIDE), np.uint32))  # (NT, 16) descriptors
@@ -266,7 +269,7 @@ def roughdielectric_material(alpha, int_ior: float, ext_ior: float = 1.000277, d
 def directional_light(direction, irradiance) -> np.ndarray:
     """Mitsuba `directional` emitter: `direction` is where the light travels (its to_world applied to +z)."""
     d = np.asarray(direction, np.float64)
-    out = np.zeros(8, np.float32)
+    out = np.zeros(DIRLIGHT_STRIDE, np.float32)
     out[0:3] = (d / np.linalg.norm(d)).astype(np.float32)
     out[3:6] = _f32(irradiance)
     return out
@@ -331,7 +334,7 @@ def _finish(quads: List[np.ndarray], cam: Camera, max_depth: int, rr_depth: int,
     recs = [t[0] for t in parts]
     smooth = any(len(t) > 1 and t[1] is not None for t in parts)
     mapped = any(len(t) > 2 and t[2] is not None for t in parts)
-    tr = np.concatenate(recs).astype(np.float32) if recs else np.zeros((0, 16), np.float32)
+    tr = np.concatenate(recs).astype(np.float32) if recs else np.zeros((0, TRI_STRIDE), np.float32)
     if tr.shape[0]:
         corners += [tr[:, 0:3], tr[:, 0:3] + tr[:, 3:6], tr[:, 0:3] + tr[:, 6:9]]
     corners = np.concatenate(corners)
