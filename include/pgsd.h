@@ -40,6 +40,8 @@ extern "C" {
  * builds); pg_enable_depth_counters takes mode 2.  No struct changed. */
 /* (still 6): new entry point pg_set_splat_filter (the training filters of pg_splat / pg_process_and_splat); an added entry
  * point breaks no caller and no struct changed, so the number stays. */
+/* (still 6): new entry points pg_render_record_geometry, pg_render_export_records (the filters in recording render passes, the
+ * renderer's path vertices as records); no struct changed. */
 #define PGSD_ABI_VERSION 6
 
 typedef struct pg_context pg_context;
@@ -229,9 +231,11 @@ int pg_process_and_splat(pg_context *ctx, uint64_t num_rays, int32_t max_depth,
  * Both filters may be set: the jitter first, then the directional deposits in the quadtree of the KD leaf of p'.
  * Sums stay exact integers: filtered results do not depend on the order of the records or of the launches, and refine, the
  * exchange format, pg_allreduce and export see nothing new.
- * The library's own renderer does not carry a vertex's position and directions to its splat (it names the two leaves found
- * during the bounce): while a filter other than nearest / nearest is set, a RECORDING pg_render_pass (iteration not final)
+ * The library's own renderer by default does not carry a vertex's position and directions to its splat (it names the two leaves
+ * found during the bounce): while a filter other than nearest / nearest is set, a RECORDING pg_render_pass (iteration not final)
  * fails with PG_ERR_INVALID and names the filter; it never falls back to nearest.  A final-iteration pass is unaffected.
+ * A scene set with pg_render_record_geometry on lifts the refusal: its recording passes keep the vertices' geometry and deposit
+ * through the filters (see there).
  * pg_enable_depth_counters: a filtered launch adds nothing to the depth counters. */
 #define PG_SPATIAL_NEAREST 0
 #define PG_SPATIAL_STOCHASTIC_BOX 1
@@ -521,6 +525,38 @@ int pg_render_reserve(pg_context *ctx, uint64_t n_lanes);
  * independent implementations of path_guiding_integrator.py:126-431: a cross-check, and a way to time the
  * SD-tree queries of any scene as a kernel of their own).  Takes effect at the next pg_scene_set[_ex]. */
 int pg_render_split_pipeline(pg_context *ctx, int32_t on);
+
+/* Opt-in vertex geometry in recording passes.  on != 0: every scene set from now on runs the split pipeline (as
+ * pg_render_split_pipeline, which this implies), and a RECORDING pg_render_pass of it (iteration not final)
+ *   - runs the four-kernel form of a bounce whatever pg_render_stages says (closest hits, shading A, shadow rays, the SD-tree
+ *     calls as a kernel of their own, shading B, and the tail kernel at its checkpoints), in the variants of the SD-tree and tail
+ *     kernels that also store, for every entry of the pass's record list, eight 32-bit words in planes of the list's stride
+ *     n_lanes * max_depth: the vertex's position (3), the canonical path direction (2), the canonical emitter direction (2; (0, 0)
+ *     where the bounce computed none -- such an entry's emitter luminance is zero and deposits nothing under either filter) and
+ *     the entry's bounce (1).  The planes exist only while the switch is on (32 bytes per entry more than the list's 60);
+ *   - with nearest / nearest set: deposits exactly as without the switch (the same kernel on the accumulators the entries name);
+ *     radiance, sums, accumulators and refined trees are those of a context with the switch off, bit for bit;
+ *   - with another filter set (pg_set_splat_filter) no longer fails: it deposits every kept entry -- one that survives
+ *     processPathData and the drop rules of the record boundary -- through the filters, exactly as pg_process_and_splat would for
+ *     the dense buffer the reference would have written for the pass.  The jitter's record number is the dense slot
+ *     g = ray * max_depth + depth modulo 2^32 (ray: the entry's lane of the pass, depth: its bounce), the seed the one given to
+ *     pg_set_splat_filter.  (On the initial tree every filter is the nearest deposit, as for pg_splat.)
+ *     Directional-box results are integer sums of per-record deposits: independent of launch order, of sharding (tiles, stripes,
+ *     ranks) and of batching.  Stochastic-jitter results are deterministic for a given launch, but do not equal those of a
+ *     differently batched or sharded run: record numbers are per launch.  A filtered splat does not touch the depth counters.
+ * A final-iteration pass is untouched and runs the form pg_render_stages selects.  A context with the switch off behaves exactly
+ * as before this entry point existed, the filter refusal included.  Takes effect at the next pg_scene_set[_ex].  Default 0. */
+int pg_render_record_geometry(pg_context *ctx, int32_t on);
+
+/* The kept records of the most recent pass of buffer set `slot` (pg_pass_params.slot), which must have been a recording pass of a
+ * scene set with pg_render_record_geometry on (else PG_ERR_INVALID): pg_process_records' output for the dense buffer the reference
+ * would have written -- columns of plane stride n_lanes * max_depth of THAT pass, in any order, *d_count (a device uint32, zeroed
+ * by the call) their number.  radiance and radiance_nee_lum are what processPathData yields (the list splat's division chain on
+ * the path's final radiance; the NaN-scrubbed luminance).  slot_out (device uint32[n_lanes * max_depth], may be NULL): the dense
+ * slot ray * max_depth + depth of record k.  Stream-ordered on `stream`, which must be ordered behind the pass; what it reads is
+ * valid until the next pass of that buffer set is issued.  Fed to pg_splat, the stream produces the pass's own accumulators. */
+int pg_render_export_records(pg_context *ctx, int32_t slot, const pg_records_out *out, uint32_t *slot_out, uint32_t *d_count,
+                             void *stream);
 
 /* Film reconstruction of one full-frame pass with Mitsuba's `tent` reconstruction filter of radius
  * one pixel -- the <rfilter type="tent"/> of the reference's scenes (scenes/cornell-box/scene.xml:27),

@@ -14,7 +14,28 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 
-def main():
+SPATIAL_FILTERS, DIRECTIONAL_FILTERS = ("nearest", "stochastic"), ("nearest", "box")
+
+
+def parse_splat_filter(text: str):
+    """--splat-filter SPATIAL,DIRECTIONAL -> (spatial, directional); argparse reports a bad value with the names that exist."""
+    parts = [p.strip() for p in text.split(",")]
+    if len(parts) != 2:
+        raise argparse.ArgumentTypeError(f"expected SPATIAL,DIRECTIONAL (e.g. stochastic,box), got {text!r}")
+    if parts[0] not in SPATIAL_FILTERS:
+        raise argparse.ArgumentTypeError(f"spatial filter must be one of {', '.join(SPATIAL_FILTERS)}, got {parts[0]!r}")
+    if parts[1] not in DIRECTIONAL_FILTERS:
+        raise argparse.ArgumentTypeError(f"directional filter must be one of {', '.join(DIRECTIONAL_FILTERS)}, got {parts[1]!r}")
+    return parts[0], parts[1]
+
+
+def scene_options(splat_filter) -> dict:
+    """Keyword arguments of the guided render's WavefrontScene: none by default -- only a training filter makes the scene
+    record the path vertices' geometry (pg_render_record_geometry: the split pipeline, 32 bytes more per record)."""
+    return {"record_geometry": True} if tuple(splat_filter) != ("nearest", "nearest") else {}
+
+
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--scene", default="cornell-box",
                     help="built-in scene (cornell-box, veach-mis, veach-ajar, torus) or a Mitsuba 3 scene XML of the supported subset")
@@ -39,7 +60,14 @@ def main():
     ap.add_argument("--out", default="debug/cornell-box")
     ap.add_argument("--ground-truth", default=None, help=".exr or .npy (H,W,3) linear ground truth for MSE, e.g. "
                     "scenes/cornell-box/TungstenRender.exr or tests/golden/cornell_gt_256_f16.npy")
-    args = ap.parse_args()
+    ap.add_argument("--splat-filter", type=parse_splat_filter, default=("nearest", "nearest"), metavar="SPATIAL,DIRECTIONAL",
+                    help="training filters of the recording passes (not in the reference): SPATIAL nearest | stochastic, "
+                         "DIRECTIONAL nearest | box; the default nearest,nearest runs exactly what runs without the option")
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
 
     from practical_path_guiding_lab_amd import scene as S
     from practical_path_guiding_lab_amd.driver import load_ground_truth, run_guided_render
@@ -75,9 +103,10 @@ def main():
         run_path_tracing(WavefrontScene(sc), integ, None if args.time_budget else args.budget_spp, args.time_budget,
                          chunk_spp=args.batch_spp, initial_seed=args.seed, ground_truth=gt, out_dir=args.out, gt_mask=mask)
         return
-    res = run_guided_render(WavefrontScene(sc), integ, args.budget_spp, initial_seed=args.seed, ground_truth=gt,
-                            batch_spp=args.batch_spp, training_spp_per_pass=args.training_spp_per_pass, out_dir=args.out,
-                            gt_mask=mask, training_passes_per_launch=args.training_passes_per_launch)
+    res = run_guided_render(WavefrontScene(sc, **scene_options(args.splat_filter)), integ, args.budget_spp, initial_seed=args.seed,
+                            ground_truth=gt, batch_spp=args.batch_spp, training_spp_per_pass=args.training_spp_per_pass,
+                            out_dir=args.out, gt_mask=mask, training_passes_per_launch=args.training_passes_per_launch,
+                            splat_filter=args.splat_filter if scene_options(args.splat_filter) else None)
     n = sc.camera.width * sc.camera.height * res["cumm_spp"]
     print(f"done: {res['cumm_spp']} spp in {res['time_s']:.2f} s = {n / res['time_s'] / 1e6:.1f} Msamples/s overall; "
           f"guided passes {res['guided_samples'] / max(res['guided_time_s'], 1e-9) / 1e6:.1f} Msamples/s")

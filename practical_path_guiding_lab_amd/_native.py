@@ -120,7 +120,7 @@ EXPORTS = (
     "pg_comm_unique_id", "pg_comm_init", "pg_comm_attach", "pg_comm_destroy", "pg_allreduce", "pg_render_reserve",
     "pg_render_split_pipeline", "pg_comm_info", "pg_exchange_pack", "pg_exchange_unpack", "pg_exchange_pack_words",
     "pg_exchange_unpack_words", "pg_sort_places", "pg_debug_fail_alloc", "pg_debug_fail_alloc_pending",
-    "pg_read_shade_phases", "pg_set_splat_filter",
+    "pg_read_shade_phases", "pg_set_splat_filter", "pg_render_record_geometry", "pg_render_export_records",
 )
 
 
@@ -227,6 +227,8 @@ def lib() -> C.CDLL:
     L.pg_sort_places.argtypes = [V, U64, V, V, V, V]
     L.pg_render_reserve.argtypes = [V, U64]
     L.pg_render_split_pipeline.argtypes = [V, C.c_int32]
+    L.pg_render_record_geometry.argtypes = [V, I32]
+    L.pg_render_export_records.argtypes = [V, I32, C.POINTER(pg_records_out), V, V, V]
     for name in EXPORTS:
         if name not in ("pg_last_error", "pg_abi_version"):
             getattr(L, name).restype = C.c_int

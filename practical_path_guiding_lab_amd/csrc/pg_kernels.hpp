@@ -80,6 +80,22 @@ struct pg_filter_args {
 	uint32_t seed;            // of the jitter's PCG32 streams
 	const float *kd_bmin, *kd_bmax; // [n_kd][3]: the boxes of the KD nodes (the exported columns), read by the jitter
 };
+// pg_render_record_geometry: what a geometry-recording pass keeps of every entry of its list beside it (planes of the list's
+// stride, indexed like it) -- the columns of pg_records the list leaves out, and the bounce of the entry
+struct pg_list_geometry {
+	const float *position;      // 3 planes
+	const float *direction;     // 2 planes, canonical
+	const float *direction_nee; // 2 planes, canonical; (0, 0) where the bounce computed none (such an entry's nee_lum is zero)
+	const uint32_t *depth;      // dense slot of the entry = ray_of * max_depth + depth
+};
+// the list through the filters, record number = dense slot (k_filter_splat_list); l_final_q as launch_splat_list's
+void launch_splat_list_filtered(const TreeView &t, const AccumView &a, const pg_filter_args &f, int store_nee, uint64_t num_rays,
+                                int32_t max_depth, const uint4 *l_final_q, const pg_list_records &rec, const pg_list_geometry &geo,
+                                const uint32_t *live_count, int n_cus, hipStream_t s);
+// the kept entries in pg_process_records' output layout, slot_out (may be nullptr) their dense slots; zeroes *d_count first
+void launch_export_list_records(uint64_t num_rays, int32_t max_depth, const uint4 *l_final_q, const pg_list_records &rec,
+                                const pg_list_geometry &geo, const uint32_t *live_count, const pg_records_out &out, uint32_t *slot_out,
+                                uint32_t *d_count, int n_cus, hipStream_t s);
 void launch_splat_filtered(const TreeView &t, const AccumView &a, const pg_filter_args &f, int store_nee, uint64_t m,
                            const pg_records &rec, const uint32_t *d_count, hipStream_t s);
 void launch_process_and_splat_filtered(const TreeView &t, const AccumView &a, const pg_filter_args &f, int store_nee,

@@ -615,6 +615,11 @@ struct PassBuf {
 	size_t sort_tmp_bytes = 0;
 	DevBuf<uint2> r_slot;   // the list names accumulators instead of positions and directions (pg_list_records)
 	DevBuf<uint32_t> r_tree;
+	// pg_render_record_geometry: kGeoPlanes planes beside the list (GEO_*, pg_render_dev.hpp), allocated only while the switch is
+	// on; geo_lanes: the lanes of this set's most recent pass if it recorded geometry, else 0 (pg_render_export_records)
+	DevBuf<uint32_t> r_geo;
+	uint64_t geo_lanes = 0;
+	int geo_depth = 0; // ... and its max_depth
 	// pg_render_overlap: k_wave_guide beside k_wave_cast on a library-owned stream
 	hipStream_t side = nullptr;
 	hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -643,6 +648,7 @@ struct pg_render_state {
 	SceneState scene; // what pg_scene_set_ex (pg_scene.hip) made of the scene description
 	DevBuf<float> ior;
 	bool split_always = false; // pg_render_split_pipeline: quad scenes run the split pipeline too
+	bool record_geometry = false; // pg_render_record_geometry, as the next pg_scene_set[_ex] will see it (SceneState::geometry)
 	int overlap = 0;           // pg_render_overlap
 	int stages = 0;            // pg_render_stages
 	int sort = 0;              // pg_render_sort
@@ -684,6 +690,7 @@ static pg_render_state *rstate(pg_context *ctx)
 
 SceneState &pg::scene_state(pg_context *ctx) { return rstate(ctx)->scene; }
 bool pg::split_pipeline_always(pg_context *ctx) { return rstate(ctx)->split_always; }
+bool pg::record_geometry_wanted(pg_context *ctx) { return rstate(ctx)->record_geometry; }
 
 void pg::destroy_render_state(pg_context *ctx)
 {
@@ -733,6 +740,7 @@ static int ensure_pass_buffers(pg_context *ctx, int slot, uint64_t N, bool recor
 		// (pg_list_records: 60 B per entry -- no position, no directions, one plane of radiance_nee)
 		PG_HIP(ctx, b.r_nee.ensure(S));
 		PG_HIP(ctx, b.r_slot.ensure(S)); PG_HIP(ctx, b.r_tree.ensure(S));
+		if (r->scene.geometry) PG_HIP(ctx, b.r_geo.ensure((size_t)kGeoPlanes * S)); // (pg_render_record_geometry: 32 B more per entry)
 	}
 	return PG_OK;
 }
@@ -747,11 +755,12 @@ static int check_pass(pg_context *ctx, const pg_pass_params *prm, const float *L
 	if (!prm || !L_out) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: NULL pointer");
 	if (prm->spp <= 0 || ctx->max_depth <= 0) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: spp and max_depth must be > 0");
 	if ((sumL == nullptr) != (sumL2 == nullptr)) return fail(ctx, PG_ERR_INVALID, "pg_render_pass: sumL and sumL2 go together");
-	// (the pass's record list names accumulators, not positions and directions: it cannot be filtered, and must not pretend to)
-	if (!ctx->is_final && ctx->filtered())
+	// (the pass's record list names accumulators, not positions and directions: it cannot be filtered, and must not pretend to
+	// -- unless the scene was set with pg_render_record_geometry on: then the list keeps them)
+	if (!ctx->is_final && ctx->filtered() && !ctx->render->scene.geometry)
 		return fail(ctx, PG_ERR_INVALID, std::string("pg_render_pass: a recording pass cannot apply the splat filter set by pg_set_splat_filter (spatial ") +
 		                                     (ctx->filter_spatial ? "stochastic box" : "nearest") + ", directional " +
-		                                     (ctx->filter_directional ? "box" : "nearest") + "); reset it to nearest / nearest or record through pg_splat / pg_process_and_splat");
+		                                     (ctx->filter_directional ? "box" : "nearest") + "); reset it to nearest / nearest, record through pg_splat / pg_process_and_splat, or set the scene with pg_render_record_geometry on");
 	PG_HIP(ctx, hipSetDevice(ctx->device));
 	const pg_camera &cam = ctx->render->scene.cam;
 	const uint64_t film = (uint64_t)cam.width * (uint64_t)cam.height;
@@ -807,6 +816,7 @@ static RenderArgs pass_args(pg_context *ctx, const pg_pass_params *prm, PassBuf 
 	// pg_render_overlap needs, to run them beside the shadow rays
 	const bool wave = r->scene.general >= 2; // mesh scenes: the split pipeline
 	a.fuse_guide = wave && r->stages < 2 && !(r->overlap & 1) ? 1 : 0;
+	if (r->scene.geometry && a.record) a.fuse_guide = 0; // (pg_render_record_geometry: k_wave_guide<true> stores the geometry)
 	// the buffer set
 	a.ray_d = b.ray_d.p; a.thr = b.thr.p; a.L = L_out; a.prev_p = b.prev_p.p;
 	a.prev_pdf = b.prev_pdf.p; a.prev_quad = b.prev_quad.p; a.hit0 = b.hit0.p;
@@ -876,9 +886,12 @@ static int wave_bounce(pg_context *ctx, PassBuf &b, RenderArgs &a, int it, int s
 	pg_render_state *r = ctx->render;
 	const uint64_t N = a.n_lanes;
 	const unsigned blocks = (unsigned)((N + kRBlock - 1) / kRBlock);
+	// pg_render_record_geometry: a recording pass runs the four-kernel form whatever pg_render_stages says -- its SD-tree calls
+	// are k_wave_guide<true>'s and k_wave_tail<., true>'s, the only kernels that store a vertex's geometry
+	uint32_t *const geo = r->scene.geometry && a.record ? b.r_geo.p : nullptr;
 	auto launch = [&](WaveStage stage, hipStream_t on, unsigned grid_blocks) {
 		Timed t(r, on, timer_of(stage));
-		launch_wave_stage(stage, r->scene.general, it == 0, a, grid_blocks, (unsigned)ctx->n_cus, on);
+		launch_wave_stage(stage, r->scene.general, it == 0, a, grid_blocks, (unsigned)ctx->n_cus, on, geo);
 	};
 	// the state set this bounce reads and the one its survivors are written to; the camera rays of the first
 	// launch go to the set the first bounce reads
@@ -912,7 +925,7 @@ static int wave_bounce(pg_context *ctx, PassBuf &b, RenderArgs &a, int it, int s
 		                            a.live_count + (it - 1), s));
 		a.perm = b.sort_perm.p;
 	}
-	if (r->stages == 0 && !(r->overlap & 1)) {
+	if (r->stages == 0 && !(r->overlap & 1) && !geo) {
 		launch(WaveStage::Shade, s, blocks);
 		return PG_OK;
 	}
@@ -930,6 +943,24 @@ static int wave_bounce(pg_context *ctx, PassBuf &b, RenderArgs &a, int it, int s
 	return PG_OK;
 }
 
+// the geometry planes of set b's list (stride S) as the splat kernels take them
+static pg_list_geometry list_geometry(const PassBuf &b, uint64_t S)
+{
+	pg_list_geometry g;
+	const float *f = reinterpret_cast<const float *>(b.r_geo.p);
+	g.position = f + GEO_P * S; g.direction = f + GEO_WO * S; g.direction_nee = f + GEO_NEE * S;
+	g.depth = b.r_geo.p + GEO_DEPTH * S;
+	return g;
+}
+
+static pg_list_records list_records(const PassBuf &b)
+{
+	pg_list_records lr;
+	lr.ray_of = b.ray_of.p; lr.bsdf = b.r_bsdf.p; lr.throughput_bsdf = b.r_tb.p; lr.throughput_radiance = b.r_tr.p;
+	lr.nee_lum = b.r_nee.p; lr.wo_pdf = b.r_wp.p; lr.slot = b.r_slot.p; lr.tree = b.r_tree.p;
+	return lr;
+}
+
 // Behind the bounces of a pass in buffer set `slot`: the splat of its records into sdTree_current, the output column of
 // the split pipeline (k_layout_L), the valid flags and the per-pixel sums (k_finish)
 static int finish_pass(pg_context *ctx, int slot, const RenderArgs &a, uint8_t *valid_out, float *sumL, float *sumL2, hipStream_t s)
@@ -939,10 +970,13 @@ static int finish_pass(pg_context *ctx, int slot, const RenderArgs &a, uint8_t *
 	if (a.record) {
 		Timed t(r, s, Timer::Splat);
 		// the depth counters of an instrumented pass describe the bounce kernels only
-		pg_list_records lr;
-		lr.ray_of = b.ray_of.p; lr.bsdf = b.r_bsdf.p; lr.throughput_bsdf = b.r_tb.p; lr.throughput_radiance = b.r_tr.p;
-		lr.nee_lum = b.r_nee.p; lr.wo_pdf = b.r_wp.p; lr.slot = b.r_slot.p; lr.tree = b.r_tree.p;
-		launch_splat_list(ctx->view(), ctx->f.accum_view(), ctx->store_nee, a.n_lanes, a.max_depth, a.L, a.Lq, lr, b.live_count.p, s);
+		const pg_list_records lr = list_records(b);
+		// (check_pass: a filter is set only with the geometry beside the list; on the initial tree every filter is the nearest deposit)
+		if (r->scene.geometry && ctx->filtered_launch())
+			launch_splat_list_filtered(ctx->view(), ctx->f.accum_view(), ctx->filter_args(), ctx->store_nee, a.n_lanes, a.max_depth, a.Lq, lr,
+			                           list_geometry(b, a.n_lanes * (uint64_t)a.max_depth), b.live_count.p, ctx->n_cus, s);
+		else
+			launch_splat_list(ctx->view(), ctx->f.accum_view(), ctx->store_nee, a.n_lanes, a.max_depth, a.L, a.Lq, lr, b.live_count.p, s);
 		PG_HIP(ctx, hipGetLastError());
 	}
 	if (r->scene.general >= 2) {
@@ -1018,6 +1052,8 @@ int pg_render_pass(pg_context *ctx, const pg_pass_params *prm, float *L_out, uin
 	// mesh scenes cast_count[2 D] and shadow_count[D] of the persistent ray-casting kernels
 	PG_HIP(ctx, hipMemsetAsync(b.live_count.p, 0, ((size_t)D + 1 + 3 * (size_t)D) * sizeof(uint32_t), s));
 	RenderArgs a = pass_args(ctx, prm, b, P, L_out);
+	b.geo_lanes = r->scene.geometry && a.record ? N : 0; // (what pg_render_export_records may read of this set from now on)
+	b.geo_depth = D;
 	const bool wave = r->scene.general >= 2; // mesh scenes: the split pipeline
 	// sorted bounces (pg_render_sort): from the second bounce (camera rays find neighbouring vertices by themselves) to
 	// the depth at which Russian roulette thins the list out (:375: a sort costs what 33 M pairs cost however few are alive)
@@ -1042,6 +1078,33 @@ int pg_render_split_pipeline(pg_context *ctx, int32_t on)
 {
 	if (!ctx) return PG_ERR_INVALID;
 	rstate(ctx)->split_always = on != 0;
+	return PG_OK;
+}
+
+int pg_render_record_geometry(pg_context *ctx, int32_t on)
+{
+	if (!ctx) return PG_ERR_INVALID;
+	rstate(ctx)->record_geometry = on != 0; // (takes effect at the next pg_scene_set[_ex]: split_pipeline_always)
+	return PG_OK;
+}
+
+int pg_render_export_records(pg_context *ctx, int32_t slot, const pg_records_out *out, uint32_t *slot_out, uint32_t *d_count, void *stream)
+{
+	if (!ctx) return PG_ERR_INVALID;
+	if (!ctx->configured) return fail(ctx, PG_ERR_INVALID, "call pg_setup or pg_import first");
+	if (slot < 0 || slot > 1) return fail(ctx, PG_ERR_INVALID, "pg_render_export_records: slot must be 0 or 1");
+	if (!out || !d_count || !out->position || !out->direction || !out->radiance || !out->wo_pdf || !out->direction_nee ||
+	    !out->radiance_nee_lum)
+		return fail(ctx, PG_ERR_INVALID, "pg_render_export_records: NULL pointer");
+	if (!ctx->render || ctx->render->pb[slot].geo_lanes == 0)
+		return fail(ctx, PG_ERR_INVALID, "pg_render_export_records: the most recent pass of this buffer set recorded no geometry "
+		                                 "(a recording pass of a scene set with pg_render_record_geometry on does)");
+	PG_HIP(ctx, hipSetDevice(ctx->device));
+	const PassBuf &b = ctx->render->pb[slot];
+	const uint64_t N = b.geo_lanes, S = N * (uint64_t)b.geo_depth;
+	launch_export_list_records(N, b.geo_depth, b.Lq.p, list_records(b), list_geometry(b, S), b.live_count.p, *out, slot_out, d_count,
+	                           ctx->n_cus, (hipStream_t)stream);
+	PG_HIP(ctx, hipGetLastError());
 	return PG_OK;
 }
 

@@ -1292,7 +1292,13 @@ __device__ __forceinline__ uint64_t global_pixel(const RenderArgs &a, uint64_t i
 // k_wave_cast (the shadow rays: a persistent kernel sized by n_cus, the compute units of the device), k_wave_guide, k_wave_shade_b,
 // k_wave_tail, or the joint k_wave_shade (pg_render_stages(0)) for ShadeA .. ShadeB; the number of 32-bit planes of its workspace
 enum class WaveStage { Trace, ShadeA, Cast, Guide, ShadeB, Tail, Shade };
-void launch_wave_stage(WaveStage stage, int level, bool first, const RenderArgs &a, unsigned grid_blocks, unsigned n_cus, hipStream_t s);
+// geo (Guide and Tail of a geometry-recording pass, pg_render_record_geometry; nullptr otherwise): kGeoPlanes planes of stride
+// n_lanes * max_depth beside the record list, indexed like it -- the vertex's position, the canonical path and emitter directions
+// (both in the unit square; (0, 0) where the bounce computed none) and the bounce of the entry.  (The bounce: entries a tail
+// launch hands out wave by wave are not in bounce order, so the prefix sums of live_count do not name it.)
+enum : int { GEO_P = 0, GEO_WO = 3, GEO_NEE = 5, GEO_DEPTH = 7, kGeoPlanes = 8 };
+void launch_wave_stage(WaveStage stage, int level, bool first, const RenderArgs &a, unsigned grid_blocks, unsigned n_cus, hipStream_t s,
+                       uint32_t *geo = nullptr);
 constexpr int kCastBlocksPerCU = 8; // upper bound of the resident 256-thread workgroups of a ray-casting kernel per compute unit
 int wave_workspace_planes();
 

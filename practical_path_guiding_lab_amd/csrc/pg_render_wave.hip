@@ -23,6 +23,7 @@
 //                          throughput, Russian roulette, the next ray; survivors are appended to the
 //                          next live list (one atomic per workgroup)
 //   k_wave_tail     all stages in sequence for the last few thousand paths of a long pass (see tail_checkpoint)
+// (k_wave_guide<true>, k_wave_tail<., true>: the same two with the vertex geometry stored beside the list, pg_render_record_geometry)
 //
 // History in one paragraph (DESIGN.md 5.2 has the measurements): round 1's single kernel per bounce needed 153
 // vector registers and kept its BVH stack in scratch memory; rounds 2 and 3 split it into the five kernels above,
@@ -275,6 +276,26 @@ __device__ __forceinline__ void store_slots(const RenderArgs &a, uint64_t rec_sl
 {
 	PG_ST(reinterpret_cast<unsigned long long *>(a.r_slot + rec_slot), (unsigned long long)g.slot_path | ((unsigned long long)g.slot_nee << 32));
 	PG_ST(a.r_tree + rec_slot, g.tree_flags);
+}
+
+// pg_render_record_geometry: a recorded vertex also keeps its position, its two canonical directions and its bounce, in planes
+// of the list's stride beside the list (GEO_*, pg_render_dev.hpp) -- what the training filters and pg_render_export_records
+// need and the accumulators' names cannot give.  Only the geometry instantiations of k_wave_guide and k_wave_tail store them.
+// The position goes out BEFORE the SD-tree calls, so that it is not alive across them; the rest beside store_slots.
+__device__ __forceinline__ void store_geo_position(const RenderArgs &a, uint32_t *geo, uint64_t rec_slot, v3 p)
+{
+	const uint64_t S = a.n_lanes * (uint64_t)a.max_depth;
+	float *gf = reinterpret_cast<float *>(geo);
+	PG_ST(gf + (GEO_P + 0) * S + rec_slot, p.x); PG_ST(gf + (GEO_P + 1) * S + rec_slot, p.y); PG_ST(gf + (GEO_P + 2) * S + rec_slot, p.z);
+}
+__device__ __forceinline__ void store_geo_directions(const RenderArgs &a, uint32_t *geo, uint64_t rec_slot, const GuideOut &g, uint32_t depth)
+{
+	const uint64_t S = a.n_lanes * (uint64_t)a.max_depth;
+	float *gf = reinterpret_cast<float *>(geo);
+	PG_ST(gf + (GEO_WO + 0) * S + rec_slot, g.wo_cx); PG_ST(gf + (GEO_WO + 1) * S + rec_slot, g.wo_cy);
+	// (a vertex whose bounce computed no emitter direction keeps (0, 0): in the square; its nee_lum is zero)
+	PG_ST(gf + (GEO_NEE + 0) * S + rec_slot, g.nee_cx); PG_ST(gf + (GEO_NEE + 1) * S + rec_slot, g.nee_cy);
+	PG_ST(geo + GEO_DEPTH * S + rec_slot, depth);
 }
 
 // ---- :247-261, 302-381; returns whether the path continues, with its state for the next bounce in
@@ -797,7 +818,13 @@ __global__ __launch_bounds__(kRBlock) void k_wave_shade_a(RenderArgs a)
 }
 
 // ---- :244, 301, 307 ----
-__global__ __launch_bounds__(kRBlock) void k_wave_guide(RenderArgs a)
+// kGeo (pg_render_record_geometry): the vertex's geometry goes into geo.planes beside its accumulators (store_geo_position).
+// The switch is a parameter of the KERNEL, and the default instantiation takes an empty second argument: a body shared by two
+// kernels through a wrapper came out of the compiler with other code for the default one (k_wave_tail<2>: other registers).
+template <bool kGeo> struct GeoArg {};
+template <> struct GeoArg<true> { uint32_t *planes; };
+template <bool kGeo = false>
+__global__ __launch_bounds__(kRBlock) void k_wave_guide(RenderArgs a, GeoArg<kGeo> geo)
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
 	uint64_t tid;
@@ -825,8 +852,14 @@ __global__ __launch_bounds__(kRBlock) void k_wave_guide(RenderArgs a)
 	GuideOut g;
 	// (the BSDF-sampled direction of a lane that keeps it; a lane that samples the tree has none to evaluate)
 	const v3 wo_in = (flags & F_SMP_TREE) ? V(0, 0, 0) : u_in;
+	if constexpr (kGeo) {
+		if (a.record && (flags & F_VALID)) store_geo_position(a, geo.planes, (a.bounce > 0 ? records_before(a) : 0) + tid, p_in);
+	}
 	stage_guide(a, s_planes, rng, p_in, ds_in, wo_in, flags, g);
 	if (a.record && (flags & F_VALID)) store_slots(a, (a.bounce > 0 ? records_before(a) : 0) + tid, g); // the entry k_wave_shade_b fills for this vertex
+	if constexpr (kGeo) {
+		if (a.record && (flags & F_VALID)) store_geo_directions(a, geo.planes, (a.bounce > 0 ? records_before(a) : 0) + tid, g, (uint32_t)a.bounce);
+	}
 	wsput(a, WS_PDF_NEE, tid, g.pdf_nee); wsput(a, WS_PDF_TREE, tid, g.pdf_tree);
 	if (flags & F_SMP_TREE) {
 		wsput3(a, WS_WO_T, tid, g.wo);
@@ -1260,8 +1293,9 @@ __global__ __launch_bounds__(kRBlock) __attribute__((amdgpu_waves_per_eu(5))) vo
 // goes through the per-lane arrays only at the start.  Record entries of the later bounces are handed
 // out wave by wave behind the entries of bounce a.bounce (a.live_count[max_depth] counts them), and
 // the survivors of every bounce are added to live_count[] as the per-bounce launches would have.
-template <int kLevel>
-__global__ __launch_bounds__(kRBlock) void k_wave_tail(RenderArgs a)
+// kGeo (pg_render_record_geometry): as k_wave_guide's
+template <int kLevel, bool kGeo = false>
+__global__ __launch_bounds__(kRBlock) void k_wave_tail(RenderArgs a, GeoArg<kGeo> geo)
 {
 	__shared__ uint2 s_stack[kLdsStack][kRBlock];
 	__shared__ float s_planes[3 * kKdGridPlanes];
@@ -1314,8 +1348,14 @@ __global__ __launch_bounds__(kRBlock) void k_wave_tail(RenderArgs a)
 				occluded = intersect<kLevel, true>(a.shapes, A.sh_o, A.sh_d, A.sh_tmax, th, stk, bu, bv) >= 0;
 			}
 			GuideOut g = guide_none(A.wo);
+			if constexpr (kGeo) {
+				if (a.record && (A.flags & F_VALID)) store_geo_position(a, geo.planes, slot, A.p);
+			}
 			if (guide_has_work(a, A.flags)) stage_guide(a, s_planes, rng, A.p, A.ds_d, A.wo, A.flags, g);
 			if (a.record && (A.flags & F_VALID)) store_slots(a, slot, g);
+			if constexpr (kGeo) {
+				if (a.record && (A.flags & F_VALID)) store_geo_directions(a, geo.planes, slot, g, (uint32_t)depth);
+			}
 			bool delta;
 			alive = stage_b<kLevel>(a, rng, thr, L, ior, A, g, occluded, lane, slot, (uint32_t)depth, ray_o, ray_d, prev_pdf, delta);
 			prev_p = A.p;
@@ -1344,7 +1384,7 @@ static dim3 persistent_grid(K kernel, unsigned &cached_per_cu, unsigned n_cus, u
 
 // ---- launcher: one stage of one bounce (pg_render_pass wraps each in its timing events) ----
 template <int kLevel>
-static void launch_stage_level(WaveStage stage, bool first, const RenderArgs &a, dim3 grid, unsigned n_cus, hipStream_t s)
+static void launch_stage_level(WaveStage stage, bool first, const RenderArgs &a, dim3 grid, unsigned n_cus, hipStream_t s, uint32_t *geo)
 {
 	const dim3 block(kRBlock);
 	static unsigned occ[2] = {0, 0}; // resident workgroups per CU of the two shadow-ray instantiations of this level
@@ -1359,13 +1399,19 @@ static void launch_stage_level(WaveStage stage, bool first, const RenderArgs &a,
 	case WaveStage::Cast:
 		PG_BY_FIRST(hipLaunchKernelGGL((k_wave_cast<kLevel, kF>), persistent_grid(k_wave_cast<kLevel, kF>, occ[kF ? 0 : 1], n_cus, a.n_lanes), block, 0, s, a));
 		break;
-	case WaveStage::Guide: hipLaunchKernelGGL(k_wave_guide, grid, block, 0, s, a); break;
+	case WaveStage::Guide: // (geo: a geometry-recording pass, pg_render_record_geometry -- its Guide and Tail launches only)
+		if (geo) hipLaunchKernelGGL(k_wave_guide<true>, grid, block, 0, s, a, GeoArg<true>{geo});
+		else hipLaunchKernelGGL(k_wave_guide<false>, grid, block, 0, s, a, GeoArg<false>{});
+		break;
 	case WaveStage::ShadeB: {
 		const size_t lds = a.carry_out ? (size_t)kRBlock * PS_ENTRIES * sizeof(uint4) : 0; // (the survivors' records of a sorted next bounce)
 		PG_BY_FIRST(hipLaunchKernelGGL((k_wave_shade_b<kLevel, kF>), grid, block, lds, s, a));
 		break;
 	}
-	case WaveStage::Tail: hipLaunchKernelGGL((k_wave_tail<kLevel>), grid, block, 0, s, a); break;
+	case WaveStage::Tail:
+		if (geo) hipLaunchKernelGGL((k_wave_tail<kLevel, true>), grid, block, 0, s, a, GeoArg<true>{geo});
+		else hipLaunchKernelGGL((k_wave_tail<kLevel, false>), grid, block, 0, s, a, GeoArg<false>{});
+		break;
 	case WaveStage::Shade: {
 		const size_t lds = (size_t)kShadeLdsQuads * sizeof(uint4);
 		if constexpr (kLevel == 3) PG_BY_FIRST(hipLaunchKernelGGL((k_wave_shade_l3<kF>), grid, block, lds, s, a));
@@ -1376,10 +1422,11 @@ static void launch_stage_level(WaveStage stage, bool first, const RenderArgs &a,
 #undef PG_BY_FIRST
 }
 
-void launch_wave_stage(WaveStage stage, int level, bool first, const RenderArgs &a, unsigned grid_blocks, unsigned n_cus, hipStream_t s)
+void launch_wave_stage(WaveStage stage, int level, bool first, const RenderArgs &a, unsigned grid_blocks, unsigned n_cus, hipStream_t s,
+                       uint32_t *geo)
 {
-	if (level >= 3) launch_stage_level<3>(stage, first, a, dim3(grid_blocks), n_cus, s);
-	else launch_stage_level<2>(stage, first, a, dim3(grid_blocks), n_cus, s);
+	if (level >= 3) launch_stage_level<3>(stage, first, a, dim3(grid_blocks), n_cus, s, geo);
+	else launch_stage_level<2>(stage, first, a, dim3(grid_blocks), n_cus, s, geo);
 }
 
 int wave_workspace_planes() { return WS_COUNT; }

@@ -205,7 +205,8 @@ int pg_scene_set_ex(pg_context *ctx, const pg_scene_desc *sc, const pg_camera *c
 	s.n_bvh_nodes = (int)sc->n_bvh_nodes; s.n_emitters = (int)h.emitters.size();
 	s.have_tri_normals = h.tri_normals; s.have_tri_uvs = h.tri_uvs;
 	for (int c = 0; c < 4; ++c) s.bsphere[c] = sc->bsphere[c];
-	s.general = split_pipeline_always(ctx) && h.general < 2 ? 2 : h.general; // pg_render_split_pipeline
+	s.geometry = record_geometry_wanted(ctx); // pg_render_record_geometry: implies the split pipeline
+	s.general = (split_pipeline_always(ctx) || s.geometry) && h.general < 2 ? 2 : h.general; // pg_render_split_pipeline
 	s.cam = *cam;
 	s.have_scene = true;
 	return PG_OK;

@@ -19,11 +19,14 @@ struct SceneState {
 	float bsphere[4] = {0, 0, 0, 0};
 	int n_quads = 0, n_spheres = 0, n_emitters = 0, n_boxes = 0, n_bvh_nodes = 0;
 	int general = 0; // feature level of the kernels to launch (0 cornell-box class, 1 veach-mis class, 2 meshes, 3 everything)
+	bool geometry = false; // pg_render_record_geometry was on when the scene was set: recording passes keep the vertices' geometry
 	pg_camera cam;
 };
 
-// pg_render.hip: the scene of the context's renderer state (made on first use), and its pg_render_split_pipeline switch
+// pg_render.hip: the scene of the context's renderer state (made on first use), and its pg_render_split_pipeline and
+// pg_render_record_geometry switches
 SceneState &scene_state(pg_context *ctx);
 bool split_pipeline_always(pg_context *ctx);
+bool record_geometry_wanted(pg_context *ctx);
 
 } // namespace pg

@@ -95,8 +95,13 @@ def run_guided_render(scene: WavefrontScene, integrator: PathGuidingIntegrator, 
                       record_in_iteration: bool = False, out_dir: Optional[str] = None,
                       all_reduce: Optional[Callable[[torch.Tensor], None]] = None,
                       log: Callable[[str], None] = print, shard=None, gt_mask=None,
-                      training_passes_per_launch: int = 1, exchange_overlap: Optional[bool] = None) -> Dict:
+                      training_passes_per_launch: int = 1, exchange_overlap: Optional[bool] = None,
+                      splat_filter=None) -> Dict:
     """Runs the whole training + rendering schedule; returns the final image, logs and timings.
+
+    splat_filter = (spatial, directional[, seed]) (not in the reference): the recording passes deposit through the training
+    filters (PathGuidingIntegrator.setSplatFilter); anything but nearest / nearest needs a WavefrontScene(record_geometry=True).
+    None: the integrator is left as it is.
 
     training_passes_per_launch = B > 1 (with training_spp_per_pass = 1, the reference's value): B consecutive training
     passes are traced as ONE device pass (pg_pass_params.batched: sample s of the launch is the sample pass seed + s gives
@@ -116,6 +121,10 @@ def run_guided_render(scene: WavefrontScene, integrator: PathGuidingIntegrator, 
     variance / MSE / the stop decision are taken on the whole film's sums -- every rank ends with the
     image, the tree and the logs a single rank produces."""
     w, h = scene.film_size
+    if splat_filter is not None:
+        integrator.setSplatFilter(*splat_filter)
+        if tuple(splat_filter[:2]) != ("nearest", "nearest") and not getattr(scene, "record_geometry", False):
+            raise ValueError(f"splat_filter {splat_filter[0]},{splat_filter[1]} needs a WavefrontScene(..., record_geometry=True)")
     gather = sums_of = None
     if shard is not None and shard[1] > 1:
         from .parallel import HaloExchange, LaneGather, all_reduce_accumulators, all_reduce_sums

@@ -58,6 +58,18 @@ class PathGuidingIntegrator:
         self._exchange_stream = None
         self._exchange_pending = False
         self._exchange_done = False
+        self.splat_filter = None  # setSplatFilter: (spatial, directional, seed), or None -- the tree's filter is left alone
+
+    def setSplatFilter(self, spatial: str = "nearest", directional: str = "nearest", seed: int = 0) -> None:
+        """Not in the reference: the training filters (SDTree.setSplatFilter) for the recording passes of sample().  The
+        choice is kept here and set before every recording pass with the seed (seed + the pass's sampler seed) mod 2^32
+        (WavefrontScene.trace_pass), so that two passes do not jitter alike; a filter other than nearest / nearest needs
+        a WavefrontScene(record_geometry=True), else sample() raises."""
+        if spatial not in SDTree._SPATIAL:
+            raise ValueError(f"spatial filter must be one of {sorted(SDTree._SPATIAL)}, got {spatial!r}")
+        if directional not in SDTree._DIRECTIONAL:
+            raise ValueError(f"directional filter must be one of {sorted(SDTree._DIRECTIONAL)}, got {directional!r}")
+        self.splat_filter = (spatial, directional, int(seed))
 
     # ---- path_guiding_integrator.py:77-105 ---------------------------------------------------
     def _join(self) -> None:

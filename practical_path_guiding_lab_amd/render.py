@@ -45,16 +45,26 @@ class IndependentSampler:
         return self._seed
 
 
+def pass_filter_seed(filter_seed: int, sampler_seed: int) -> int:
+    """The seed pg_set_splat_filter gets for a recording pass: (the integrator's filter seed + the pass's sampler seed) mod 2^32
+    -- the jitter's record numbers are per launch, so passes of one seed would jitter the same slots alike."""
+    return (int(filter_seed) + int(sampler_seed)) & 0xFFFFFFFF
+
+
 class WavefrontScene:
     """Device-resident scene (quads + camera) implementing the `trace_pass` protocol of
     PathGuidingIntegrator.sample()."""
 
     def __init__(self, scene: Scene, split_pipeline: bool = False, overlap: int = 0, in_flight: int = 1, sort: bool = True,
-                 stages: int = 0):
+                 stages: int = 0, record_geometry: bool = False):
         """split_pipeline: run the bounce as the split pipeline also for a scene the fused kernel could
-        run (pg_render_split_pipeline: same results, the SD-tree queries as a kernel of their own)."""
+        run (pg_render_split_pipeline: same results, the SD-tree queries as a kernel of their own).
+        record_geometry: recording passes keep every path vertex's position and directions beside their record list
+        (pg_render_record_geometry; implies the split pipeline, and the four-kernel form of a bounce in those passes):
+        what PathGuidingIntegrator.setSplatFilter and SDTree.exportPassRecords need.  Same results at nearest / nearest."""
         self.scene = scene
         self.split_pipeline = bool(split_pipeline)
+        self.record_geometry = bool(record_geometry)
         self.overlap = int(overlap)  # pg_render_overlap: independent kernels of a pass side by side (same results)
         # pg_render_sort: the live list of a mesh scene's bounce in a global spatial order (same results, +10 % on
         # veach-ajar; the fused kernels of quad scenes ignore it)
@@ -125,6 +135,7 @@ class WavefrontScene:
             d.n_texels, d.texels = txl.shape[0], (txl.ctypes.data if txl.size else None)
             d.srgb_lut = lut.ctypes.data
         N.check(tree._h, tree._lib.pg_render_split_pipeline(tree._h, 1 if self.split_pipeline else 0))
+        N.check(tree._h, tree._lib.pg_render_record_geometry(tree._h, 1 if self.record_geometry else 0))
         N.check(tree._h, tree._lib.pg_render_overlap(tree._h, self.overlap))
         N.check(tree._h, tree._lib.pg_render_sort(tree._h, 1 if self.sort else 0))
         N.check(tree._h, tree._lib.pg_render_stages(tree._h, self.stages))
@@ -206,6 +217,14 @@ class WavefrontScene:
             # k_finish indexes the sums by film pixel: setup(numRays) must have been given the film size
             raise ValueError(f"integrator.setup(numRays={integrator.sumL.shape[1]}) does not match the film "
                              f"{cam.width}x{cam.height}: call setup again for this scene")
+        # PathGuidingIntegrator.setSplatFilter: the filter of this pass, with a seed of its own (two passes must not jitter alike)
+        splat_filter = getattr(integrator, "splat_filter", None)
+        filtered = splat_filter is not None and tuple(splat_filter[:2]) != ("nearest", "nearest")
+        if filtered and not self.record_geometry:
+            raise ValueError(f"the integrator's splat filter {splat_filter[0]},{splat_filter[1]} needs the path vertices' geometry: "
+                             "build the scene with WavefrontScene(..., record_geometry=True)")
+        if splat_filter is not None and not integrator.isFinalIter:
+            tree.setSplatFilter(splat_filter[0], splat_filter[1], pass_filter_seed(splat_filter[2], sampler.seed_value))
         slot, stream = 0, torch.cuda.current_stream()
         if self.in_flight == 2 and n:
             if self._streams is None:
@@ -233,6 +252,7 @@ class WavefrontScene:
             sl2 = integrator.sumL2.data_ptr() if accumulate else None
             N.check(tree._h, tree._lib.pg_render_pass(tree._h, C.byref(p), L.data_ptr(), valid.data_ptr(), sl, sl2,
                                                       stream.cuda_stream))
+            tree._pass_lanes[slot] = n  # (SDTree.exportPassRecords sizes its columns by it)
         if stream is not torch.cuda.current_stream():
             # (the tensors were allocated on the pass's stream and will be read on the current one after join())
             L.record_stream(torch.cuda.current_stream())

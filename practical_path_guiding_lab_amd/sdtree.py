@@ -69,6 +69,8 @@ class SDTree:
         N.check(None, self._lib.pg_create(C.byref(h), device))
         self._h = h
         self.store_nee = True
+        self._max_depth = 0
+        self._pass_lanes = {}  # buffer set -> lanes of its most recent render pass (WavefrontScene.trace_pass; exportPassRecords)
 
     def __del__(self):
         try:
@@ -89,6 +91,7 @@ class SDTree:
         bmin = (C.c_float * 3)(*[float(v) for v in bbox_min])
         bmax = (C.c_float * 3)(*[float(v) for v in bbox_max])
         self.store_nee = bool(isStoreNEERadiance)
+        self._max_depth = int(max_depth)
         self._ck(self._lib.pg_setup(self._h, bmin, bmax, int(numRays), int(max_depth), int(sdTreeMaxDepth),
                                     int(quadTreeMaxDepth), int(self.store_nee), float(bsdfSamplingFraction)))
 
@@ -103,7 +106,9 @@ class SDTree:
         "stochastic" (the position is jittered by the extent of its KD leaf), directional "nearest" | "box" (the energy is
         shared between the quadtree leaves a leaf-sized square around the direction overlaps).  addDataPropagate,
         processAndSplat and prepareProcessAndSplat follow it; setup() resets it to nearest / nearest.  While a filter is
-        set, a recording render pass raises (the renderer's record list cannot be filtered)."""
+        set, a recording render pass raises (the renderer's record list cannot be filtered) unless the scene records the
+        vertices' geometry (WavefrontScene(record_geometry=True)): then the pass deposits through the filters, and the
+        jitter's record number is the dense slot ray * max_depth + depth."""
         if spatial not in self._SPATIAL:
             raise ValueError(f"spatial filter must be one of {sorted(self._SPATIAL)}, got {spatial!r}")
         if directional not in self._DIRECTIONAL:
@@ -228,6 +233,34 @@ class SDTree:
                 raise ValueError("count must be a CUDA int32 tensor")
             cp = count.data_ptr()
         self._ck(self._lib.pg_splat(self._h, m, C.byref(r), cp, _stream_ptr()))
+
+    def exportPassRecords(self, slot: int = 0) -> Dict[str, torch.Tensor]:
+        """The kept path-vertex records of the most recent render pass of buffer set `slot` (pg_render_export_records): a
+        recording pass of a WavefrontScene(record_geometry=True); anything else raises.  Returns the columns addDataPropagate
+        takes (plane stride n_lanes * max_depth of that pass, the records in any order) plus "slot" (int32, the bits of a
+        uint32: the dense slot ray * max_depth + depth of every record) and "count" (int32[1], the number of records): addDataPropagate(rec, rec["count"]) on a tree of the same topology reproduces the pass's own
+        accumulators.  Reads the pass's buffers on the current stream: with in_flight = 2 call scene.join() first; valid
+        until the next pass of that buffer set."""
+        S = int(self._pass_lanes.get(int(slot), 0)) * self._max_depth
+        out = {
+            "position": torch.empty((3, S), dtype=torch.float32, device=self.device),
+            "direction": torch.empty((2, S), dtype=torch.float32, device=self.device),
+            "radiance": torch.empty(S, dtype=torch.float32, device=self.device),
+            "woPdf": torch.empty(S, dtype=torch.float32, device=self.device),
+            "direction_nee": torch.empty((2, S), dtype=torch.float32, device=self.device),
+            "radiance_nee_lum": torch.empty(S, dtype=torch.float32, device=self.device),
+            "slot": torch.empty(S, dtype=torch.int32, device=self.device),
+            "count": torch.zeros(1, dtype=torch.int32, device=self.device),
+        }
+        o = N.pg_records_out()
+        # (never NULL, also for S = 0: the library then refuses because no pass recorded geometry, not because of a pointer)
+        ptr = lambda t: t.data_ptr() or out["count"].data_ptr()  # noqa: E731
+        o.position = ptr(out["position"]); o.direction = ptr(out["direction"])
+        o.radiance = ptr(out["radiance"]); o.wo_pdf = ptr(out["woPdf"])
+        o.direction_nee = ptr(out["direction_nee"]); o.radiance_nee_lum = ptr(out["radiance_nee_lum"])
+        self._ck(self._lib.pg_render_export_records(self._h, int(slot), C.byref(o), out["slot"].data_ptr() or None,
+                                                    out["count"].data_ptr(), _stream_ptr()))
+        return out
 
     def _dense(self, rec: Dict[str, torch.Tensor], S: int) -> N.pg_dense_records:
         d = N.pg_dense_records()

@@ -1,0 +1,71 @@
+"""Host side of the filters in recording render passes (no GPU): the two new exports, main.py's --splat-filter, the arithmetic
+of the per-pass filter seed, and the Python layer's bookkeeping of the choice."""
+import ctypes
+import os
+import re
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def test_the_library_exports_58_symbols_with_the_two_new_ones():
+    """(58, not the 57 the plan for this change counted on: the header declared 56 entry points before it -- pg_set_splat_filter had
+    been added without DESIGN.md's "55 exports" being moved -- and this change adds two.)"""
+    from practical_path_guiding_lab_amd import _native
+
+    if not os.path.exists(_native.LIB_PATH):
+        _native.build()
+    hdr = open(os.path.join(ROOT, "include", "pgsd.h")).read()
+    declared = set(re.findall(r"^(?:int|const char \*)\s*(pg_[a-z_0-9]+)\s*\(", hdr, flags=re.M))
+    assert len(declared) == len(_native.EXPORTS) == 58 and declared == set(_native.EXPORTS)
+    assert {"pg_render_record_geometry", "pg_render_export_records"} <= declared
+    L = _native.lib()
+    assert L.pg_abi_version() == _native.ABI_VERSION == 6      # added entry points: the number stays
+    assert L.pg_render_record_geometry.argtypes == [ctypes.c_void_p, ctypes.c_int32]
+    assert len(L.pg_render_export_records.argtypes) == 6
+    # a NULL context is refused before anything touches a device
+    assert L.pg_render_record_geometry(None, 1) == -1
+    assert L.pg_render_export_records(None, 0, None, None, None, None) == -1
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    assert "58 exports" in design and "55 exports" not in design
+
+
+def test_main_parses_the_splat_filter():
+    import main
+
+    ap = main.build_parser()
+    assert ap.parse_args([]).splat_filter == ("nearest", "nearest")
+    assert ap.parse_args(["--splat-filter", "stochastic,box"]).splat_filter == ("stochastic", "box")
+    assert ap.parse_args(["--splat-filter", " nearest , box "]).splat_filter == ("nearest", "box")
+    for bad in ("box,nearest", "stochastic", "stochastic,box,1", "gaussian,box", "stochastic,tent", ""):
+        with pytest.raises(SystemExit):
+            ap.parse_args(["--splat-filter", bad])
+    # the default builds the scene exactly as before the option existed: no keyword at all, no geometry recording
+    assert main.scene_options(("nearest", "nearest")) == {}
+    for f in (("stochastic", "nearest"), ("nearest", "box"), ("stochastic", "box")):
+        assert main.scene_options(f) == {"record_geometry": True}
+
+
+def test_scene_and_integrator_keep_the_choice():
+    from practical_path_guiding_lab_amd.render import WavefrontScene
+    from practical_path_guiding_lab_amd.scene import cornell_box
+
+    sc = cornell_box(8, 8, 4, 8)
+    assert WavefrontScene(sc).record_geometry is False and WavefrontScene(sc).split_pipeline is False
+    assert WavefrontScene(sc, record_geometry=True).record_geometry is True
+
+
+def test_per_pass_filter_seed_arithmetic():
+    from practical_path_guiding_lab_amd.render import pass_filter_seed
+
+    assert pass_filter_seed(0, 0) == 0
+    assert pass_filter_seed(11, 4242) == 4253
+    assert pass_filter_seed(0xFFFFFFFF, 1) == 0                      # modulo 2^32
+    assert pass_filter_seed(0xFFFFFFF0, 0x20) == 0x10
+    assert pass_filter_seed(3, (1 << 32) + 5) == 8                   # a sampler seed beyond 32 bits counts by its low word
+    assert pass_filter_seed(7, 100) != pass_filter_seed(7, 101)      # two passes of an iteration do not jitter alike
+    assert all(0 <= pass_filter_seed(a, b) < (1 << 32) for a in (0, 1, 0xFFFFFFFF) for b in (0, 0xFFFFFFFF, 1 << 40))
