@@ -502,7 +502,9 @@ int pg_render_overlap(pg_context *ctx, int32_t mode);
 int pg_render_stages(pg_context *ctx, int32_t mode);
 
 /* Not in the reference (Dr.Jit's wavefront keeps pixel order): with `on`, the bounces of a mesh scene from the second one
- * up to rr_depth process the live list in a global spatial order -- the places sorted by the Morton cell of the vertex
+ * (bounce 1) to bounce min(rr_depth, max_depth - 1) inclusive -- the bounce at whose end Russian roulette first thins the list
+ * out still shades every path that reached it -- process the live list in a global spatial order, those of them that enough
+ * lanes reached in the buffer set's previous pass: the places sorted by the Morton cell of the vertex
  * the ray has just found (a device radix sort of 16-bit keys per bounce) -- so that the lanes of a wave stand next to
  * each other in the scene for the shading, the shadow rays, the SD-tree queries and, after the survivors are appended
  * in that order, the next bounce's closest hits.  A lane's result depends on its own state only: radiance, sums,

@@ -603,7 +603,10 @@ struct PassBuf {
 	                        // k_wave_shade reads the records of its bounce and writes the next bounce's in one launch
 	// which bounces are worth a sort is read off the PREVIOUS pass of this set: its live counts come back to the host
 	// behind the pass (pinned memory, an event), and a bounce is sorted when at least kSortMinLive of the lanes were alive
-	// going into it -- a sort costs what N pairs cost however few are left (scenes/torus: 24 % after the second bounce)
+	// going into it (scenes/torus: 24 % after the second bounce).  The sort itself covers n_sort places, a little more than
+	// were alive then (wave_bounce), so its cost follows the live count; what a thin sorted bounce still pays whatever is
+	// left are the sort's eight launches, the 65536 places of slack, and N-sized grids that find their lanes through the
+	// permutation and their state in 128-byte records instead of planes
 	uint32_t *h_live = nullptr;       // pinned, max_depth entries
 	int h_live_n = 0;
 	hipEvent_t ev_live = nullptr;
@@ -854,8 +857,9 @@ static void quad_bounce(pg_render_state *r, const RenderArgs &a, int it, hipStre
 	}
 }
 
-// pg_render_sort: is bounce `bounce` of a pass of N lanes in set b sorted?  Those from the second one to sort_until, when enough
-// lanes were alive going into it in the set's last pass (the choice changes no result: without counts every one is sorted)
+// pg_render_sort: is bounce `bounce` of a pass of N lanes in set b sorted?  Those from the second one (bounce 1) to the last one
+// below sort_until, when enough lanes were alive going into it in the set's last pass (the choice changes no result: without
+// counts every one of them is sorted)
 static bool worth_sorting(const PassBuf &b, int bounce, int sort_until, uint64_t N)
 {
 	if (bounce < 1 || bounce >= sort_until) return false;
@@ -1056,8 +1060,10 @@ int pg_render_pass(pg_context *ctx, const pg_pass_params *prm, float *L_out, uin
 	b.geo_depth = D;
 	const bool wave = r->scene.general >= 2; // mesh scenes: the split pipeline
 	// sorted bounces (pg_render_sort): from the second bounce (camera rays find neighbouring vertices by themselves) to
-	// the depth at which Russian roulette thins the list out (:375: a sort costs what 33 M pairs cost however few are alive)
-	const int sort_until = wave && r->sort ? (prm->rr_depth < D ? prm->rr_depth : D) : 0;
+	// the bounce at whose end Russian roulette thins the list out, that one included: bounce rr_depth still shades every path
+	// that came through bounce rr_depth - 1 and rolls the dice only behind that (stage_b).  So bounces 1 .. min(rr_depth,
+	// D - 1) are candidates, and worth_sorting drops those of them that few lanes reach.
+	const int sort_until = wave && r->sort ? (prm->rr_depth < D ? prm->rr_depth + 1 : D) : 0;
 	if (sort_until > 1) take_live_counts(b, N, D);
 	for (int it = 0; it < D; ++it) {
 		a.bounce = it;
