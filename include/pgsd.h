@@ -611,6 +611,22 @@ int pg_math_eval(pg_context *ctx, int32_t which, uint64_t n, const float *x, flo
  * d_places_out behind `live` are not written.  d_keys: uint16[n], d_places_out: uint32[n], device pointers.  Synchronises. */
 int pg_sort_places(pg_context *ctx, uint64_t n, const uint16_t *d_keys, const uint32_t *d_live, uint32_t *d_places_out, void *stream);
 
+/* The renderer's ray casting by itself, for tests: ray i = (d_origin[3 i ..], d_dir[3 i ..]) is cast against the scene set on
+ * the context, through the very device functions the render kernels call, at the scene's feature level, for hits with
+ * 0 < t < d_tmax[i] (strictly; +inf: no limit).  d_t[i] becomes the distance of the closest hit (d_tmax[i] itself where there is
+ * none), d_prim[i] its shape number (quads, spheres, 6 box faces per box, triangles in BVH leaf order; -1: no hit) and
+ * d_uv[2 i], d_uv[2 i + 1] the barycentrics of a triangle hit (0 for every other shape and for a miss).
+ * any_hit != 0: the shadow rays' walk, which stops at the first occluder it meets -- d_prim[i] >= 0 exactly where the closest-hit
+ * walk finds something; WHICH occluder, its t and its uv are not specified beyond that.
+ * walk_form: how the BVH walk is laid out (the results do not depend on it) -- 0: as in the ray-casting kernels (8 stack
+ * entries per lane and the first 48 nodes in LDS), 1: as in k_wave_shade (6 entries, 40 nodes, the register-saving walk),
+ * 2: no nodes in LDS.  Deeper stack entries go to overflow strips the call allocates and frees itself.
+ * d_origin, d_dir: float[3 n]; d_tmax, d_t: float[n]; d_prim: int32[n]; d_uv: float[2 n]; device pointers, none NULL.
+ * n = 0 does nothing; n > 2^20 is refused, as are a context without a scene and a walk_form outside 0..2.  Any float input
+ * (NaN, infinities, the zero direction) is safe: the walk is bounded by a step budget.  Synchronises the stream. */
+int pg_scene_intersect(pg_context *ctx, uint64_t n, const float *d_origin, const float *d_dir, const float *d_tmax,
+                       int32_t any_hit, int32_t walk_form, float *d_t, int32_t *d_prim, float *d_uv, void *stream);
+
 /* Per-kernel device time of pg_render_pass, measured with HIP events recorded on the launch
  * stream around each kernel (off by default).  pg_read_kernel_timing synchronises. */
 typedef struct pg_kernel_timing {

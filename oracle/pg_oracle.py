@@ -557,6 +557,25 @@ def texture_eval(scene_obj, index: int, u: float, v: float):
     return out
 
 
+def intersect(scene_obj, o, d, tmax=None):
+    """The oracle's ray casting by itself (pgo_intersect): o, d (n,3) float32, tmax (n,) float32 or None (no limit) ->
+    (t (n,) float32, prim (n,) int32, u (n,), v (n,) float32, waiting (n,) int32: the walk's greatest stack height)."""
+    lb = lib()
+    lb.pgo_intersect.argtypes = [C.POINTER(_Scene), C.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P]
+    lb.pgo_intersect.restype = None
+    sc, keep = _scene_struct(scene_obj, None, None, None, None)
+    o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+    n = o.shape[0]
+    assert d.shape[0] == n
+    tm = np.full(n, np.inf, np.float32) if tmax is None else np.ascontiguousarray(tmax, np.float32).reshape(n)
+    t, u, v = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+    prim, waiting = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    lb.pgo_intersect(C.byref(sc), n, _ptr(o), _ptr(d), _ptr(tm), _ptr(t), _ptr(prim), _ptr(u), _ptr(v), _ptr(waiting))
+    del keep
+    return t, prim, u, v, waiting
+
+
 def render_pass(pair: "OracleSDTreePair", quads, cam, max_depth, rr_depth, iteration, is_final, seed, spp=1,
                 store_nee=True, bsdf_sampling_fraction=0.5, sumL=None, sumL2=None, spheres=None, materials=None,
                 boxes=None):

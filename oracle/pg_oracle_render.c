@@ -106,9 +106,12 @@ static int bvh_box_hit(const uint32_t *N, int c, const float oo[3], const float 
 }
 
 /* closest hit over all shapes: 0 < t < tmax; returns the shape number (quads, spheres, box faces,
- * triangles) */
-static int intersect(const pgo_scene *sc, v3 o, v3 d, float tmax, float *t_out)
+ * triangles).  *u_out, *v_out: the barycentrics of a triangle hit (0 otherwise); *waiting_out: the most
+ * entries that waited on the BVH walk's stack at once (pgo_intersect reports them; they enter nothing). */
+static int intersect_ex(const pgo_scene *sc, v3 o, v3 d, float tmax, float *t_out, float *u_out, float *v_out, int *waiting_out)
 {
+	float bu = 0.0f, bv = 0.0f;
+	int waiting = 0;
 	const size_t nq = sc->n_quads;
 	const float *quads = sc->quads;
 	int best = -1;
@@ -207,6 +210,7 @@ static int intersect(const pgo_scene *sc, v3 o, v3 d, float tmax, float *t_out)
 #undef PGO_CSWAP
 				for (int c = 3; c >= 1; --c)
 					if (r[c] != NONE) { st_ref[sp] = r[c]; st_t[sp] = t[c]; ++sp; }
+				if (sp > waiting) waiting = sp;
 				next = r[0];
 				continue;
 			}
@@ -227,13 +231,32 @@ static int intersect(const pgo_scene *sc, v3 o, v3 d, float tmax, float *t_out)
 					const float v = dot3(d, q) * inv_det;
 					if (!(v >= 0.0f && u + v <= 1.0f)) continue;
 					const float t = dot3(e2, q) * inv_det;
-					if (t > 0.0f && t < bt) { bt = t; best = (int)(tri_base + i); }
+					if (t > 0.0f && t < bt) { bt = t; best = (int)(tri_base + i); bu = u; bv = v; }
 				}
 			}
 		}
 	}
 	*t_out = bt;
+	*u_out = bu; *v_out = bv;
+	*waiting_out = waiting;
 	return best;
+}
+
+static int intersect(const pgo_scene *sc, v3 o, v3 d, float tmax, float *t_out)
+{
+	float u, v;
+	int waiting;
+	return intersect_ex(sc, o, d, tmax, t_out, &u, &v, &waiting);
+}
+
+void pgo_intersect(const pgo_scene *sc, size_t n, const float *origin, const float *dir, const float *tmax, float *t_out,
+                   int32_t *prim_out, float *u_out, float *v_out, int32_t *waiting_out)
+{
+	for (size_t i = 0; i < n; ++i) {
+		int waiting;
+		prim_out[i] = intersect_ex(sc, ld3(origin + 3 * i), ld3(dir + 3 * i), tmax[i], &t_out[i], &u_out[i], &v_out[i], &waiting);
+		waiting_out[i] = waiting;
+	}
 }
 
 /* outward unit normal of box face `face` (2 axis + negative) */

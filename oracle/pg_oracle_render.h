@@ -123,6 +123,13 @@ void pgo_render_pass_scene(const pgo_tree *prev, pgo_tree *current, const pgo_sc
                            const pgo_camera *cam, const pgo_render_params *prm, float *L_out,
                            uint8_t *valid_out, float *sumL, float *sumL2);
 
+/* The ray casting of the render pass by itself: ray i = (origin[3 i ..], dir[3 i ..]), hits with 0 < t < tmax[i].
+ * t_out[i]: the closest hit's distance (tmax[i] where there is none); prim_out[i]: its shape number (quads, spheres, 6 faces
+ * per box, triangles in leaf order; -1: none); u_out, v_out: the barycentrics of a triangle hit (0 otherwise); waiting_out[i]:
+ * the most entries that waited on the BVH walk's stack at once during that ray's walk. */
+void pgo_intersect(const pgo_scene *scene, size_t n, const float *origin, const float *dir, const float *tmax, float *t_out,
+                   int32_t *prim_out, float *u_out, float *v_out, int32_t *waiting_out);
+
 /* Texture `index` of the scene at (u, v): the reflectance a textured material takes there. */
 void pgo_texture_eval(const pgo_scene *scene, int index, float u, float v, float rgb[3]);
 

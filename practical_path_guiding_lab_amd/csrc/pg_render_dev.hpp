@@ -1184,6 +1184,43 @@ struct RenderArgs {
 };
 
 
+// The first nodes of the BVH in LDS (bvh_node_step): every thread of the workgroup calls this.  How many: what the LDS
+// leaves beside the walks' stacks at seven workgroups per compute unit (16 KB of stack + 6 KB of nodes each).  Measured on
+// veach-ajar, ms per step: closest hits 12.7 / 11.8 / 11.6 with 16 / 32 / 48 nodes (15.1 with none); shadow rays 6.9 /
+// 6.6 / 6.6 with 32 / 64 / 80 at six waves per SIMD (7.9 with none), 6.5 / 6.4 with 32 / 48 at seven.
+constexpr int kBvhTopNodes = 48;
+template <int kNodes>
+__device__ __forceinline__ void stage_bvh_top(u32x4_t *s_top, const RenderArgs &a, BvhStack &stk)
+{
+	const uint32_t n = a.shapes.n_bvh_nodes < kNodes ? (uint32_t)a.shapes.n_bvh_nodes : (uint32_t)kNodes;
+	// (every load of a thread is asked for before the first is stored: as a loop -- load, wait, store, again -- the second
+	// 16 bytes of a thread began their round trip when the first had ended)
+	constexpr int kLoads = (kNodes * kBvhNodeQuads + kRBlock - 1) / kRBlock;
+	if (n) { // (uniform; a scene without meshes has no table: nothing is read)
+		u32x4_t v[kLoads];
+#pragma unroll
+		for (int k = 0; k < kLoads; ++k) { // (unconditional, so that nothing ties a load to its store: a lane past the nodes reads entry 0)
+			const uint32_t i = threadIdx.x + (uint32_t)k * kRBlock;
+			v[k] = reinterpret_cast<const u32x4_t *>(a.shapes.bvh)[i < n * (uint32_t)kBvhNodeQuads ? i : 0u];
+		}
+#pragma unroll
+		for (int k = 0; k < kLoads; ++k) {
+			const uint32_t i = threadIdx.x + (uint32_t)k * kRBlock;
+			if (i < n * (uint32_t)kBvhNodeQuads) s_top[i] = v[k];
+		}
+	}
+	__syncthreads();
+	stk.top = (const LdsQuad *)s_top;
+	stk.n_top = n;
+}
+// k_wave_shade (pg_render_wave.hip) walks its shadow rays with less LDS:
+constexpr int kShadeTopNodes = 40; // BVH nodes kept in LDS beside the stash (the ray-casting kernels keep kBvhTopNodes): what five workgroups per compute unit leave
+// The walk's stack keeps kShadeStack entries per lane in LDS here (the ray-casting kernels keep kLdsStack = 8; deeper ones go
+// to the lane's overflow strip either way), which leaves room for the stash: kShadeStash values per lane that only stage_b
+// reads wait in LDS while the two walks run.
+constexpr int kShadeStack = 6;
+static_assert(kShadeStack >= kMinLdsStack && kShadeStack <= kLdsStack, "k_wave_shade: LDS stack depth");
+
 // The tail of a long path (max_depth 30 in scenes/torus): a launch cannot be shorter than the slowest
 // single path's bounce (0.1-0.3 ms when that is two BVH walks inside a glass case), so a few
 // thousand survivors would cost that floor once per bounce.  At fixed checkpoints the host also

@@ -189,6 +189,29 @@ class WavefrontScene:
         self._upload(tree)
         N.check(tree._h, tree._lib.pg_render_stages(tree._h, self.stages))
 
+    def intersect(self, tree, origin: torch.Tensor, direction: torch.Tensor, tmax=None, any_hit: bool = False,
+                  walk_form: int = 0):
+        """pg_scene_intersect: the renderer's ray casting by itself, for tests -- origin, direction: (n,3) float32 cuda tensors,
+        tmax: (n,) float32 or None (no limit); tree: the SDTree whose context holds the scene.  Returns (t (n,) float32,
+        prim (n,) int32, uv (n,2) float32); walk_form 0 / 1 / 2: the ray-casting kernels' walk, k_wave_shade's, or one
+        without BVH nodes in LDS (same results)."""
+        self._upload(tree)
+        o = origin.to(torch.float32).contiguous()
+        d = direction.to(torch.float32).contiguous()
+        n = o.shape[0]
+        if o.shape != (n, 3) or d.shape != (n, 3):
+            raise ValueError("origin and direction must be (n,3)")
+        tm = torch.full((n,), float("inf"), dtype=torch.float32, device=o.device) if tmax is None else tmax.to(torch.float32).contiguous()
+        if tm.shape != (n,):
+            raise ValueError("tmax must be (n,)")
+        t = torch.empty(n, dtype=torch.float32, device=o.device)
+        prim = torch.empty(n, dtype=torch.int32, device=o.device)
+        uv = torch.empty((n, 2), dtype=torch.float32, device=o.device)
+        N.check(tree._h, tree._lib.pg_scene_intersect(tree._h, n, o.data_ptr(), d.data_ptr(), tm.data_ptr(), 1 if any_hit else 0,
+                                                      int(walk_form), t.data_ptr(), prim.data_ptr(), uv.data_ptr(),
+                                                      torch.cuda.current_stream().cuda_stream))
+        return t, prim, uv
+
     def join(self) -> None:
         """in_flight = 2: the current stream waits for every pass issued so far (no host synchronisation)."""
         if self._streams is not None:
