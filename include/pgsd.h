@@ -627,6 +627,23 @@ int pg_sort_places(pg_context *ctx, uint64_t n, const uint16_t *d_keys, const ui
 int pg_scene_intersect(pg_context *ctx, uint64_t n, const float *d_origin, const float *d_dir, const float *d_tmax,
                        int32_t any_hit, int32_t walk_form, float *d_t, int32_t *d_prim, float *d_uv, void *stream);
 
+/* The renderer's BSDF layer by itself, for tests: lane i evaluates and samples material row d_material_index[i] of the table
+ * d_materials (n_mat rows of PG_MATERIAL_STRIDE floats, the layout of pg_scene_desc.materials) through the very device
+ * functions the render kernels call, as a kernel of feature level `level` reads the row (0: every row is a two-sided diffuse
+ * material; 1, 2: roughconductor rows too; 3: every type, and one-sided rows).  Directions are in the local frame (z: the
+ * normal) and are taken as given, not normalised.
+ *   eval:   d_value[3 i ..] = f(wi, wo) cos(theta_o) and d_pdf[i], for wi = d_wi[3 i ..], wo = d_wo[3 i ..];
+ *   sample: from d_u[3 i] (the lobe sample) and d_u[3 i + 1], d_u[3 i + 2] (the 2-D sample): d_sampled_wo[3 i ..],
+ *           d_sampled_pdf[i], d_weight[3 i ..] = value / pdf, d_eta[i] (the relative index along the sampled direction) and
+ *           d_delta[i] (1: a delta lobe was sampled).  A failed sample leaves zeros.
+ * The table must pass the material-row checks of pg_scene_set_ex (known type, alpha finite and not 0, index ratio > 0); a
+ * row's texture is ignored: the plain reflectance is used.  Needs no scene.  n = 0 does nothing; n > 2^20, n_mat outside
+ * 1..65536, a row number outside the table, a level outside 0..3 and a NULL pointer are refused.  All pointers are device
+ * pointers.  Synchronises the stream (before reading the table and the row numbers back for the checks, and after the kernel). */
+int pg_bsdf_probe(pg_context *ctx, uint64_t n, uint64_t n_mat, const float *d_materials, const int32_t *d_material_index,
+                  const float *d_wi, const float *d_wo, const float *d_u, int32_t level, float *d_value, float *d_pdf,
+                  float *d_sampled_wo, float *d_sampled_pdf, float *d_weight, float *d_eta, int32_t *d_delta, void *stream);
+
 /* Per-kernel device time of pg_render_pass, measured with HIP events recorded on the launch
  * stream around each kernel (off by default).  pg_read_kernel_timing synchronises. */
 typedef struct pg_kernel_timing {

@@ -638,6 +638,26 @@ def bsdf_sample_full(material, wi, lobe, u1, u2):
     return wo, float(pdf[0]), w, float(eta[0]), int(delta[0])
 
 
+def bsdf_probe(materials, index, wi, wo, u, level=3):
+    """pgo_bsdf_probe: materials (n_mat,16), index (n,) int32, wi, wo, u (n,3) float32 -> (value (n,3), pdf (n,), sampled wo
+    (n,3), sample pdf (n,), weight (n,3), eta (n,) float32, delta (n,) int32) as a device kernel of feature level `level`
+    reads the rows (3: as they stand)."""
+    lb = lib()
+    lb.pgo_bsdf_probe.argtypes = [C.c_size_t, _P, _P, _P, _P, _P, C.c_int] + [_P] * 7
+    lb.pgo_bsdf_probe.restype = None
+    m = np.ascontiguousarray(materials, np.float32).reshape(-1, 16)
+    idx = np.ascontiguousarray(index, np.int32).reshape(-1)
+    n = idx.shape[0]
+    assert n == 0 or (idx.min() >= 0 and idx.max() < m.shape[0])
+    a, b, r = (np.ascontiguousarray(x, np.float32).reshape(n, 3) for x in (wi, wo, u))
+    value, swo, weight = (np.zeros((n, 3), np.float32) for _ in range(3))
+    pdf, spdf, eta = (np.zeros(n, np.float32) for _ in range(3))
+    delta = np.zeros(n, np.int32)
+    lb.pgo_bsdf_probe(n, _ptr(m), _ptr(idx), _ptr(a), _ptr(b), _ptr(r), int(level), _ptr(value), _ptr(pdf), _ptr(swo), _ptr(spdf),
+                      _ptr(weight), _ptr(eta), _ptr(delta))
+    return value, pdf, swo, spdf, weight, eta, delta
+
+
 def film_tent(seed, spp, width, height, L):
     """hdrfilm + tent rfilter reconstruction of one full-frame pass (pgo_film_tent); returns (3, H*W)."""
     return film("tent", seed, spp, width, height, L)

@@ -722,7 +722,7 @@ static void rd_eval_pdf(const material *mt, v3 wi, v3 wo, v3 *value, float *pdf)
 	*pdf = 0.0f;
 	const float alpha = mt->alpha, eta_m = mt->eta.x;
 	const float ci = wi.z, co = wo.z;
-	if (ci == 0.0f) return;
+	if (ci == 0.0f || eta_m == 1.0f) return; /* (eta 1: no interface -- the half vector of the one direction light takes is 0 / 0) */
 	const int reflect = ci * co > 0.0f;
 	const float eta = ci > 0.0f ? eta_m : 1.0f / eta_m, inv_eta = ci > 0.0f ? 1.0f / eta_m : eta_m;
 	const v3 m = rd_half_vector(wi, wo, eta, reflect);
@@ -756,7 +756,7 @@ static void rd_sample(const material *mt, v3 wi, float u1, float u, float v, v3 
 	*wo = V(0, 0, 0); *pdf = 0.0f; *weight = V(0, 0, 0); *eta_out = 0.0f;
 	const float alpha = mt->alpha, eta_m = mt->eta.x;
 	const float ci = wi.z;
-	if (ci == 0.0f) return;
+	if (ci == 0.0f || eta_m == 1.0f) return; /* (eta 1: no interface -- the half vector of the one direction light takes is 0 / 0) */
 	float pdf_m;
 	const v3 m = rc_sample_m(vflip_if(wi, ci < 0.0f), alpha, u, v, &pdf_m);
 	if (!(pdf_m != 0.0f)) return;
@@ -769,12 +769,18 @@ static void rd_sample(const material *mt, v3 wi, float u1, float u, float v, v3 
 	float w = 1.0f, dwh_dwo;
 	if (reflect) {
 		o = vsub(vscale(m, 2.0f * wim), wi);
-		dwh_dwo = 1.0f / (4.0f * dot3(o, m));
+		const float om = dot3(o, m);
+		if (!(om * wim > 0.0f)) return; /* (see below) */
+		dwh_dwo = 1.0f / (4.0f * om);
 		*eta_out = 1.0f;
 	} else {
 		o = vsub(vscale(m, wim * eta_ti + cos_t), vscale(wi, eta_ti)); /* refract(wi, m, cos_theta_t, eta_ti) */
 		w = eta_ti * eta_ti;
 		const float om = dot3(o, m), denom = wim + eta_it * om;
+		/* The direction leaves the microfacet on wi's side (reflection) or on the other one.  Only rounding can say otherwise,
+		 * for a normal perpendicular to wi -- GGX's sampler returns one for a 2-D sample on the unit square's border -- and
+		 * the Jacobians' 1 / dot(o, m) then means nothing (0 there: an infinite pdf).  Such a sample fails. */
+		if (!(om * wim < 0.0f)) return;
 		dwh_dwo = ((eta_it * eta_it) * om) / (denom * denom);
 		*eta_out = eta_it;
 	}
@@ -889,6 +895,35 @@ void pgo_bsdf_sample_full(const float *m, const float wi[3], float lobe, float u
 	*delta_out = delta;
 	wo[0] = o.x; wo[1] = o.y; wo[2] = o.z;
 	weight[0] = w.x; weight[1] = w.y; weight[2] = w.z;
+}
+
+/* The material a render kernel of feature level `level` makes of a row (the device's load_material and the kGeneral tests of
+ * its bsdf_eval_pdf<> / bsdf_sample<>): level 0 knows two-sided diffuse only and reads every row as that; levels 1 and 2 know
+ * roughconductor besides; one-sided rows and the types from the smooth conductor on are honoured from level 3 only. */
+static material load_material_at_level(const float *M, int level)
+{
+	material mt = load_material(M);
+	if (level < 3) mt.one_sided = 0;
+	if (level < 3 && mt.type >= 2) mt.type = 0;
+	if (level < 1) mt.type = 0;
+	return mt;
+}
+
+void pgo_bsdf_probe(size_t n, const float *materials, const int32_t *material_index, const float *wi, const float *wo,
+                    const float *u, int level, float *value, float *pdf, float *sampled_wo, float *sampled_pdf, float *weight,
+                    float *eta, int32_t *delta)
+{
+	for (size_t i = 0; i < n; ++i) {
+		const material mt = load_material_at_level(materials + (size_t)material_index[i] * PGO_MATERIAL_STRIDE, level);
+		v3 val, o, w;
+		int dl;
+		bsdf_eval_pdf(&mt, ld3(wi + 3 * i), ld3(wo + 3 * i), 1, &val, &pdf[i]);
+		bsdf_sample(&mt, ld3(wi + 3 * i), u[3 * i], u[3 * i + 1], u[3 * i + 2], 1, &o, &sampled_pdf[i], &w, &eta[i], &dl);
+		value[3 * i] = val.x; value[3 * i + 1] = val.y; value[3 * i + 2] = val.z;
+		sampled_wo[3 * i] = o.x; sampled_wo[3 * i + 1] = o.y; sampled_wo[3 * i + 2] = o.z;
+		weight[3 * i] = w.x; weight[3 * i + 1] = w.y; weight[3 * i + 2] = w.z;
+		delta[i] = dl;
+	}
 }
 
 void pgo_render_pass(const pgo_tree *prev, pgo_tree *current, size_t nq, const float *quads,

@@ -145,6 +145,14 @@ void pgo_bsdf_sample(const float *m, const float wi[3], float u1, float u2, floa
 void pgo_bsdf_sample_full(const float *m, const float wi[3], float lobe, float u1, float u2, float wo[3], float *pdf,
                           float weight[3], float *eta_out, int *delta_out);
 
+/* The same for n lanes in one call, every output of both: lane i takes row material_index[i] of `materials` (rows of
+ * PGO_MATERIAL_STRIDE floats), wi[3 i ..], wo[3 i ..] and u[3 i ..] = (lobe sample, 2-D sample).  `level`: the feature level of
+ * the device kernel whose reading of the row is wanted (0: every row two-sided diffuse; 1, 2: roughconductor too; 3: the
+ * row as it stands -- what the scalar entry points and the render pass compute). */
+void pgo_bsdf_probe(size_t n, const float *materials, const int32_t *material_index, const float *wi, const float *wo,
+                    const float *u, int level, float *value, float *pdf, float *sampled_wo, float *sampled_pdf, float *weight,
+                    float *eta, int32_t *delta);
+
 /* Film reconstruction of one full-frame pass with Mitsuba's `tent` reconstruction filter, radius one
  * pixel (the <rfilter type="tent"/> of scenes/cornell-box/scene.xml:27): what mi.render returns at
  * main.py:218.  Sample s of pixel (px,py) sits at (px + jx, py + jy), its first two sampler draws;

@@ -1,7 +1,11 @@
 // pg_probe.hip -- pg_scene_intersect: the renderer's ray casting by itself, for tests.  One ray per lane through intersect<>
 // of pg_render_dev.hpp -- the function the render kernels call, not a copy -- in the three forms those kernels give its walk:
 // the ray-casting kernels' (kLdsStack stack entries and kBvhTopNodes nodes in LDS), k_wave_shade's (kShadeStack entries,
-// kShadeTopNodes nodes, the kSlim walk) and one without staged nodes.  Nothing of the product path launches this kernel.
+// kShadeTopNodes nodes, the kSlim walk) and one without staged nodes.  pg_bsdf_probe: the BSDF layer by itself -- one
+// (material row, wi, wo, u) per lane through load_material, bsdf_eval_pdf<> and bsdf_sample<> of the same header.  Nothing of
+// the product path launches these kernels.
+#include <vector>
+
 #include "pg_render_dev.hpp"
 #include "pg_scene_state.hpp"
 
@@ -64,7 +68,79 @@ void launch_any(bool any, int form, dim3 grid, hipStream_t s, const ProbeArgs &p
 	else launch_form<kLevel, false>(form, grid, s, p);
 }
 
+struct BsdfProbeArgs {
+	uint64_t n;
+	const float *mats;       // n_mat rows of kMaterialStride floats
+	const int32_t *mat;      // (n) row of lane i: checked against n_mat on the host
+	const float *wi, *wo, *u; // (n,3) each; u = (lobe sample, 2-D sample)
+	float *value, *pdf;      // (n,3), (n): bsdf_eval_pdf
+	float *s_wo, *s_pdf, *s_weight, *s_eta; // (n,3), (n), (n,3), (n): bsdf_sample
+	int32_t *s_delta;        // (n)
+};
+
+// No loop but rc_sample_visible_11's three Newton steps; every address is a function of tid < n and of a checked row number.
+template <int kLevel>
+__global__ __launch_bounds__(kRBlock) void k_probe_bsdf(BsdfProbeArgs p)
+{
+	const uint64_t tid = (uint64_t)blockIdx.x * kRBlock + threadIdx.x;
+	if (tid >= p.n) return;
+	const Material mt = load_material(p.mats + (uint64_t)p.mat[tid] * kMaterialStride, kLevel);
+	const v3 wi = ld3(p.wi + 3 * tid), wo = ld3(p.wo + 3 * tid), u = ld3(p.u + 3 * tid);
+	v3 value, o, weight;
+	float pdf, s_pdf, eta;
+	bool delta;
+	bsdf_eval_pdf<kLevel>(mt, wi, wo, true, value, pdf);
+	bsdf_sample<kLevel>(mt, wi, u.x, u.y, u.z, true, o, s_pdf, weight, eta, delta);
+	p.value[3 * tid] = value.x; p.value[3 * tid + 1] = value.y; p.value[3 * tid + 2] = value.z;
+	p.pdf[tid] = pdf;
+	p.s_wo[3 * tid] = o.x; p.s_wo[3 * tid + 1] = o.y; p.s_wo[3 * tid + 2] = o.z;
+	p.s_pdf[tid] = s_pdf;
+	p.s_weight[3 * tid] = weight.x; p.s_weight[3 * tid + 1] = weight.y; p.s_weight[3 * tid + 2] = weight.z;
+	p.s_eta[tid] = eta;
+	p.s_delta[tid] = delta ? 1 : 0;
+}
+
 } // namespace
+
+int pg_bsdf_probe(pg_context *ctx, uint64_t n, uint64_t n_mat, const float *d_materials, const int32_t *d_material_index,
+                  const float *d_wi, const float *d_wo, const float *d_u, int32_t level, float *d_value, float *d_pdf,
+                  float *d_sampled_wo, float *d_sampled_pdf, float *d_weight, float *d_eta, int32_t *d_delta, void *stream)
+{
+	if (!ctx) return PG_ERR_INVALID;
+	if (level < 0 || level > 3) return fail(ctx, PG_ERR_INVALID, "pg_bsdf_probe: level must be 0, 1, 2 or 3");
+	if (n > kProbeMaxRays) return fail(ctx, PG_ERR_INVALID, "pg_bsdf_probe: at most 2^20 lanes in one call");
+	if (n == 0) return PG_OK;
+	if (!d_materials || !d_material_index || !d_wi || !d_wo || !d_u || !d_value || !d_pdf || !d_sampled_wo || !d_sampled_pdf ||
+	    !d_weight || !d_eta || !d_delta)
+		return fail(ctx, PG_ERR_INVALID, "pg_bsdf_probe: NULL pointer");
+	if (n_mat == 0 || n_mat > 65536) return fail(ctx, PG_ERR_INVALID, "pg_bsdf_probe: need 1..65536 material rows");
+	PG_HIP(ctx, hipSetDevice(ctx->device));
+	const hipStream_t s = (hipStream_t)stream;
+	PG_HIP(ctx, hipStreamSynchronize(s)); // (the caller's writes of the inputs, before the host reads them)
+	// the rows and the row numbers are checked on the host before a lane follows them
+	std::vector<float> rows(n_mat * kMaterialStride);
+	PG_HIP(ctx, hipMemcpy(rows.data(), d_materials, rows.size() * sizeof(float), hipMemcpyDeviceToHost));
+	// (a probe has no textures: any index a scene could hold passes, and the kernel reads the row's plain reflectance)
+	if (const char *err = check_material_rows(rows.data(), n_mat, 65536)) return fail(ctx, PG_ERR_INVALID, std::string("pg_bsdf_probe: ") + err);
+	std::vector<int32_t> index(n);
+	PG_HIP(ctx, hipMemcpy(index.data(), d_material_index, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+	for (uint64_t i = 0; i < n; ++i)
+		if (index[i] < 0 || (uint64_t)index[i] >= n_mat) return fail(ctx, PG_ERR_INVALID, "pg_bsdf_probe: material index outside the table");
+	BsdfProbeArgs p;
+	p.n = n; p.mats = d_materials; p.mat = d_material_index; p.wi = d_wi; p.wo = d_wo; p.u = d_u;
+	p.value = d_value; p.pdf = d_pdf; p.s_wo = d_sampled_wo; p.s_pdf = d_sampled_pdf; p.s_weight = d_weight; p.s_eta = d_eta;
+	p.s_delta = d_delta;
+	const dim3 grid((unsigned)((n + kRBlock - 1) / kRBlock));
+	switch (level) {
+	case 0: hipLaunchKernelGGL((k_probe_bsdf<0>), grid, dim3(kRBlock), 0, s, p); break;
+	case 1: hipLaunchKernelGGL((k_probe_bsdf<1>), grid, dim3(kRBlock), 0, s, p); break;
+	case 2: hipLaunchKernelGGL((k_probe_bsdf<2>), grid, dim3(kRBlock), 0, s, p); break;
+	default: hipLaunchKernelGGL((k_probe_bsdf<3>), grid, dim3(kRBlock), 0, s, p); break;
+	}
+	PG_HIP(ctx, hipGetLastError());
+	PG_HIP(ctx, hipStreamSynchronize(s));
+	return PG_OK;
+}
 
 int pg_scene_intersect(pg_context *ctx, uint64_t n, const float *d_origin, const float *d_dir, const float *d_tmax,
                        int32_t any_hit, int32_t walk_form, float *d_t, int32_t *d_prim, float *d_uv, void *stream)

@@ -852,7 +852,7 @@ __device__ PG_OUTLINE void rd_eval_pdf(const float *M, v3 wi, v3 wo, v3 &value, 
 	pdf = 0.0f;
 	const float alpha = M[MAT_ALPHA], eta_m = M[MAT_ETA];
 	const float ci = wi.z, co = wo.z;
-	if (ci == 0.0f) return;
+	if (ci == 0.0f || eta_m == 1.0f) return; // (eta 1: no interface -- the half vector of the one direction light takes is 0 / 0)
 	const bool reflect = ci * co > 0.0f;
 	const float eta = ci > 0.0f ? eta_m : 1.0f / eta_m, inv_eta = ci > 0.0f ? 1.0f / eta_m : eta_m;
 	v3 m = normalize3(vadd(wi, vscale(wo, reflect ? 1.0f : eta)));
@@ -883,7 +883,7 @@ __device__ PG_OUTLINE void rd_sample(const float *M, v3 wi, float u1, float u, f
 	wo = V(0, 0, 0); pdf = 0.0f; weight = V(0, 0, 0); eta_out = 0.0f;
 	const float alpha = M[MAT_ALPHA], eta_m = M[MAT_ETA];
 	const float ci = wi.z;
-	if (ci == 0.0f) return;
+	if (ci == 0.0f || eta_m == 1.0f) return; // (eta 1: no interface -- the half vector of the one direction light takes is 0 / 0)
 	float pdf_m;
 	const v3 m = rc_sample_m(vflip_if(wi, ci < 0.0f), alpha, u, v, pdf_m);
 	if (!(pdf_m != 0.0f)) return;
@@ -896,12 +896,18 @@ __device__ PG_OUTLINE void rd_sample(const float *M, v3 wi, float u1, float u, f
 	float w = 1.0f, dwh_dwo, e;
 	if (reflect) {
 		o = vsub(vscale(m, 2.0f * wim), wi);
-		dwh_dwo = 1.0f / (4.0f * dot3(o, m));
+		const float om = dot3(o, m);
+		if (!(om * wim > 0.0f)) return; // (see below)
+		dwh_dwo = 1.0f / (4.0f * om);
 		e = 1.0f;
 	} else {
 		o = vsub(vscale(m, wim * eta_ti + cos_t), vscale(wi, eta_ti)); // refract(wi, m, cos_theta_t, eta_ti)
 		w = eta_ti * eta_ti;
 		const float om = dot3(o, m), denom = wim + eta_it * om;
+		// The direction leaves the microfacet on wi's side (reflection) or on the other one.  Only rounding can say otherwise, for a
+		// normal perpendicular to wi -- GGX's sampler returns one for a 2-D sample on the unit square's border -- and the
+		// Jacobians' 1 / dot(o, m) then means nothing (0 there: an infinite pdf).  Such a sample fails.
+		if (!(om * wim < 0.0f)) return;
 		dwh_dwo = ((eta_it * eta_it) * om) / (denom * denom);
 		e = eta_it;
 	}

@@ -18,6 +18,7 @@ struct PackedScene {
 	std::vector<int32_t> emitters; // shape numbers of flagged quads, then flagged spheres, then -1-k for directional light k
 	bool tri_normals = false, tri_uvs = false;
 	int general = 0;               // feature level of the kernels (see intersect()): decided by the materials the shapes USE
+	std::string error;             // the text of a refusal that is put together here (the others are literals)
 };
 
 // a finite float that is a whole number in [0, n): how the tables name a row of another table
@@ -88,16 +89,7 @@ const char *check_and_pack(const pg_scene_desc &sc, const pg_camera &cam, Packed
 				return "pg_scene_set: bitmap texture outside the texel array";
 		} else if (T[TEX_KIND] != TEX_CHECKERBOARD) return "pg_scene_set: unknown texture kind";
 	}
-	for (uint64_t m = 0; m < n_mats; ++m) {
-		const float *M = &mats[m * kMaterialStride];
-		const float type = M[MAT_TYPE];
-		if (!is_index(type, MAT_ROUGH_DIELECTRIC + 1)) return "pg_scene_set: unknown material type";
-		const bool rough = type == (float)MAT_ROUGH_CONDUCTOR || type == (float)MAT_ROUGH_DIELECTRIC;
-		if (rough && !(fabsf(M[MAT_ALPHA]) > 0.0f && fabsf(M[MAT_ALPHA]) < 3.0e38f)) return "pg_scene_set: microfacet alpha must be finite and not 0";
-		if ((type == (float)MAT_DIELECTRIC || type == (float)MAT_ROUGH_DIELECTRIC) && !(M[MAT_ETA] > 0.0f))
-			return "pg_scene_set: dielectric index ratio must be > 0";
-		if (!is_index(M[MAT_TEXTURE], n_tex + 1)) return "pg_scene_set: material texture index out of range"; // (index + 1; 0: none)
-	}
+	if (const char *why = check_material_rows(mats.data(), n_mats, n_tex)) return (out.error = std::string("pg_scene_set: ") + why).c_str();
 	int general = ns > 0 ? 1 : 0;
 	// the material row a shape names: false when it names none; raises the feature level to what the material needs
 	auto use_material = [&](float mi) {
@@ -177,6 +169,24 @@ int upload_tables(pg_context *ctx, SceneState &s, const pg_scene_desc &sc, const
 }
 
 } // namespace
+
+// What a material row must satisfy before a kernel reads it (pg_scene_state.hpp): a known type, a microfacet alpha the
+// distributions can divide by, a positive index ratio, a texture the scene has (index + 1; 0: none).
+const char *check_material_rows(const float *mats, uint64_t n_mats, uint64_t n_tex)
+{
+	for (uint64_t m = 0; m < n_mats; ++m) {
+		const float *M = &mats[m * kMaterialStride];
+		const float type = M[MAT_TYPE];
+		if (!is_index(type, MAT_ROUGH_DIELECTRIC + 1)) return "unknown material type";
+		const bool rough = type == (float)MAT_ROUGH_CONDUCTOR || type == (float)MAT_ROUGH_DIELECTRIC;
+		if (rough && !(fabsf(M[MAT_ALPHA]) > 0.0f && fabsf(M[MAT_ALPHA]) < 3.0e38f)) return "microfacet alpha must be finite and not 0";
+		if ((type == (float)MAT_DIELECTRIC || type == (float)MAT_ROUGH_DIELECTRIC) && !(M[MAT_ETA] > 0.0f))
+			return "dielectric index ratio must be > 0";
+		if (!is_index(M[MAT_TEXTURE], n_tex + 1)) return "material texture index out of range"; // (index + 1; 0: none)
+	}
+	return nullptr;
+}
+
 } // namespace pg
 
 using namespace pg;

@@ -29,4 +29,9 @@ SceneState &scene_state(pg_context *ctx);
 bool split_pipeline_always(pg_context *ctx);
 bool record_geometry_wanted(pg_context *ctx);
 
+// pg_scene.hip: the checks pg_scene_set_ex applies to the rows of a material table (host memory, n_mats rows of
+// kMaterialStride floats; n_tex: the textures a row may name) -- the bare reason of the first one a row fails
+// ("unknown material type": the caller puts its own name in front), or nullptr
+const char *check_material_rows(const float *mats, uint64_t n_mats, uint64_t n_tex);
+
 } // namespace pg

@@ -340,6 +340,25 @@ class SDTree:
         self._ck(self._lib.pg_sort_places(self._h, n, k.data_ptr(), None if d_live is None else d_live.data_ptr(), out.data_ptr(), _stream_ptr()))
         return out
 
+    def bsdfProbe(self, materials: torch.Tensor, index: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, u: torch.Tensor,
+                  level: int = 3):
+        """pg_bsdf_probe: the renderer's BSDF layer by itself, for tests -- materials (n_mat, 16) float32, index (n,) int32,
+        wi, wo, u (n,3) float32, all on this device; returns (value (n,3), pdf (n,), sampled wo (n,3), sample pdf (n,),
+        weight (n,3), eta (n,), delta (n,) int32) as a kernel of feature level `level` computes them."""
+        f = lambda t: t.to(torch.float32).contiguous()
+        m, a, b, r = f(materials), f(wi), f(wo), f(u)
+        idx = index.to(torch.int32).contiguous()
+        n = int(idx.numel())
+        if m.dim() != 2 or m.shape[1] != 16 or a.shape != (n, 3) or b.shape != (n, 3) or r.shape != (n, 3):
+            raise ValueError("materials must be (n_mat,16); wi, wo and u (n,3); index (n,)")
+        new = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)
+        value, pdf, swo, spdf, weight, eta = new(n, 3), new(n), new(n, 3), new(n), new(n, 3), new(n)
+        delta = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self._ck(self._lib.pg_bsdf_probe(self._h, n, m.shape[0], m.data_ptr(), idx.data_ptr(), a.data_ptr(), b.data_ptr(), r.data_ptr(),
+                                         int(level), value.data_ptr(), pdf.data_ptr(), swo.data_ptr(), spdf.data_ptr(),
+                                         weight.data_ptr(), eta.data_ptr(), delta.data_ptr(), _stream_ptr()))
+        return value, pdf, swo, spdf, weight, eta, delta
+
     def packAccumulators(self) -> torch.Tensor:
         """sdTree_current's accumulators in the 24-byte exchange format (pg_exchange_pack, on the current stream): the int64
         tensor a host-side collective sums instead of accumulators() -- a quarter fewer bytes; unpackAccumulators() writes
