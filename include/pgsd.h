@@ -202,6 +202,32 @@ int pg_process_and_splat(pg_context *ctx, uint64_t num_rays, int32_t max_depth,
  * index in pg_splat's stream; in pg_process_and_splat it is the dense slot g = ray * max_depth + depth modulo 2^32.  The two
  * routes therefore jitter the same record differently (a compacted stream numbers the survivors, the dense buffer the slots).
  *
+ * PG_SPATIAL_OVERLAP_BOX.  The box filter itself, of which the stochastic box is a one-sample estimate: the record is shared
+ * between all KD leaves that a box the size of its own KD leaf, placed around its position, overlaps, each in proportion to the
+ * overlap's volume.  No random numbers: `seed` is ignored.  For a record with position p inside the root box (inclusive; a
+ * record outside it or with a NaN coordinate is handled exactly as without the filter): L = the KD leaf of p,
+ *     e[a]  = kd_bbox_max[L][a] - kd_bbox_min[L][a]                                   a = x, y, z
+ * The record's COUNT goes to L alone, and within L's quadtree to the leaf the nearest walk of the path direction finds -- also
+ * where that leaf's share of the energy comes out zero; a counted record whose direction reaches no leaf increments the fallback
+ * counter of L's quadtree once, as without the filter.  If L is the root (depth 0), or an e[a] is not finite or is <= 0, the
+ * record is handled exactly as with PG_SPATIAL_NEAREST.  Else the box B = [lo, hi] is, per axis,
+ *     lo[a] = max(p[a] - 0.5 * e[a], root_min[a])          hi[a] = lo[a] + e[a]
+ *     if hi[a] > root_max[a]:  hi[a] = root_max[a],  lo[a] = max(hi[a] - e[a], root_min[a])
+ * i.e. B is SHIFTED to stay inside the root box; nothing is clipped away (as the directional footprint in y).  For every KD
+ * leaf M of the tree
+ *     len[a] = min(kd_bbox_max[M][a], hi[a]) - max(kd_bbox_min[M][a], lo[a])
+ * (The leaves are found from the root, entering a child only if B reaches across its parent's split plane.  That finds every
+ * leaf with len[a] > 0 in a tree whose boxes nest -- a child's box is its parent's, cut at the split plane on the split axis --
+ * which holds for every tree this library builds or refines; pg_import verifies that the children of a node meet at its split
+ * plane, not the nesting, and on an imported tree whose boxes do not nest the leaves the walk does not reach receive nothing.)
+ * M takes part exactly when len[a] > 0 on all three axes, with the share
+ *     s = ((len[0] / e[0]) * (len[1] / e[1])) * (len[2] / e[2])          (three IEEE divisions, two products)
+ * and for each (direction, weight w) pair of the record -- (direction, radiance / wo_pdf) and, with store_nee, (direction_nee,
+ * radiance_nee_lum / wo_pdf) -- M's quadtree receives the pair (direction, w * s) (one product) through the directional filter
+ * that is set: PG_DIRECTIONAL_NEAREST deposits quantize(w * s) in the nearest leaf of M's quadtree, PG_DIRECTIONAL_BOX follows
+ * the rules below with w := w * s and N found in M's own quadtree.  No counts are added in M != L.  A direction outside the unit
+ * square deposits nothing in any M.  Energy is conserved up to these roundings and one truncation to 2^-PG_FRAC_BITS per deposit.
+ *
  * PG_DIRECTIONAL_BOX.  For a (direction c = (cx, cy), weight w) pair of a record -- (direction, radiance / wo_pdf) and, with
  * store_nee, (direction_nee, radiance_nee_lum / wo_pdf) -- in the quadtree of the record's KD leaf.  A direction outside the
  * unit square is handled exactly as without the filter (fallback counter included).  Otherwise N = the leaf the nearest walk
@@ -228,7 +254,8 @@ int pg_process_and_splat(pg_context *ctx, uint64_t num_rays, int32_t max_depth,
  * Energy is conserved up to the roundings of these products and one truncation to 2^-PG_FRAC_BITS per deposit.  A weight
  * whose own quantize(w) is zero (0, NaN, |w| < 2^-PG_FRAC_BITS) deposits nothing anywhere, as every part of it would.
  *
- * Both filters may be set: the jitter first, then the directional deposits in the quadtree of the KD leaf of p'.
+ * A spatial and the directional filter may be set together: the jitter first, then the directional deposits in the quadtree of
+ * the KD leaf of p'; or the directional deposits of (direction, w * s) in every KD leaf under the overlap box.
  * Sums stay exact integers: filtered results do not depend on the order of the records or of the launches, and refine, the
  * exchange format, pg_allreduce and export see nothing new.
  * The library's own renderer by default does not carry a vertex's position and directions to its splat (it names the two leaves
@@ -239,6 +266,7 @@ int pg_process_and_splat(pg_context *ctx, uint64_t num_rays, int32_t max_depth,
  * pg_enable_depth_counters: a filtered launch adds nothing to the depth counters. */
 #define PG_SPATIAL_NEAREST 0
 #define PG_SPATIAL_STOCHASTIC_BOX 1
+#define PG_SPATIAL_OVERLAP_BOX 3   /* 2 is not assigned and stays refused */
 #define PG_DIRECTIONAL_NEAREST 0
 #define PG_DIRECTIONAL_BOX 1
 int pg_set_splat_filter(pg_context *ctx, int32_t spatial, int32_t directional, uint32_t seed);
@@ -544,8 +572,10 @@ int pg_render_split_pipeline(pg_context *ctx, int32_t on);
  *     g = ray * max_depth + depth modulo 2^32 (ray: the entry's lane of the pass, depth: its bounce), the seed the one given to
  *     pg_set_splat_filter.  (On the initial tree every filter is the nearest deposit, as for pg_splat.)
  *     Directional-box results are integer sums of per-record deposits: independent of launch order, of sharding (tiles, stripes,
- *     ranks) and of batching.  Stochastic-jitter results are deterministic for a given launch, but do not equal those of a
- *     differently batched or sharded run: record numbers are per launch.  A filtered splat does not touch the depth counters.
+ *     ranks) and of batching.  PG_SPATIAL_OVERLAP_BOX results belong to the same class, with either directional filter: no
+ *     record number and no seed enters them.  Stochastic-jitter results are deterministic for a given launch, but do not equal
+ *     those of a differently batched or sharded run: record numbers are per launch.  A filtered splat does not touch the depth
+ *     counters.
  * A final-iteration pass is untouched and runs the form pg_render_stages selects.  A context with the switch off behaves exactly
  * as before this entry point existed, the filter refusal included.  Takes effect at the next pg_scene_set[_ex].  Default 0. */
 int pg_render_record_geometry(pg_context *ctx, int32_t on);

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 
-SPATIAL_FILTERS, DIRECTIONAL_FILTERS = ("nearest", "stochastic"), ("nearest", "box")
+SPATIAL_FILTERS, DIRECTIONAL_FILTERS = ("nearest", "stochastic", "overlap"), ("nearest", "box")
 
 
 def parse_splat_filter(text: str):
@@ -61,8 +61,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--ground-truth", default=None, help=".exr or .npy (H,W,3) linear ground truth for MSE, e.g. "
                     "scenes/cornell-box/TungstenRender.exr or tests/golden/cornell_gt_256_f16.npy")
     ap.add_argument("--splat-filter", type=parse_splat_filter, default=("nearest", "nearest"), metavar="SPATIAL,DIRECTIONAL",
-                    help="training filters of the recording passes (not in the reference): SPATIAL nearest | stochastic, "
-                         "DIRECTIONAL nearest | box; the default nearest,nearest runs exactly what runs without the option")
+                    help="training filters of the recording passes (not in the reference): SPATIAL nearest | stochastic | overlap "
+                         "(the deterministic box), DIRECTIONAL nearest | box; the default nearest,nearest runs exactly what runs "
+                         "without the option")
     return ap
 
 

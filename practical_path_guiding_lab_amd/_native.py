@@ -18,6 +18,7 @@ PG_OK = 0
 PG_ACC_LIMBS = 3
 PG_FRAC_BITS = 40
 PG_SPATIAL_NEAREST, PG_SPATIAL_STOCHASTIC_BOX = 0, 1
+PG_SPATIAL_OVERLAP_BOX = 3  # (2 is not assigned)
 PG_DIRECTIONAL_NEAREST, PG_DIRECTIONAL_BOX = 0, 1
 
 

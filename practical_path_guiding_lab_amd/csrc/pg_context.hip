@@ -186,7 +186,7 @@ int pg_set_iteration(pg_context *ctx, int32_t iteration, int32_t is_final)
 int pg_set_splat_filter(pg_context *ctx, int32_t spatial, int32_t directional, uint32_t seed)
 {
 	if (!ctx) return PG_ERR_INVALID;
-	if (spatial != PG_SPATIAL_NEAREST && spatial != PG_SPATIAL_STOCHASTIC_BOX)
+	if (spatial != PG_SPATIAL_NEAREST && spatial != PG_SPATIAL_STOCHASTIC_BOX && spatial != PG_SPATIAL_OVERLAP_BOX)
 		return fail(ctx, PG_ERR_INVALID, "pg_set_splat_filter: unknown spatial filter");
 	if (directional != PG_DIRECTIONAL_NEAREST && directional != PG_DIRECTIONAL_BOX)
 		return fail(ctx, PG_ERR_INVALID, "pg_set_splat_filter: unknown directional filter");

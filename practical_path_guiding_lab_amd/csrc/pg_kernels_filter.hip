@@ -1,6 +1,9 @@
 // pg_kernels_filter.hip -- recording into sdTree_current through the training filters of pg_set_splat_filter
 // (include/pgsd.h states the semantics; this file follows them operation by operation):
 //   stochastic box in space : the record's position is jittered by the extent of its KD leaf before the leaf is looked up;
+//   overlap box in space    : the record is shared between all KD leaves that a box the size of its KD leaf, placed around its
+//                             position and shifted to stay inside the root box, overlaps, each in proportion to the overlap's
+//                             volume;
 //   box in direction        : a (direction, weight) pair is shared between all quadtree leaves that a square the size of its
 //                             nearest leaf, centred on the direction, overlaps.
 // Accumulators exist at quadtree leaves only and all sums are integers (pg_kernels_splat.hip), so a filtered record is just
@@ -15,6 +18,7 @@
 // scratch memory): the walk keeps the record of the depth-d cell (the anchor), the level it stands on and the child it stands
 // at on every level above -- two bits per level in one 64-bit word -- and, when it has finished a record's four children,
 // climbs by walking down again from the anchor along those bits.  Subtrees the footprint does not reach are never entered.
+// The KD leaves under a record's box are enumerated the same way (KdWalk), one bit per level.
 #include "pg_descent.hpp"
 #include "pg_kernels.hpp"
 #include "pg_splat_dev.hpp"
@@ -265,6 +269,126 @@ __device__ __forceinline__ KdPlan plan_kd(const TreeView &t, const float *planes
 	return p;
 }
 
+// ---- PG_SPATIAL_OVERLAP_BOX: the KD leaves under a record's box ----
+__device__ __forceinline__ float sel3f(uint32_t k, float a, float b, float c) { return k == 0u ? a : (k == 1u ? b : c); }
+__device__ __forceinline__ float minf(float a, float b) { return a < b ? a : b; }
+__device__ __forceinline__ float maxf(float a, float b) { return a > b ? a : b; }
+
+// The depth-first walk over the KD leaves a box reaches, WITHOUT a stack: the child taken on every level (`path`, one bit per
+// level) and the levels on which the right child is still to be visited (`pend`).  A finished leaf hands over to the right
+// child of the deepest pending level: the walk goes down again along `path` -- from the anchor, the node at which it first
+// had to go both ways while nothing was pending: everything still to be visited lies below it.
+struct KdWalk {
+	bool active;
+	uint32_t home;            // L, the leaf of the record's own position: the caller has dealt with it
+	float lx, ly, lz, hx, hy, hz; // the box
+	float ex, ey, ez;         // its extent: that of L
+	uint32_t node, k;         // the node the walk stands on and its level
+	uint32_t child, axis;     // its child word (0: a leaf) and split axis
+	float split;
+	uint32_t tree;            // a leaf's quadtree
+	uint32_t path, pend, fk;  // below level fk the walk follows `path` instead of deciding
+	uint32_t anchor, anchor_k;
+};
+
+__device__ __forceinline__ void kd_walk_load(KdWalk &w, const TreeView &t, uint32_t node)
+{
+	const KdNode nd = load_kd(t.kd, node);
+	w.node = node;
+	w.child = nd.child;
+	w.axis = nd.axis_depth & 3u;
+	w.split = nd.split;
+	w.tree = nd.tree;
+}
+
+// include/pgsd.h: the share of KD node `node` in the box of `w`; false: it takes no part
+__device__ __forceinline__ bool kd_share(const KdWalk &w, const pg_filter_args &f, uint32_t node, float &s)
+{
+	const float *lo = f.kd_bmin + 3 * (size_t)node, *hi = f.kd_bmax + 3 * (size_t)node;
+	const float l0 = minf(hi[0], w.hx) - maxf(lo[0], w.lx);
+	const float l1 = minf(hi[1], w.hy) - maxf(lo[1], w.ly);
+	const float l2 = minf(hi[2], w.hz) - maxf(lo[2], w.lz);
+	s = ((l0 / w.ex) * (l1 / w.ey)) * (l2 / w.ez);
+	return l0 > 0.0f && l1 > 0.0f && l2 > 0.0f;
+}
+
+// The record's box, and the walk over it made ready at the root.  False: the record is handled as PG_SPATIAL_NEAREST (L is the
+// root, or an extent of L is not a positive finite number).
+__device__ __forceinline__ bool kd_walk_begin(KdWalk &w, const TreeView &t, const pg_filter_args &f, uint32_t L, float x, float y,
+                                              float z)
+{
+	w.active = false;
+	w.home = L;
+	if (L == 0u) return false;
+	const float *lo = f.kd_bmin + 3 * (size_t)L, *hi = f.kd_bmax + 3 * (size_t)L;
+	const float p[3] = {x, y, z};
+	float e[3], bl[3], bh[3];
+	bool ok = true;
+#pragma unroll
+	for (int a = 0; a < 3; ++a) {
+		e[a] = hi[a] - lo[a];
+		ok = ok && e[a] > 0.0f && e[a] < __builtin_inff(); // (NaN fails both)
+		bl[a] = maxf(p[a] - 0.5f * e[a], t.bmin[a]);
+		bh[a] = bl[a] + e[a];
+		if (bh[a] > t.bmax[a]) { bh[a] = t.bmax[a]; bl[a] = maxf(bh[a] - e[a], t.bmin[a]); }
+	}
+	if (!ok) return false;
+	w.ex = e[0]; w.ey = e[1]; w.ez = e[2];
+	w.lx = bl[0]; w.ly = bl[1]; w.lz = bl[2];
+	w.hx = bh[0]; w.hy = bh[1]; w.hz = bh[2];
+	w.k = 0; w.path = 0; w.pend = 0; w.fk = 0;
+	w.anchor = 0; w.anchor_k = 0;
+	kd_walk_load(w, t, 0u);
+	w.active = true;
+	return true;
+}
+
+// The next KD leaf other than L that takes part, with its quadtree and share -- or false when this call found none (the caller
+// goes on calling while w.active).  The work of one call is bounded, like box_next's.
+__device__ __forceinline__ bool kd_walk_next(KdWalk &w, const TreeView &t, const pg_filter_args &f, uint32_t &tree, float &s)
+{
+	for (int guard = 0; guard < 8 && w.active; ++guard) {
+		if (w.child != 0u && w.k < 31u) { // an inner node: down (KD depth <= 30: the depth limit of pg_setup and pg_import)
+			uint32_t bit = (w.path >> w.k) & 1u;
+			bool down = true;
+			if (w.k >= w.fk) { // a child is visited only if the box reaches across the split plane
+				const bool left = sel3f(w.axis, w.lx, w.ly, w.lz) < w.split, right = sel3f(w.axis, w.hx, w.hy, w.hz) > w.split;
+				bit = left ? 0u : 1u;
+				down = left || right;
+				if (left && right) {
+					if (w.pend == 0u) { w.anchor = w.node; w.anchor_k = w.k; }
+					w.pend |= 1u << w.k;
+				}
+				w.path = (w.path & ~(1u << w.k)) | (bit << w.k);
+			}
+			if (down) {
+				kd_walk_load(w, t, w.child + bit);
+				++w.k;
+				continue;
+			}
+		}
+		bool found = false;
+		if (w.child == 0u && w.node != w.home) {
+			found = kd_share(w, f, w.node, s);
+			tree = w.tree;
+		}
+		if (w.pend == 0u) w.active = false;
+		else { // on to the right child of the deepest pending level
+			const uint32_t l = 31u - (uint32_t)__builtin_clz(w.pend);
+			w.pend &= ~(1u << l);
+			w.path = (w.path & ((1u << l) - 1u)) | (1u << l);
+			w.fk = l + 1u;
+			if (w.k == l + 1u) kd_walk_load(w, t, w.node + 1u); // the walk stands on its left child: the children of a node are adjacent
+			else {
+				w.k = w.anchor_k;
+				kd_walk_load(w, t, w.anchor);
+			}
+		}
+		if (found) return true;
+	}
+	return false;
+}
+
 // The wave's queue of deposits: kQueue entries of {accumulator | count flag, weight} in LDS, filled by the walks' rounds and
 // drained 64 at a time through coop_add.  `len` is uniform over the wave.
 constexpr uint32_t kQueue = 512;
@@ -288,8 +412,28 @@ __device__ __forceinline__ void queue_drain(const AccumView &a, uint2 *s_q, uint
 	len = 0;
 }
 
-// One record: the KD leaf (jittered or not), the two nearest walks, then the deposits of both pairs, queued in rounds in
-// which every lane of the wave takes part.
+// The pairs of a record enter quadtree `tree`: the two nearest walks, and the deposits of the path pair (weight w) begun; the
+// emitter pair waits in `cn`.  counted: the record's count goes to this tree (and, should its direction reach no leaf, to the
+// tree's fallback counter).
+__device__ __forceinline__ void open_tree(const TreeView &t, const AccumView &a, const pg_filter_args &f, int store_nee, uint32_t tree,
+                                          bool counted, float dx, float dy, float nx, float ny, float w, BoxWalk &b, TreeHead &head,
+                                          LeafCursor &cn, bool &second)
+{
+	head = load_head_s(t.head, tree);
+	const JumpPre pre_p = jump_prefetch(t.jump, tree, dx, dy, in_unit_square(dx, dy));
+	const JumpPre pre_n = jump_prefetch(t.jump, tree, nx, ny, store_nee != 0 && in_unit_square(nx, ny));
+	LeafCursor cp = leaf_cursor_pre(head, dx, dy, true, pre_p);
+	cn = leaf_cursor_pre(head, nx, ny, store_nee != 0, pre_n);
+	quad_find_leaf_slots2(t.rec, cp, cn);
+	// a counted record whose direction reaches no leaf (outside the unit square): fallback counter
+	if (counted && !cp.found) atomicAdd(a.leaf_count + tree, 1ull);
+	box_begin(b, t, tree, cp, w, counted ? 1 : 0, f.directional != 0);
+	second = store_nee != 0 && cn.found;
+}
+
+// One record: the KD leaf (jittered or not) -- kOverlap: one KD leaf under the record's box after the other, L first --, the
+// two nearest walks, then the deposits of both pairs, queued in rounds in which every lane of the wave takes part.
+template <bool kOverlap>
 __device__ __forceinline__ void splat_filtered(const TreeView &t, const AccumView &a, const float *planes, const pg_filter_args &f,
                                                int store_nee, bool valid, uint32_t index, float x, float y, float z, float dx,
                                                float dy, float radiance, float wo_pdf, float nx, float ny, float nee_lum,
@@ -306,28 +450,49 @@ __device__ __forceinline__ void splat_filtered(const TreeView &t, const AccumVie
 	float wn = 0.0f;
 	uint32_t tree = 0;
 	bool second = false; // the emitter pair is still to come
+	KdWalk kw;           // (kOverlap) the KD leaves other than L
+	kw.active = false;
+	float w0 = 0.0f, wn0 = 0.0f; // (kOverlap) the pairs' whole weights
 	if (valid) {
-		const KdPlan kp = plan_kd(t, planes, f, index, x, y, z);
-		tree = kp.tree;
-		head = load_head_s(t.head, tree);
-		const JumpPre pre_p = jump_prefetch(t.jump, tree, dx, dy, in_unit_square(dx, dy));
-		const JumpPre pre_n = jump_prefetch(t.jump, tree, nx, ny, store_nee != 0 && in_unit_square(nx, ny));
 		const float w = wo_pdf > 0.0f ? radiance / wo_pdf : 0.0f;   // quadtree.py:451
 		wn = wo_pdf > 0.0f ? nee_lum / wo_pdf : 0.0f;               // quadtree.py:462
-		LeafCursor cp = leaf_cursor_pre(head, dx, dy, true, pre_p);
-		cn = leaf_cursor_pre(head, nx, ny, store_nee != 0, pre_n);
-		quad_find_leaf_slots2(t.rec, cp, cn);
-		// a counted record whose direction reaches no leaf (outside the unit square): fallback counter
-		if (kp.inside && !cp.found) atomicAdd(a.leaf_count + tree, 1ull);
-		box_begin(b, t, tree, cp, w, kp.inside ? 1 : 0, f.directional != 0);
-		second = store_nee != 0 && cn.found;
+		if (!kOverlap) {
+			const KdPlan kp = plan_kd(t, planes, f, index, x, y, z);
+			tree = kp.tree;
+			open_tree(t, a, f, store_nee, tree, kp.inside, dx, dy, nx, ny, w, b, head, cn, second);
+		} else {
+			const bool inside = inside_root(t, x, y, z);
+			KdNode leaf;
+			uint32_t lv;
+			const uint32_t L = kd_descend_grid(t, planes, x, y, z, inside, leaf, lv);
+			tree = leaf.tree; // outside the bbox: node 0's (stale) tree (kdtree.py:224)
+			w0 = w; wn0 = wn;
+			float wl = w;
+			if (inside && kd_walk_begin(kw, t, f, L, x, y, z)) { // L's own share; its count does not depend on it
+				float s;
+				const bool part = kd_share(kw, f, L, s);
+				wl = part ? w0 * s : 0.0f;
+				wn = part ? wn0 * s : 0.0f;
+				// (a record neither direction of which reaches a leaf deposits nothing in any KD leaf)
+				kw.active = in_unit_square(dx, dy) || (store_nee != 0 && in_unit_square(nx, ny));
+			}
+			open_tree(t, a, f, store_nee, tree, inside, dx, dy, nx, ny, wl, b, head, cn, second);
+		}
 	}
 	for (;;) {
 		if (!b.active && second) {
 			box_begin(b, t, tree, cn, wn, 0, f.directional != 0);
 			second = false;
 		}
-		if (__ballot(b.active) == 0ull) break;
+		if (kOverlap && !b.active && kw.active) { // (second is false here: a waiting emitter pair has just made b active)
+			float s;
+			if (kd_walk_next(kw, t, f, tree, s)) {
+				wn = wn0 * s;
+				open_tree(t, a, f, store_nee, tree, false, dx, dy, nx, ny, w0 * s, b, head, cn, second);
+			}
+		}
+		// (second: a leaf just opened for the emitter pair alone)
+		if (__ballot(b.active || (kOverlap && (second || kw.active))) == 0ull) break;
 		const Part s = box_next(b, t, head);
 		const bool has = s.idx != kNoPart;
 		const unsigned long long m = __ballot(has);
@@ -340,6 +505,7 @@ __device__ __forceinline__ void splat_filtered(const TreeView &t, const AccumVie
 	}
 }
 
+template <bool kOverlap>
 __global__ __launch_bounds__(kFBlock) void k_filter_splat(TreeView t, AccumView a, pg_filter_args f, int store_nee, uint64_t m,
                                                           const float *__restrict__ pos, const float *__restrict__ dir,
                                                           const float *__restrict__ radiance,
@@ -365,11 +531,12 @@ __global__ __launch_bounds__(kFBlock) void k_filter_splat(TreeView t, AccumView 
 		rad = radiance[i]; wp = wo_pdf[i];
 		if (store_nee) { nx = dir_nee[i]; ny = dir_nee[m + i]; nl = nee_lum[i]; }
 	}
-	splat_filtered(t, a, s_planes, f, store_nee, valid, (uint32_t)i, x, y, z, dx, dy, rad, wp, nx, ny, nl, s_q, len, s_val, s_ptr);
+	splat_filtered<kOverlap>(t, a, s_planes, f, store_nee, valid, (uint32_t)i, x, y, z, dx, dy, rad, wp, nx, ny, nl, s_q, len, s_val, s_ptr);
 	queue_drain(a, s_q, len, s_val, s_ptr);
 }
 
 // the dense record buffer (k_process_and_splat's loop over the tiles, pg_kernels_splat.hip); record number = dense slot g
+template <bool kOverlap>
 __global__ __launch_bounds__(kFBlock) void k_filter_process_and_splat(TreeView t, AccumView a, pg_filter_args f, int store_nee,
                                                                       uint64_t num_rays, int32_t max_depth,
                                                                       const float *__restrict__ l_final, pg_dense_records r)
@@ -393,7 +560,7 @@ __global__ __launch_bounds__(kFBlock) void k_filter_process_and_splat(TreeView t
 			dx = r.direction[g]; dy = r.direction[S + g];
 			nx = r.direction_nee[g]; ny = r.direction_nee[S + g];
 		}
-		splat_filtered(t, a, s_planes, f, store_nee, keep, (uint32_t)g, x, y, z, dx, dy, radiance, wp, nx, ny, nee_lum, s_q, len, s_val,
+		splat_filtered<kOverlap>(t, a, s_planes, f, store_nee, keep, (uint32_t)g, x, y, z, dx, dy, radiance, wp, nx, ny, nee_lum, s_q, len, s_val,
 		               s_ptr);
 	}
 	queue_drain(a, s_q, len, s_val, s_ptr);
@@ -440,6 +607,7 @@ __device__ __forceinline__ uint64_t list_entries(uint64_t num_rays, int32_t max_
 
 // The list through the filters: every kept entry is the record pg_process_and_splat would have found in dense slot
 // ray * max_depth + depth of the reference's buffer, and that slot (modulo 2^32) is its record number for the jitter.
+template <bool kOverlap>
 __global__ __launch_bounds__(kFBlock) void k_filter_splat_list(TreeView t, AccumView a, pg_filter_args f, int store_nee, uint64_t num_rays,
                                                                int32_t max_depth, const uint4 *__restrict__ l_final_q, pg_list_records r,
                                                                pg_list_geometry geo, const uint32_t *__restrict__ live_count)
@@ -466,7 +634,7 @@ __global__ __launch_bounds__(kFBlock) void k_filter_splat_list(TreeView t, Accum
 			nx = geo.direction_nee[g]; ny = geo.direction_nee[S + g];
 			index = (uint32_t)((uint64_t)ray * (uint64_t)max_depth + geo.depth[g]);
 		}
-		splat_filtered(t, a, s_planes, f, store_nee, keep, index, x, y, z, dx, dy, radiance, wp, nx, ny, nee_lum, s_q, len, s_val, s_ptr);
+		splat_filtered<kOverlap>(t, a, s_planes, f, store_nee, keep, index, x, y, z, dx, dy, radiance, wp, nx, ny, nee_lum, s_q, len, s_val, s_ptr);
 	}
 	queue_drain(a, s_q, len, s_val, s_ptr);
 }
@@ -509,6 +677,9 @@ __global__ __launch_bounds__(kFBlock) void k_export_list_records(uint64_t num_ra
 	}
 }
 
+// the kernels of PG_SPATIAL_OVERLAP_BOX are instances of their own: those of the other filters carry nothing of its walk
+static inline bool overlap(const pg_filter_args &f) { return f.spatial == PG_SPATIAL_OVERLAP_BOX; }
+
 static inline dim3 grid_for_f(uint64_t n) { return dim3((unsigned)((n + kFBlock - 1) / kFBlock)); }
 
 // a fixed grid striding over the tiles (the list's length is known only on the device)
@@ -524,8 +695,9 @@ void launch_splat_list_filtered(const TreeView &t, const AccumView &a, const pg_
 {
 	const uint64_t S = num_rays * (uint64_t)max_depth;
 	if (S == 0) return;
-	hipLaunchKernelGGL(k_filter_splat_list, strided_grid_f(S, n_cus), dim3(kFBlock), 0, s, t, a, f, store_nee, num_rays, max_depth,
-	                   l_final_q, rec, geo, live_count);
+	const auto kernel = overlap(f) ? k_filter_splat_list<true> : k_filter_splat_list<false>;
+	hipLaunchKernelGGL(kernel, strided_grid_f(S, n_cus), dim3(kFBlock), 0, s, t, a, f, store_nee, num_rays, max_depth, l_final_q, rec, geo,
+	                   live_count);
 }
 
 void launch_export_list_records(uint64_t num_rays, int32_t max_depth, const uint4 *l_final_q, const pg_list_records &rec,
@@ -543,7 +715,8 @@ void launch_splat_filtered(const TreeView &t, const AccumView &a, const pg_filte
                            const pg_records &rec, const uint32_t *d_count, hipStream_t s)
 {
 	if (m == 0) return;
-	hipLaunchKernelGGL(k_filter_splat, grid_for_f(m), dim3(kFBlock), 0, s, t, a, f, store_nee, m, rec.position, rec.direction,
+	const auto kernel = overlap(f) ? k_filter_splat<true> : k_filter_splat<false>;
+	hipLaunchKernelGGL(kernel, grid_for_f(m), dim3(kFBlock), 0, s, t, a, f, store_nee, m, rec.position, rec.direction,
 	                   rec.radiance, rec.wo_pdf, rec.direction_nee, rec.radiance_nee_lum, d_count);
 }
 
@@ -554,7 +727,8 @@ void launch_process_and_splat_filtered(const TreeView &t, const AccumView &a, co
 	const uint64_t S = num_rays * (uint64_t)max_depth;
 	if (S == 0) return;
 	const uint64_t tiles = (S + kFBlock - 1) / kFBlock, cap = (uint64_t)(n_cus > 0 ? n_cus : 256) * 64u;
-	hipLaunchKernelGGL(k_filter_process_and_splat, dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(kFBlock), 0, s, t, a, f,
+	const auto kernel = overlap(f) ? k_filter_process_and_splat<true> : k_filter_process_and_splat<false>;
+	hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(kFBlock), 0, s, t, a, f,
 	                   store_nee, num_rays, max_depth, l_final, rec);
 }
 

@@ -762,7 +762,7 @@ static int check_pass(pg_context *ctx, const pg_pass_params *prm, const float *L
 	// -- unless the scene was set with pg_render_record_geometry on: then the list keeps them)
 	if (!ctx->is_final && ctx->filtered() && !ctx->render->scene.geometry)
 		return fail(ctx, PG_ERR_INVALID, std::string("pg_render_pass: a recording pass cannot apply the splat filter set by pg_set_splat_filter (spatial ") +
-		                                     (ctx->filter_spatial ? "stochastic box" : "nearest") + ", directional " +
+		                                     (ctx->filter_spatial == PG_SPATIAL_OVERLAP_BOX ? "overlap box" : ctx->filter_spatial ? "stochastic box" : "nearest") + ", directional " +
 		                                     (ctx->filter_directional ? "box" : "nearest") + "); reset it to nearest / nearest, record through pg_splat / pg_process_and_splat, or set the scene with pg_render_record_geometry on");
 	PG_HIP(ctx, hipSetDevice(ctx->device));
 	const pg_camera &cam = ctx->render->scene.cam;

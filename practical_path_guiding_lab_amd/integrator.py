@@ -63,8 +63,8 @@ class PathGuidingIntegrator:
     def setSplatFilter(self, spatial: str = "nearest", directional: str = "nearest", seed: int = 0) -> None:
         """Not in the reference: the training filters (SDTree.setSplatFilter) for the recording passes of sample().  The
         choice is kept here and set before every recording pass with the seed (seed + the pass's sampler seed) mod 2^32
-        (WavefrontScene.trace_pass), so that two passes do not jitter alike; a filter other than nearest / nearest needs
-        a WavefrontScene(record_geometry=True), else sample() raises."""
+        (WavefrontScene.trace_pass), so that two passes do not jitter alike ("overlap" uses no seed); a filter other than
+        nearest / nearest needs a WavefrontScene(record_geometry=True), else sample() raises."""
         if spatial not in SDTree._SPATIAL:
             raise ValueError(f"spatial filter must be one of {sorted(SDTree._SPATIAL)}, got {spatial!r}")
         if directional not in SDTree._DIRECTIONAL:

@@ -98,12 +98,14 @@ class SDTree:
     def setIteration(self, iteration: int, isFinalIter: bool = False):
         self._ck(self._lib.pg_set_iteration(self._h, int(iteration), int(bool(isFinalIter))))
 
-    _SPATIAL = {"nearest": N.PG_SPATIAL_NEAREST, "stochastic": N.PG_SPATIAL_STOCHASTIC_BOX}
+    _SPATIAL = {"nearest": N.PG_SPATIAL_NEAREST, "stochastic": N.PG_SPATIAL_STOCHASTIC_BOX, "overlap": N.PG_SPATIAL_OVERLAP_BOX}
     _DIRECTIONAL = {"nearest": N.PG_DIRECTIONAL_NEAREST, "box": N.PG_DIRECTIONAL_BOX}
 
     def setSplatFilter(self, spatial: str = "nearest", directional: str = "nearest", seed: int = 0):
         """The training filters of the record boundary (pg_set_splat_filter; not in the reference): spatial "nearest" |
-        "stochastic" (the position is jittered by the extent of its KD leaf), directional "nearest" | "box" (the energy is
+        "stochastic" (the position is jittered by the extent of its KD leaf) | "overlap" (the deterministic box the jitter
+        estimates: the record is shared between the KD leaves a leaf-sized box around its position overlaps, by volume; no
+        seed, exact integer sums whatever the order, batching or sharding), directional "nearest" | "box" (the energy is
         shared between the quadtree leaves a leaf-sized square around the direction overlaps).  addDataPropagate,
         processAndSplat and prepareProcessAndSplat follow it; setup() resets it to nearest / nearest.  While a filter is
         set, a recording render pass raises (the renderer's record list cannot be filtered) unless the scene records the
