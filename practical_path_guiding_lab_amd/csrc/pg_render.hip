@@ -6,73 +6,61 @@
 // (quads, twosided diffuse BSDFs, a one-sided area emitter, perspective camera) and, in the
 // kGeneral instantiations, of scenes/veach-mis (spheres, several emitters, Beckmann rough conductors).
 //
-// One kernel per bounce over the live rays; the SD-tree queries are the same device functions the
-// stand-alone query kernels use, so a bounce costs one KD descent and at most two quadtree descents
-// per live lane and no intermediate wavefront buffers.  The first bounce generates its camera rays
+// One kernel per bounce over the live rays.  The bounce itself is not written here: bounce_lane strings together the stages
+// of pg_render_stages.hpp (camera_ray, stage_a1, stage_a2, stage_guide, store_slots, stage_b), the same functions the kernels
+// of mesh scenes are made of (pg_render_wave.hip), at feature levels 0 and 1 -- so a bounce costs one KD descent and at most
+// two quadtree descents per live lane, none for an emitter sample whose BSDF value is zero, and no intermediate wavefront
+// buffers.  What is this file's own is where a path lives between bounces.  The first bounce generates its camera rays
 // itself, every bounce appends its survivors to the live-ray list of the next one (one atomic per
 // workgroup), and a path carries 57 B of state between bounces.  Path-vertex records go to a dense
 // slot buffer (the reference's :318, stored depth-major here so that a wavefront's stores coalesce)
 // that pg_process_and_splat consumes after the last bounce (:388-395).
 //
 // Arithmetic mirrors oracle/pg_oracle_render.c operation by operation (fp32, no contraction), so
-// radiance, records and therefore the refined trees are bit-identical to the CPU restatement.
-// (The microfacet helpers are inlined here too since round 5: kept out of line, every call cost the level-1 kernels a 32-byte
-// stack frame in scratch memory; inlined, k_bounce<*, 1> is 87 / 89 registers at five waves per SIMD with no scratch at
-// all -- veach-mis 2.33 -> 2.32 ms per pass, profiles/r05/ab_fused_kernel_helpers_inlined.txt.)
-#include "pg_render_dev.hpp"
+// radiance, records and therefore the refined trees are bit-identical to the CPU restatement -- the oracle is the independent
+// statement of the bounce; the device has one.
+// (The microfacet helpers are inlined since round 5: kept out of line, every call cost the level-1 kernels a 32-byte
+// stack frame in scratch memory -- profiles/r05/ab_fused_kernel_helpers_inlined.txt.  Registers of the kernels as they are
+// now: profiles/fused_from_stages.)
+#include "pg_render_stages.hpp"
 #include "pg_scene_state.hpp"
 
 namespace pg {
 
 
-// One loop iteration of :179-381 for one live lane; returns whether the path continues.
-// kFirst: the camera ray is generated here (mi.render's sensor.sample_ray_differential: one 2-D
-// jitter draw per sample, box reconstruction) instead of being read back from a generate kernel.
-// kGeneral: the scene has spheres or rough conductors; false compiles the all-diffuse quad scene only.
-// stash (k_bounce; nullptr in the tail kernel): column threadIdx.x of a [kBounceStash][kRBlock] array in LDS, where values
-// that only the code BEHIND an SD-tree walk reads wait while the walk runs -- this kernel leaves the LDS almost empty, and
-// the walks are where its registers peak (tools/vgpr_liveness.py).
-constexpr int kBounceStash = 17;
+// One loop iteration of :179-381 for one live lane, assembled from the stages of pg_render_stages.hpp in the sequence of
+// k_wave_tail's loop body; returns whether the path continues.  The fused kernels' own: the state planes (ray_d, thr, L,
+// prev_p, prev_pdf, prev_quad, the sampler) indexed by lane, the ray origin made again from the previous vertex, ray casting
+// without a BVH (feature levels 0 and 1 have no meshes), the radiance kept up to date in a.L.
+// kFirst: the camera ray is generated here instead of being read back from a generate kernel.
+// kGeneral: the scene has spheres or rough conductors (level 1); 0 compiles the all-diffuse quad scene only.
+// stash (k_bounce; nullptr in the tail kernel): column threadIdx.x of a [kBounceStash][kRBlock] array in LDS, where what only
+// stage_b reads waits while the SD-tree walks run -- this kernel leaves the LDS almost empty, and the walks are where its
+// registers peak (tools/vgpr_liveness.py), as k_wave_shade parks its values around its walks.
+constexpr int kBounceStash = 21;
 typedef __attribute__((address_space(3))) float LdsFloat;
 template <bool kFirst, int kGeneral, bool kStash = false>
-__device__ __forceinline__ bool bounce_lane(const RenderArgs &a, const uint4 *s_kd, const uint64_t lane,
+__device__ __forceinline__ bool bounce_lane(const RenderArgs &a, const float *s_planes, const uint64_t lane,
                                             const uint64_t rec_slot, const uint32_t depth, LdsFloat *stash = nullptr)
 {
+	static_assert(kGeneral < 2, "mesh scenes run the split pipeline of pg_render_wave.hip");
 	const uint64_t N = a.n_lanes;
-	const int D = a.max_depth;
-	const float f = a.frac;
 	const Shapes &sh = a.shapes;
 	Pcg32 rng;
-	v3 ray_o, ray_d, thr, L, prev_p;
-	float prev_bsdf_pdf;
-	const bool prev_delta = kFirst; // no delta lobes in these scenes (feature levels 0 and 1): only the camera "vertex" counts as one
-	const float ior = 1.0f;         // every BSDF of these scenes has eta 1: the running product stays exactly 1
-	static_assert(kGeneral < 2, "mesh scenes run the split pipeline of pg_render_wave.hip");
+	v3 ray_o, ray_d, thr, prev_p;
+	float prev_pdf;
 	if (kFirst) {
-		const uint64_t pixel = global_pixel(a, lane / (uint64_t)a.spp);
-		rng = lane_stream(a.seed, a.spp, a.batched, pixel, (uint32_t)(lane % (uint64_t)a.spp));
-		const int W = a.cam.width, H = a.cam.height;
-		const float px = (float)(pixel % (uint64_t)W), py = (float)(pixel / (uint64_t)W);
-		const float jx = rng.next_f32(), jy = rng.next_f32();
-		const float tan_y = a.cam.tan_half_fov_x / ((float)W / (float)H);
-		const float cx = (1.0f - 2.0f * ((px + jx) / (float)W)) * a.cam.tan_half_fov_x;
-		const float cy = (1.0f - 2.0f * ((py + jy) / (float)H)) * tan_y;
-		const float len = __builtin_sqrtf((cx * cx + cy * cy) + 1.0f);
-		const v3 dc = V(cx / len, cy / len, 1.0f / len);
-		ray_d = vadd(vadd(vscale(ld3(a.cam.axis_x), dc.x), vscale(ld3(a.cam.axis_y), dc.y)), vscale(ld3(a.cam.axis_z), dc.z));
-		ray_o = ld3(a.cam.origin);
+		camera_ray(a, lane, rng, ray_o, ray_d);
 		thr = V(1, 1, 1);
-		L = V(0, 0, 0);
 		prev_p = V(0, 0, 0);
-		prev_bsdf_pdf = 1.0f;
+		prev_pdf = 1.0f;
 	} else {
 		rng.state = a.rng_state[lane];
 		rng.inc = a.rng_inc[lane];
 		ray_d = V(a.ray_d[lane], a.ray_d[N + lane], a.ray_d[2 * N + lane]);
 		thr = V(a.thr[lane], a.thr[N + lane], a.thr[2 * N + lane]);
-		L = V(a.L[lane], a.L[N + lane], a.L[2 * N + lane]);
 		prev_p = V(a.prev_p[lane], a.prev_p[N + lane], a.prev_p[2 * N + lane]);
-		prev_bsdf_pdf = a.prev_pdf[lane];
+		prev_pdf = a.prev_pdf[lane];
 		// :352 spawn_ray of the previous vertex: the same three operations that produced the origin
 		const uint32_t pq = a.prev_quad[lane];
 		const v3 pn = normal_at<kGeneral>(sh, (int)pq, prev_p);
@@ -80,232 +68,70 @@ __device__ __forceinline__ bool bounce_lane(const RenderArgs &a, const uint4 *s_
 		if (dot3(pn, ray_d) < 0.0f) mag = -mag;
 		ray_o = vadd(prev_p, vscale(pn, mag));
 	}
-
-	// ---- :185 ray_intersect ----
-	float t_hit;
-	const int q = intersect<kGeneral>(sh, ray_o, ray_d, __builtin_huge_valf(), t_hit);
-	const bool valid = q >= 0;
-	Surface sf;
-	sf.p = V(0, 0, 0); sf.n = V(0, 0, 1); sf.ng = V(0, 0, 1); sf.radiance = V(0, 0, 0); sf.is_em = false;
-	sf.m.type = 0; sf.m.refl = V(0, 0, 0); sf.m.M = nullptr; sf.m.one_sided = false;
-	if (valid) sf = surface_at<kGeneral>(sh, a.mats, q, ray_o, ray_d, t_hit);
-	const v3 p = sf.p, n = sf.n;
-	const Material &mt = sf.m;
-	const Frame fr = make_frame(n);
-	const v3 wi = to_local(fr, V(-ray_d.x, -ray_d.y, -ray_d.z));
-	const bool is_em = valid && sf.is_em;
-	const float inv_em_count = 1.0f / (float)a.n_emitters; // only used when an emitter was hit
-	// ---- :189-200 direct emission ----
-	const v3 em_radiance = (is_em && wi.z > 0.0f) ? sf.radiance : V(0, 0, 0);
-	float emitter_pdf = 0.0f;
-	if (is_em && !prev_delta) emitter_pdf = emitter_hit_pdf<kGeneral>(sh, q, prev_p, p, n, inv_em_count);
-	const float mis = mis_weight(prev_bsdf_pdf, emitter_pdf);
-	const v3 Le = vmul(vscale(thr, mis), em_radiance);
-	// ---- :207-220 emitter sampling ----
-	bool active_next = (depth + 1 < (uint32_t)D) && valid;
-	bool active_em = active_next; // :210 BSDFFlags.Smooth: every BSDF of these scenes has a non-delta lobe
-	const float e1 = rng.next_f32(), e2 = rng.next_f32(); // :214, unmasked
-	v3 ds_d = V(0, 0, 0), em_weight = V(0, 0, 0);
-	float ds_pdf = 0.0f;
-	bool ds_delta = false;
-	if (active_em)
-		sample_emitter<kGeneral>(sh, a.dir_lights, a.emitters, a.n_emitters, p, sf.ng, e1, e2, ds_d, ds_pdf, em_weight, ds_delta);
-	active_em = active_em && (ds_pdf != 0.0f); // :216
-	const v3 wo_em = to_local(fr, ds_d);
-	v3 bsdf_value_em;
-	float bsdf_pdf_em;
-	bsdf_eval_pdf<kGeneral>(mt, wi, wo_em, active_em, bsdf_value_em, bsdf_pdf_em);
-	// ---- :223-256 NEE MIS against the mixture pdf ----
-	const bool active_sd_em = active_em && a.guided;
-	const float pdf_diffuse = 1.0f; // :222-241
-	TreeHead head = {kNoRecord, 0.0f};
-	uint32_t tree_id = 0;
-	bool tree_known = false;
-	float sdtree_pdf_em = 1.0f;
-	uint32_t lv;
-	unsigned c_kd = 0, c_kdq = 0, c_q = 0, c_qq = 0; // descent statistics for the byte model
-	const bool do_record = a.record && valid;
-	// dirToCanonical of the emitter direction feeds the NEE pdf query (:244) and the record (:338):
-	// one evaluation serves both
-	float nee_cx = 0.0f, nee_cy = 0.0f;
-	// a recorded vertex names its accumulators in sdTree_current (pg_list_records): the leaves the walks of sdTree_prev
-	// below end in (same topology, :582), or -- unguided iterations, the last vertex of a path -- walks made for them
-	uint32_t slot_path = kSlotNone, slot_nee = kSlotNone, tree_flags = 0u;
-	const bool nee_slot_wanted = do_record && a.store_nee && active_em;
-	if (active_sd_em || (do_record && a.store_nee)) dir_to_canonical(ds_d.x, ds_d.y, ds_d.z, nee_cx, nee_cy);
-	if (kStash) { // (what only the NEE term and the record read, behind the first walks)
+	HitRec h;
+	h.u = 0.0f; h.v = 0.0f;
+	h.prim = intersect<kGeneral>(sh, ray_o, ray_d, __builtin_huge_valf(), h.t); // :185
+	StageA A;
+	// (no delta lobes at these levels: only the camera "vertex" counts as one)
+	stage_a1<kGeneral>(a, rng, ray_o, ray_d, thr, prev_p, prev_pdf, kFirst, h, depth, A);
+	if (kStash) { // what only stage_b reads of stage_a1's results and of the path's state: parked ahead of the shadow ray and the BSDF sample
 		stash[0 * kRBlock] = thr.x; stash[1 * kRBlock] = thr.y; stash[2 * kRBlock] = thr.z;
-		stash[3 * kRBlock] = L.x; stash[4 * kRBlock] = L.y; stash[5 * kRBlock] = L.z;
-		stash[6 * kRBlock] = Le.x; stash[7 * kRBlock] = Le.y; stash[8 * kRBlock] = Le.z;
-		stash[9 * kRBlock] = bsdf_value_em.x; stash[10 * kRBlock] = bsdf_value_em.y; stash[11 * kRBlock] = bsdf_value_em.z;
-		stash[12 * kRBlock] = em_weight.x; stash[13 * kRBlock] = em_weight.y; stash[14 * kRBlock] = em_weight.z;
-		stash[15 * kRBlock] = bsdf_pdf_em; stash[16 * kRBlock] = ds_pdf;
+		stash[3 * kRBlock] = A.Le.x; stash[4 * kRBlock] = A.Le.y; stash[5 * kRBlock] = A.Le.z;
+		stash[6 * kRBlock] = A.bv_em.x; stash[7 * kRBlock] = A.bv_em.y; stash[8 * kRBlock] = A.bv_em.z;
+		stash[9 * kRBlock] = A.em_w.x; stash[10 * kRBlock] = A.em_w.y; stash[11 * kRBlock] = A.em_w.z;
+		stash[12 * kRBlock] = A.bp_em; stash[13 * kRBlock] = A.ds_pdf;
 	}
-	if (active_sd_em || do_record) {
-		KdNode leaf;
-		const bool inside = inside_root(a.tree, p.x, p.y, p.z);
-		kd_descend_grid(a.tree, reinterpret_cast<const float *>(s_kd), p.x, p.y, p.z, inside, leaf, lv);
-		c_kd += lv; ++c_kdq;
-		const uint2 hv = gather8(a.tree.head + leaf.tree);
-		head.root_rec = hv.x;
-		head.root_irr = __uint_as_float(hv.y);
-		tree_known = true;
-		tree_id = leaf.tree;
-		tree_flags = tree_id | (inside ? 0x80000000u : 0u);
+	bool occluded = false;
+	if (A.flags & F_NEED_SHADOW) { // :213 test_visibility
+		float th;
+		occluded = intersect<kGeneral, true>(sh, A.sh_o, A.sh_d, A.sh_tmax, th) >= 0;
 	}
-	if (active_sd_em) {
-		sdtree_pdf_em = quad_pdf_t<true>(a.tree.rec, a.tree.jump, tree_id, head, nee_cx, nee_cy, lv, slot_nee);
-		c_q += lv; ++c_qq;
+	stage_a2<kGeneral>(a, rng, A);
+	if (kStash) { // ... and of stage_a2's, ahead of the SD-tree walks
+		stash[14 * kRBlock] = A.bsdf_w.x; stash[15 * kRBlock] = A.bsdf_w.y; stash[16 * kRBlock] = A.bsdf_w.z; stash[17 * kRBlock] = A.bsdf_pdf;
+		stash[18 * kRBlock] = A.wi.x; stash[19 * kRBlock] = A.wi.y; stash[20 * kRBlock] = A.wi.z;
 	}
-	v3 Le_ = Le, bsdf_value_em_ = bsdf_value_em, em_weight_ = em_weight;
-	float bsdf_pdf_em_ = bsdf_pdf_em, ds_pdf_ = ds_pdf;
-	if (kStash) {
-		thr = V(stash[0 * kRBlock], stash[1 * kRBlock], stash[2 * kRBlock]);
-		L = V(stash[3 * kRBlock], stash[4 * kRBlock], stash[5 * kRBlock]);
-		Le_ = V(stash[6 * kRBlock], stash[7 * kRBlock], stash[8 * kRBlock]);
-		bsdf_value_em_ = V(stash[9 * kRBlock], stash[10 * kRBlock], stash[11 * kRBlock]);
-		em_weight_ = V(stash[12 * kRBlock], stash[13 * kRBlock], stash[14 * kRBlock]);
-		bsdf_pdf_em_ = stash[15 * kRBlock]; ds_pdf_ = stash[16 * kRBlock];
-	}
-	float surface_pdf_em = f * bsdf_pdf_em_ + ((1.0f - f) * sdtree_pdf_em) * pdf_diffuse;
-	if (!a.guided) surface_pdf_em = bsdf_pdf_em_;
-	const float mis_em = mis_weight(ds_pdf_, surface_pdf_em); // :253 (no delta emitters in these scenes)
-	v3 Lr_dir = vmul(vmul(vscale(thr, mis_em), bsdf_value_em_), em_weight_);
-	L = vadd(L, vadd(Le_, Lr_dir)); // :261
-	if (kStash) { // (what only the record and the next bounce's state read, behind the second walks)
-		stash[0 * kRBlock] = thr.x; stash[1 * kRBlock] = thr.y; stash[2 * kRBlock] = thr.z;
-		stash[3 * kRBlock] = L.x; stash[4 * kRBlock] = L.y; stash[5 * kRBlock] = L.z;
-		stash[6 * kRBlock] = Lr_dir.x; stash[7 * kRBlock] = Lr_dir.y; stash[8 * kRBlock] = Lr_dir.z;
-	}
-	// ---- :272-311 next direction ----
-	float s1 = 0.0f, s2x = 0.0f, s2y = 0.0f;
-	if (active_next) { // next_1d (lobe choice: only the dielectric reads it), next_2d
-		rng.skip(); // (the lobe choice: only dielectrics read it)
-		s2x = rng.next_f32();
-		s2y = rng.next_f32();
-	}
-	v3 wo_local, bsdf_weight;
-	float bsdf_pdf, eta;
-	bool delta;
-	bsdf_sample<kGeneral>(mt, wi, s1, s2x, s2y, active_next, wo_local, bsdf_pdf, bsdf_weight, eta, delta);
-	v3 bsdf_value = vscale(bsdf_weight, bsdf_pdf);
-	float woPdf = bsdf_pdf;
-	v3 wo_world = to_world(fr, wo_local);
-	const bool do_mis = active_next && !delta && a.guided; // :283
-	bool pick_tree = false;
-	if (active_next) pick_tree = rng.next_f32() > f; // :286
-	const bool smp_tree = pick_tree && do_mis;
-	const bool bsdf_mis = do_mis && !smp_tree;
-	float sdtree_pdf = 1.0f;
-	if ((smp_tree || bsdf_mis) && !tree_known) {
-		KdNode leaf;
-		kd_descend_grid(a.tree, reinterpret_cast<const float *>(s_kd), p.x, p.y, p.z, inside_root(a.tree, p.x, p.y, p.z), leaf, lv);
-		c_kd += lv; ++c_kdq;
-		const uint2 hv = gather8(a.tree.head + leaf.tree);
-		head.root_rec = hv.x;
-		head.root_irr = __uint_as_float(hv.y);
-		tree_id = leaf.tree;
-	}
-	if (smp_tree) { // :301-304
-		float dx, dy, dz;
-		quad_sample_t<true>(a.tree.rec, a.tree.jump, tree_id, head, rng, dx, dy, dz, sdtree_pdf, lv, slot_path);
-		c_q += lv; ++c_qq;
-		wo_world = V(dx, dy, dz);
-		wo_local = to_local(fr, wo_world);
-		bsdf_eval_pdf<kGeneral>(mt, wi, wo_local, true, bsdf_value, bsdf_pdf);
-	}
-	// dirToCanonical of the continuation direction feeds the pdf query (:307) and the record (:327)
-	float wo_cx = 0.0f, wo_cy = 0.0f;
-	if (bsdf_mis || do_record) dir_to_canonical(wo_world.x, wo_world.y, wo_world.z, wo_cx, wo_cy);
-	if (bsdf_mis) { // :307
-		sdtree_pdf = quad_pdf_t<true>(a.tree.rec, a.tree.jump, tree_id, head, wo_cx, wo_cy, lv, slot_path);
-		c_q += lv; ++c_qq;
-	}
-	{ // the leaves no query has walked to: the two walks of QuadTree.addDataPropagate (quadtree.py:443-464), in lock step
-		const bool walk_path = do_record && !smp_tree && !bsdf_mis, walk_nee = nee_slot_wanted && !active_sd_em;
-		if (walk_path || walk_nee) {
-			LeafCursor cp = leaf_cursor(a.tree.jump, tree_id, head, wo_cx, wo_cy, walk_path);
-			LeafCursor cn = leaf_cursor(a.tree.jump, tree_id, head, nee_cx, nee_cy, walk_nee);
-			quad_find_leaf_slots2(a.tree.rec, cp, cn);
-			if (walk_path) { slot_path = cursor_slot(cp); c_q += cp.levels; ++c_qq; }
-			if (walk_nee) { slot_nee = cursor_slot(cn); c_q += cn.levels; ++c_qq; }
-		}
-	}
-	if (a.dc && c_kdq) { // instrumented passes only (pg_enable_depth_counters)
-		atomicAdd(&a.dc->kd_levels, (unsigned long long)stat_levels(c_kd)); // (c_kd, c_q: sums of statistics words, pg_descent.hpp)
-		atomicAdd(&a.dc->kd_queries, (unsigned long long)c_kdq);
-		atomicAdd(&a.dc->quad_levels, (unsigned long long)stat_levels(c_q));
-		atomicAdd(&a.dc->quad_queries, (unsigned long long)c_qq);
-		atomicAdd(&a.dc->layout_bytes, (unsigned long long)(stat_bytes(c_kd) + stat_bytes(c_q)));
-	}
-	if (kStash) {
-		thr = V(stash[0 * kRBlock], stash[1 * kRBlock], stash[2 * kRBlock]);
-		L = V(stash[3 * kRBlock], stash[4 * kRBlock], stash[5 * kRBlock]);
-		Lr_dir = V(stash[6 * kRBlock], stash[7 * kRBlock], stash[8 * kRBlock]);
-	}
-	if (do_mis) { // :310-311
-		woPdf = f * bsdf_pdf + (1.0f - f) * sdtree_pdf;
-		bsdf_weight = vdivs(bsdf_value, woPdf);
-		// deliberate deviation: 0/0 when a zero-energy tree proposes a direction below
-		// the surface; the reference's throughput turns NaN there, here the path simply ends
-		if (!(woPdf > 0.0f)) bsdf_weight = V(0, 0, 0);
-	}
-	// ---- :318-346 record ----
-	// The reference's slot is ray*max_depth + depth (:318), a stride-max_depth scatter into a buffer
-	// that is mostly empty at the deeper bounces.  The library's own buffer is a list instead: this
-	// launch's thread t owns entry rec_slot = (records of the earlier bounces) + t, so a wavefront's
-	// stores coalesce and the splat visits no empty tail; ray_of names the path (k_splat_list looks its
-	// final radiance up, :440), kNoRay marks a path that left the scene here.  An entry holds what
-	// processPathData (:434-453) needs and the accumulators found above (pg_list_records).
-	if (a.record) a.ray_of[rec_slot] = valid ? (uint32_t)lane : 0xffffffffu;
-	if (do_record) {
-		const uint64_t S = N * (uint64_t)D;
-		const uint64_t g = rec_slot;
-		a.r_bsdf[g] = bsdf_weight.x; a.r_bsdf[S + g] = bsdf_weight.y; a.r_bsdf[2 * S + g] = bsdf_weight.z;
-		a.r_tb[g] = thr.x; a.r_tb[S + g] = thr.y; a.r_tb[2 * S + g] = thr.z;
-		a.r_tr[g] = L.x; a.r_tr[S + g] = L.y; a.r_tr[2 * S + g] = L.z;
-		float nee_lum = 0.0f;
-		if (a.store_nee) { // :336, and the NaN scrub + luminance of :467, 471 (the only use of the three channels)
-			v3 rn = vdiv(Lr_dir, thr);
-			if (rn.x != rn.x) rn.x = 0.0f;
-			if (rn.y != rn.y) rn.y = 0.0f;
-			if (rn.z != rn.z) rn.z = 0.0f;
-			nee_lum = luminance(rn.x, rn.y, rn.z);
-		}
-		a.r_nee[g] = nee_lum;
-		a.r_wp[g] = woPdf;
-		a.r_slot[g] = make_uint2(slot_path, slot_nee);
-		a.r_tree[g] = tree_flags;
-	}
-	// ---- :352-381 advance ----
-	// ior (:357): without a dielectric every sampled direction has eta = 1, the running product stays
-	// exactly 1 and is not carried; general scenes carry it
-	thr = vmul(thr, bsdf_weight);
-	const float tmax = max3(thr);
-	active_next = active_next && (tmax != 0.0f);
-	float rr_prob = tmax * (ior * ior);
-	if (!(rr_prob < 0.95f)) rr_prob = 0.95f;
-	const bool rr_active = depth >= (uint32_t)a.rr_depth;
-	const float rr = rng.next_f32(); // :377, unmasked
-	const bool rr_continue = rr < rr_prob;
-	active_next = active_next && (!rr_active || rr_continue);
-	// ---- state for the next bounce; a path that ends here leaves only its radiance ----
+	// ---- the addresses of the state for the next bounce, and the radiance so far ----
 	// (The addresses are made HERE, from the lane's number taken as a new value: left alone the compiler keeps the sixteen
 	// 64-bit addresses it formed for the loads at the top -- the same planes -- alive through the whole bounce, 32 of this
-	// kernel's 122 vector registers: tools/vgpr_liveness.py)
+	// kernel's 122 vector registers: tools/vgpr_liveness.py, DESIGN.md 5.7.  The radiance, which only stage_b reads, is not
+	// loaded at the top for the same reason.  Level 1 asks for it ahead of the SD-tree walks, which hide the load -- its
+	// registers peak in stage_a1; level 0, whose registers peak in the walks, behind them: profiles/fused_from_stages.)
 	uint32_t lane32 = (uint32_t)lane;
 	asm volatile("" : "+v"(lane32));
 	const uint64_t ln = lane32;
+	v3 L = V(0, 0, 0);
+	if (!kFirst && kGeneral) L = V(a.L[ln], a.L[N + ln], a.L[2 * N + ln]);
+	GuideOut g = guide_none(A.wo);
+	if (guide_has_work(a, A.flags)) stage_guide(a, s_planes, rng, A.p, A.ds_d, (A.flags & F_SMP_TREE) ? V(0, 0, 0) : A.wo, A.flags, g);
+	if (a.record && (A.flags & F_VALID)) store_slots(a, rec_slot, g);
+	if (kStash) {
+		thr = V(stash[0 * kRBlock], stash[1 * kRBlock], stash[2 * kRBlock]);
+		A.Le = V(stash[3 * kRBlock], stash[4 * kRBlock], stash[5 * kRBlock]);
+		A.bv_em = V(stash[6 * kRBlock], stash[7 * kRBlock], stash[8 * kRBlock]);
+		A.em_w = V(stash[9 * kRBlock], stash[10 * kRBlock], stash[11 * kRBlock]);
+		A.bp_em = stash[12 * kRBlock]; A.ds_pdf = stash[13 * kRBlock];
+		A.bsdf_w = V(stash[14 * kRBlock], stash[15 * kRBlock], stash[16 * kRBlock]); A.bsdf_pdf = stash[17 * kRBlock];
+		A.wi = V(stash[18 * kRBlock], stash[19 * kRBlock], stash[20 * kRBlock]);
+	}
+	if (!kFirst && !kGeneral) L = V(a.L[ln], a.L[N + ln], a.L[2 * N + ln]);
+	// (ior, :357: every BSDF of these levels has eta 1, the running product stays exactly 1 and is not carried; the next origin
+	// is made again from the vertex by the next bounce, above)
+	float ior = 1.0f;
+	bool delta;
+	v3 next_o;
+	const bool active_next = stage_b<kGeneral>(a, rng, thr, L, ior, A, g, occluded, ln, rec_slot, depth, next_o, ray_d, prev_pdf, delta);
+	// ---- state for the next bounce; a path that ends here leaves only its radiance ----
 	a.L[ln] = L.x; a.L[N + ln] = L.y; a.L[2 * N + ln] = L.z;
-	if (kFirst) a.hit0[ln] = valid ? 1 : 0;
+	if (kFirst) a.hit0[ln] = (A.flags & F_VALID) ? 1 : 0;
 	if (active_next) {
 		a.rng_state[ln] = rng.state;
 		if (kFirst) a.rng_inc[ln] = rng.inc;
-		a.ray_d[ln] = wo_world.x; a.ray_d[N + ln] = wo_world.y; a.ray_d[2 * N + ln] = wo_world.z;
+		a.ray_d[ln] = ray_d.x; a.ray_d[N + ln] = ray_d.y; a.ray_d[2 * N + ln] = ray_d.z;
 		a.thr[ln] = thr.x; a.thr[N + ln] = thr.y; a.thr[2 * N + ln] = thr.z;
-		a.prev_p[ln] = p.x; a.prev_p[N + ln] = p.y; a.prev_p[2 * N + ln] = p.z;
-		a.prev_pdf[ln] = woPdf;
-		a.prev_quad[ln] = (uint32_t)q;
+		a.prev_p[ln] = A.p.x; a.prev_p[N + ln] = A.p.y; a.prev_p[2 * N + ln] = A.p.z;
+		a.prev_pdf[ln] = prev_pdf;
+		a.prev_quad[ln] = (uint32_t)h.prim;
 	}
 	return active_next;
 }
@@ -321,7 +147,6 @@ template <bool kFirst, int kGeneral>
 __global__ __launch_bounds__(kRBlock) void k_bounce(RenderArgs a)
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
-	const uint4 *s_kd = reinterpret_cast<const uint4 *>(s_planes); // (bounce_lane's parameter: the staged table of whichever kind)
 	__shared__ uint32_t s_wave[kRBlock / 64];
 	__shared__ uint32_t s_base;
 	__shared__ float s_stash[kBounceStash][kRBlock];
@@ -332,7 +157,7 @@ __global__ __launch_bounds__(kRBlock) void k_bounce(RenderArgs a)
 	const uint64_t lane = alive ? (kFirst ? tid : (uint64_t)a.order_in[tid]) : 0;
 	const uint64_t rec_base = kFirst ? 0 : records_before(a);
 	bool cont = false;
-	if (alive) cont = bounce_lane<kFirst, kGeneral, true>(a, s_kd, lane, rec_base + tid, (uint32_t)a.bounce, (LdsFloat *)&s_stash[0][threadIdx.x]);
+	if (alive) cont = bounce_lane<kFirst, kGeneral, true>(a, s_planes, lane, rec_base + tid, (uint32_t)a.bounce, (LdsFloat *)&s_stash[0][threadIdx.x]);
 	if (a.last) return; // nothing survives the last bounce
 	const unsigned long long ballot = __ballot(cont);
 	const unsigned wl = threadIdx.x & 63u, wv = threadIdx.x >> 6;
@@ -362,7 +187,6 @@ template <int kGeneral>
 __global__ __launch_bounds__(kRBlock) void k_bounce_tail(RenderArgs a)
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
-	const uint4 *s_kd = reinterpret_cast<const uint4 *>(s_planes); // (bounce_lane's parameter: the staged table of whichever kind)
 	const uint64_t tid = (uint64_t)blockIdx.x * kRBlock + threadIdx.x;
 	const uint64_t live = (uint64_t)live_final(a, a.bounce - 1);
 	if (live > kTailPaths || (uint64_t)blockIdx.x * kRBlock >= live) return;
@@ -374,7 +198,7 @@ __global__ __launch_bounds__(kRBlock) void k_bounce_tail(RenderArgs a)
 	const uint64_t tail_base = rec_base + live; // behind the entries of bounce a.bounce
 	uint64_t slot = rec_base + tid;
 	for (int depth = a.bounce; depth < a.max_depth; ++depth) {
-		if (alive) alive = bounce_lane<false, kGeneral>(a, s_kd, lane, slot, (uint32_t)depth);
+		if (alive) alive = bounce_lane<false, kGeneral>(a, s_planes, lane, slot, (uint32_t)depth);
 		if (!tail_next_slot(a, depth, alive, tail_base, slot)) break;
 	}
 }

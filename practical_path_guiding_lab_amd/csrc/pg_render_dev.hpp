@@ -1010,7 +1010,7 @@ struct DirLights {
 // (zero when occluded, facing away, or from inside a sphere)
 // The emitter sample without its visibility test: returns the shadow ray (origin, unit direction, length to test) and
 // em_weight as if unoccluded; `need_shadow` says whether the caller has to trace it (and zero em_weight when it is
-// occluded) -- the split pipeline does that in a kernel of its own, sample_emitter below in place.
+// occluded): by a kernel of its own (k_wave_cast) or by an any-hit walk in place.
 template <int kGeneral>
 __device__ __forceinline__ void sample_emitter_ray(const Shapes &sh, const DirLights &dls, const int32_t *__restrict__ emitters,
                                                    int n_em, v3 p, v3 n, float e1, float e2, v3 &ds_d, float &ds_pdf,
@@ -1106,19 +1106,6 @@ __device__ __forceinline__ void sample_emitter_ray(const Shapes &sh, const DirLi
 		sh_o = so; sh_d = vdivs(sd, sdist); sh_tmax = sdist * (1.0f - kShadowEps);
 		em_weight = vscale(vdivs(radiance, pdf), count);
 	}
-}
-
-// ... with the visibility test made here (the fused kernels of pg_render.hip, feature levels 0 and 1: no BVH, no stack)
-template <int kGeneral>
-__device__ __forceinline__ void sample_emitter(const Shapes &sh, const DirLights &dls, const int32_t *__restrict__ emitters,
-                                               int n_em, v3 p, v3 n, float e1, float e2, v3 &ds_d, float &ds_pdf,
-                                               v3 &em_weight, bool &ds_delta)
-{
-	bool need_shadow;
-	v3 sh_o, sh_d;
-	float sh_tmax, th;
-	sample_emitter_ray<kGeneral>(sh, dls, emitters, n_em, p, n, e1, e2, ds_d, ds_pdf, em_weight, ds_delta, need_shadow, sh_o, sh_d, sh_tmax);
-	if (need_shadow && intersect<kGeneral, true>(sh, sh_o, sh_d, sh_tmax, th) >= 0) em_weight = V(0, 0, 0);
 }
 
 struct RenderArgs {
