@@ -685,6 +685,8 @@ typedef struct pg_kernel_timing {
 	 * kernels (pg_render_stages(0): the one, with shadow_ms = guide_ms = shade_b_ms = 0); tail_ms = the launch
 	 * that finishes the last paths. */
 	double trace_ms, shade_ms, shadow_ms, guide_ms, tail_ms;
+	/* trace_launches counts the bounces' closest-hit passes: pg_render_stages(0) walks the camera rays inside the first
+	 * shading launch, which is counted here and adds its whole time to shade_ms, none to trace_ms */
 	uint64_t trace_launches, guide_launches;
 	double shade_a_ms, shade_b_ms; /* the two shading kernels of shade_ms, each on its own */
 	double sort_ms;                /* pg_render_sort: the radix sorts of the sorted bounces */

@@ -238,6 +238,46 @@ __global__ __launch_bounds__(kRBlock) void k_finish(RenderArgs a, uint8_t *__res
 	}
 }
 
+// k_layout_L and k_finish in ONE streaming pass, for the passes whose spp divides the workgroup (finish_streams): a workgroup
+// takes kRBlock consecutive lanes -- whole pixels -- reads Lq and hit0 side by side, writes the three planes of L and the valid
+// flags side by side, and hands the radiances through LDS to the threads that own a (pixel, channel) pair, which add the pixel's
+// samples in lane order onto the running sums: k_finish's additions in k_finish's order.  (k_finish reads L back with one thread
+// per pixel, its lanes spp floats apart: at 16 spp every load of a wave touches 64 lines.)  A pixel's samples stand spp + 1 words
+// apart in LDS (spp 1: side by side), so the owners' reads spread over the banks.
+__host__ __device__ constexpr int finish_pixel_stride(int spp) { return spp > 1 ? spp + 1 : 1; }
+__host__ __device__ constexpr bool finish_streams(int spp) { return spp >= 1 && spp <= kRBlock && kRBlock % spp == 0; }
+__global__ __launch_bounds__(kRBlock) void k_finish_stream(RenderArgs a, uint8_t *__restrict__ valid_out,
+                                                           float *__restrict__ sumL, float *__restrict__ sumL2)
+{
+	__shared__ float s_L[3][kRBlock + kRBlock / 2]; // (the widest: spp 2, 128 pixels of stride 3)
+	const uint64_t N = a.n_lanes, P = a.film_pixels;
+	const uint64_t i = (uint64_t)blockIdx.x * kRBlock + threadIdx.x;
+	const uint32_t spp = (uint32_t)a.spp, stride = (uint32_t)finish_pixel_stride(a.spp);
+	if (i < N) {
+		const uint4 q = a.Lq[i];
+		const float x = __uint_as_float(q.x), y = __uint_as_float(q.y), z = __uint_as_float(q.z);
+		a.L[i] = x; a.L[N + i] = y; a.L[2 * N + i] = z;
+		valid_out[i] = a.hit0[i];
+		const uint32_t at = (threadIdx.x / spp) * stride + threadIdx.x % spp;
+		s_L[0][at] = x; s_L[1][at] = y; s_L[2][at] = z;
+	}
+	__syncthreads();
+	const uint32_t ppb = (uint32_t)kRBlock / spp; // pixels of a workgroup; pair c * ppb + p is channel c of its pixel p
+	for (uint32_t k = threadIdx.x; k < 3u * ppb; k += (uint32_t)kRBlock) { // (more pairs than threads at 1 and 2 spp)
+		const uint32_t c = k / ppb, p = k % ppb;
+		const uint64_t pix = (uint64_t)blockIdx.x * ppb + p;
+		if (pix >= a.n_pixels) continue;
+		const uint64_t gpix = global_pixel(a, pix); // the sums are full-film arrays
+		float s1 = sumL[c * P + gpix], s2 = sumL2[c * P + gpix];
+		for (uint32_t s = 0; s < spp; ++s) {
+			const float v = s_L[c][p * stride + s];
+			s1 = s1 + v;
+			s2 = s2 + v * v;
+		}
+		sumL[c * P + gpix] = s1; sumL2[c * P + gpix] = s2;
+	}
+}
+
 // element-wise evaluation of the library's deterministic fp32 functions (pg_math_eval)
 __global__ __launch_bounds__(kRBlock) void k_math_eval(int which, uint64_t n, const float *__restrict__ x,
                                                        float *__restrict__ out)
@@ -467,8 +507,10 @@ struct PassBuf {
 constexpr uint64_t kSortMinLiveNum = 3, kSortMinLiveDen = 10;
 
 // What an interval of pg_enable_kernel_timing is credited to (pg_read_kernel_timing): a quad scene's bounce (k_bounce_tail and
-// k_bounce as one), the kernels of the split pipeline (timer_of) and its sorts, k_splat_list, and k_layout_L with k_finish
-enum class Timer { Bounce, Trace, ShadeA, Shadow, Guide, ShadeB, Tail, Sort, Splat, Finish };
+// k_bounce as one), the kernels of the split pipeline (timer_of) and its sorts, k_splat_list, and k_layout_L with k_finish (or k_finish_stream)
+// (ShadeFirst: the joint form's first launch, k_wave_shade<., true> -- it walks the camera rays' closest hits itself, so it is
+// the bounce's closest-hit pass and its shading kernel in one interval: counted as both, its time as shading)
+enum class Timer { Bounce, Trace, ShadeA, ShadeFirst, Shadow, Guide, ShadeB, Tail, Sort, Splat, Finish };
 
 // library-owned renderer state
 struct pg_render_state {
@@ -705,8 +747,8 @@ static Timer timer_of(WaveStage stage)
 }
 
 // Bounce `it` of a mesh scene: the split pipeline's kernels (pg_render_wave.hip), each timed on its own -- the tail launch at
-// a checkpoint; the closest hits (a sorted bounce: with the keys cleared before and the sort after); then the joint shading
-// kernel, or ShadeA, Cast, Guide (unless fused into ShadeA) and ShadeB.  pg_render_overlap runs Guide beside Cast on the
+// a checkpoint; the closest hits (a sorted bounce: with the keys cleared before and the sort after; none for bounce 0 of the
+// joint form, whose shading kernel walks the camera rays itself); then the joint shading kernel, or ShadeA, Cast, Guide (unless fused into ShadeA) and ShadeB.  pg_render_overlap runs Guide beside Cast on the
 // set's side stream -- both read what ShadeA left and write planes of their own, one bound by divergent gathers into the
 // tree, the other by the BVH walk's dependent loads -- except in a sorted bounce, where it runs after Cast on s.
 static int wave_bounce(pg_context *ctx, PassBuf &b, RenderArgs &a, int it, int sort_until, hipStream_t s)
@@ -718,7 +760,7 @@ static int wave_bounce(pg_context *ctx, PassBuf &b, RenderArgs &a, int it, int s
 	// are k_wave_guide<true>'s and k_wave_tail<., true>'s, the only kernels that store a vertex's geometry
 	uint32_t *const geo = r->scene.geometry && a.record ? b.r_geo.p : nullptr;
 	auto launch = [&](WaveStage stage, hipStream_t on, unsigned grid_blocks) {
-		Timed t(r, on, timer_of(stage));
+		Timed t(r, on, stage == WaveStage::Shade && it == 0 ? Timer::ShadeFirst : timer_of(stage));
 		launch_wave_stage(stage, r->scene.general, it == 0, a, grid_blocks, (unsigned)ctx->n_cus, on, geo);
 	};
 	// the state set this bounce reads and the one its survivors are written to; the camera rays of the first
@@ -746,14 +788,17 @@ static int wave_bounce(pg_context *ctx, PassBuf &b, RenderArgs &a, int it, int s
 		a.n_sort = (uint32_t)(n_sort < N ? n_sort : N);
 		PG_HIP(ctx, hipMemsetAsync(b.sort_key.p, 0xff, (size_t)a.n_sort * sizeof(uint16_t), s)); // (0xffff: a place without a path)
 	}
-	launch(WaveStage::Trace, s, blocks);
+	// (the joint form's first launch makes and walks the camera rays itself, shade_body<., true>: bounce 0 has no closest-hit
+	// launch there and no Timer::Trace interval -- Timer::ShadeFirst counts the bounce)
+	const bool joint = r->stages == 0 && !(r->overlap & 1) && !geo;
+	if (!(joint && it == 0)) launch(WaveStage::Trace, s, blocks);
 	if (sorted) {
 		Timed t(r, s, Timer::Sort);
 		PG_HIP(ctx, sort_places16(b.sort_tmp.p, b.sort_tmp_bytes, b.sort_key.p, b.sort_key_out.p, b.sort_perm.p, a.n_sort,
 		                            a.live_count + (it - 1), s));
 		a.perm = b.sort_perm.p;
 	}
-	if (r->stages == 0 && !(r->overlap & 1) && !geo) {
+	if (joint) {
 		launch(WaveStage::Shade, s, blocks);
 		return PG_OK;
 	}
@@ -790,7 +835,7 @@ static pg_list_records list_records(const PassBuf &b)
 }
 
 // Behind the bounces of a pass in buffer set `slot`: the splat of its records into sdTree_current, the output column of
-// the split pipeline (k_layout_L), the valid flags and the per-pixel sums (k_finish)
+// the split pipeline (k_layout_L), the valid flags and the per-pixel sums (k_finish) -- or k_finish_stream for all three
 static int finish_pass(pg_context *ctx, int slot, const RenderArgs &a, uint8_t *valid_out, float *sumL, float *sumL2, hipStream_t s)
 {
 	pg_render_state *r = ctx->render;
@@ -807,7 +852,9 @@ static int finish_pass(pg_context *ctx, int slot, const RenderArgs &a, uint8_t *
 			launch_splat_list(ctx->view(), ctx->f.accum_view(), ctx->store_nee, a.n_lanes, a.max_depth, a.L, a.Lq, lr, b.live_count.p, s);
 		PG_HIP(ctx, hipGetLastError());
 	}
-	if (r->scene.general >= 2) {
+	// (a mesh scene's pass with flags and sums whose spp divides the workgroup: one streaming kernel for both, below)
+	const bool stream = r->scene.general >= 2 && a.Lq && valid_out && sumL && sumL2 && finish_streams(a.spp);
+	if (r->scene.general >= 2 && !stream) {
 		Timed t(r, s, Timer::Finish);
 		hipLaunchKernelGGL(k_layout_L, dim3((unsigned)((a.n_lanes + kRBlock - 1) / kRBlock)), dim3(kRBlock), 0, s, b.Lq.p, a.L, a.n_lanes);
 	}
@@ -817,8 +864,12 @@ static int finish_pass(pg_context *ctx, int slot, const RenderArgs &a, uint8_t *
 		PassBuf &other = r->pb[1 - slot];
 		if (sumL && other.finish_recorded) PG_HIP(ctx, hipStreamWaitEvent(s, other.ev_finish, 0));
 		Timed t(r, s, Timer::Finish);
-		hipLaunchKernelGGL(k_finish, dim3((unsigned)((a.n_pixels + kRBlock - 1) / kRBlock)), dim3(kRBlock), 0, s, a, valid_out,
-		                   sumL, sumL2);
+		if (stream)
+			hipLaunchKernelGGL(k_finish_stream, dim3((unsigned)((a.n_lanes + kRBlock - 1) / kRBlock)), dim3(kRBlock), 0, s, a, valid_out,
+			                   sumL, sumL2);
+		else
+			hipLaunchKernelGGL(k_finish, dim3((unsigned)((a.n_pixels + kRBlock - 1) / kRBlock)), dim3(kRBlock), 0, s, a, valid_out,
+			                   sumL, sumL2);
 		PG_HIP(ctx, hipGetLastError());
 		if (sumL) {
 			if (!b.ev_finish) PG_HIP(ctx, hipEventCreateWithFlags(&b.ev_finish, hipEventDisableTiming));
@@ -1118,6 +1169,9 @@ int pg_read_kernel_timing(pg_context *ctx, pg_kernel_timing *out, int32_t reset)
 		case Timer::Bounce: r->acc.bounce_ms += ms; ++r->acc.bounce_launches; break;
 		case Timer::Trace: r->acc.trace_ms += ms; r->acc.bounce_ms += ms; ++r->acc.trace_launches; ++r->acc.bounce_launches; break;
 		case Timer::ShadeA: r->acc.shade_ms += ms; r->acc.shade_a_ms += ms; r->acc.bounce_ms += ms; break;
+		case Timer::ShadeFirst:
+			r->acc.shade_ms += ms; r->acc.shade_a_ms += ms; r->acc.bounce_ms += ms; ++r->acc.trace_launches; ++r->acc.bounce_launches;
+			break;
 		case Timer::Shadow: r->acc.shadow_ms += ms; r->acc.bounce_ms += ms; break;
 		case Timer::Guide: r->acc.guide_ms += ms; r->acc.bounce_ms += ms; ++r->acc.guide_launches; break;
 		case Timer::ShadeB: r->acc.shade_ms += ms; r->acc.shade_b_ms += ms; r->acc.bounce_ms += ms; break;

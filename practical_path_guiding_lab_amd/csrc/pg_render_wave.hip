@@ -6,10 +6,13 @@
 // sort keys, the kernels and their launchers:
 //
 //   k_wave_trace    :185   scene.ray_intersect: closest hit of every live ray (BVH walk; stacks and the hottest
-//                          nodes in LDS); the first launch also makes the camera rays.  Between it and what
+//                          nodes in LDS); the first launch also makes the camera rays (the split forms only: the
+//                          joint form has no such launch for bounce 0).  Between it and what
 //                          follows the live list of a sorted bounce is put in spatial order (pg_sort.hip).
 //   k_wave_shade    :189-381   (the default) everything else of the bounce on one lane's registers: stage_a,
-//                          stage_guide, the shadow ray as an inline any-hit walk, stage_b, the survivors' append
+//                          stage_guide, the shadow ray as an inline any-hit walk, stage_b, the survivors' append;
+//                          its FIRST launch makes the camera ray and walks its closest hit too (:185, the slim walk on
+//                          the kernel's own stack and LDS top) -- ray, sampler and hit never go through device memory
 // or, handing their results on through the planes of `ws` (indexed by the lane's place in the live list):
 //   k_wave_shade_a  :189-220, 272-297   stage_a: surface and textures at the hit, emitted radiance and its MIS
 //                          weight, one emitter sample (a shadow ray to trace), the BSDF towards it, the
@@ -798,7 +801,16 @@ __device__ __forceinline__ void shade_body(const RenderArgs &a)
 		const bool from_rec = !kFirst && a.perm != nullptr; // a sorted bounce: the path's 128-byte record, through the permutation
 		uint32_t place = (uint32_t)tid; // (32-bit: a place in the live list; one register through the walks, not two)
 		if (!coop && from_rec && tid < (uint64_t)a.n_sort) place = a.perm[tid];
-		if (from_rec) {
+		if (kFirst) {
+			// The camera bounce: the ray is a function of the lane number, so it is made and walked HERE, on this kernel's own
+			// stack and LDS top (the slim walk, as the shadow ray's below) -- ray, sampler and hit never leave the registers.  No
+			// k_wave_trace runs ahead of this launch and nothing of st_in / inc_in / the hit planes is read or written: the next
+			// bounce's set is written by append_survivors as ever.  Nothing else of a path is alive yet, so the walk is far from
+			// the kernel's register peak.
+			camera_ray(a, tid, rng, ray_o, ray_d);
+			h.u = 0.0f; h.v = 0.0f;
+			h.prim = intersect<kLevel, false, true>(a.shapes, ray_o, ray_d, __builtin_huge_valf(), h.t, stk, h.u, h.v);
+		} else if (from_rec) {
 			const uint4 *rec = st_rec(a.carry_in, place);
 			uint4 q0, q1, q2, q3, q5, q6;
 			if (coop) { q0 = cq0; q1 = cq1; q2 = cq2; q3 = cq3; q5 = cq5; q6 = cq6; }
@@ -817,18 +829,16 @@ __device__ __forceinline__ void shade_body(const RenderArgs &a)
 			rng.state = st_u64(q0.w, q1.w);
 			rng.inc = a.inc_in[tid];
 			ray_o = st_v3(q0); ray_d = st_v3(q1);
-			if (!kFirst) {
-				const uint4 q2 = st_load(a.st_in, a, PS_THR, tid), q3 = st_load(a.st_in, a, PS_PREV, tid);
-				thr = st_v3(q2);
-				{ const uint4 q4 = st_load(a.st_in, a, PS_L, tid); ior = st_ior(q2); L = st_v3(q4); lane = st_lane(q4); }
-				prev_delta = st_delta(q2);
-				prev_p = st_v3(q3);
-				prev_pdf = st_wf(q3);
-			}
+			const uint4 q2 = st_load(a.st_in, a, PS_THR, tid), q3 = st_load(a.st_in, a, PS_PREV, tid);
+			thr = st_v3(q2);
+			{ const uint4 q4 = st_load(a.st_in, a, PS_L, tid); ior = st_ior(q2); L = st_v3(q4); lane = st_lane(q4); }
+			prev_delta = st_delta(q2);
+			prev_p = st_v3(q3);
+			prev_pdf = st_wf(q3);
 			h = ws_hit(a, tid);
 		}
 		StageA A;
-		PG_PHASE(0)
+		PG_PHASE(0) // (in the first launch the camera ray's closest-hit walk falls into this phase, "records + staging")
 		stage_a1<kLevel>(a, rng, ray_o, ray_d, thr, prev_p, prev_pdf, prev_delta, h, (uint32_t)a.bounce, A);
 		// What stage_a1 leaves is PINNED here: every output is made now, so that its inputs die.  (Left alone the compiler
 		// sinks the last operations of a value that is only read behind the walk -- the emitted radiance's three products, the

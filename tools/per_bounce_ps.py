@@ -2,7 +2,8 @@
   python tools/per_bounce_ps.py TRACE_DIR BENCH_DETAIL.json [passes]
 A pass = the kernels between two k_finish launches.  Of the passes that ran the joint shading kernel (k_wave_shade: the
 timed region of `value`, not the pg_render_stages(2) region behind it) the last `passes` (default 3) are averaged.  Launch b
-of k_wave_shade / k_wave_trace in a pass is bounce b; the lanes that went into it are the film's for bounce 0 and
+of k_wave_shade in a pass is bounce b; launch b of k_wave_trace is bounce b + 1 (the joint form's first launch walks the camera
+rays itself: bounce 0 has no k_wave_trace and its column reads 0); the lanes that went into it are the film's for bounce 0 and
 config.paths_alive_after_bounce[b - 1] of the detail file after that.  Also prints which bounces a sort ran in front of
 (the k_sort_hist launches between two k_wave_trace launches: two per sort) and the sort kernels' time there."""
 import csv
@@ -30,7 +31,7 @@ trace = [[] for _ in range(D)]
 sort_us = [[] for _ in range(D)]
 hists = [[] for _ in range(D)]
 for p in joint:
-    b_shade, b_trace, su, nh = 0, -1, 0.0, 0
+    b_shade, b_trace, su, nh = 0, 0, 0.0, 0  # (the first k_wave_trace of a joint pass is bounce 1's)
     for k, us in p:
         if "k_wave_trace<" in k:
             b_trace += 1
@@ -48,7 +49,7 @@ for p in joint:
 
 
 def mean(x):
-    return sum(x) / len(x)
+    return sum(x) / len(x) if x else 0.0
 
 
 print(f"# {detail['extra']['library']}  {cfg['workload'][:60]}...  mean of the last {len(joint)} passes of the timed region")

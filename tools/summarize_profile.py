@@ -14,7 +14,7 @@ src, dst, cfg = sys.argv[1], sys.argv[2], sys.argv[3]
 BOUNCES = int(sys.argv[4]) if len(sys.argv) > 4 else 8  # k_bounce launches per pass = max_depth
 os.makedirs(dst, exist_ok=True)
 KERNELS = ("k_wave_trace", "k_wave_shade_a", "k_wave_cast", "k_wave_guide", "k_wave_shade_b", "k_wave_shade", "k_wave_tail", "k_bounce", "k_splat_list",
-           "k_process_and_splat", "k_finish", "k_sort_scatter", "k_sort_hist", "k_sort_scan")  # (k_wave_shade after _a and _b: the first name found in a kernel's name counts)  # k_wave_cast = the persistent any-hit kernel of the shadow rays
+           "k_process_and_splat", "k_layout_L", "k_finish", "k_sort_scatter", "k_sort_hist", "k_sort_scan")  # (k_wave_shade after _a and _b: the first name found in a kernel's name counts)  # k_wave_cast = the persistent any-hit kernel of the shadow rays
 PER_BOUNCE = ("k_bounce", "k_wave_trace", "k_wave_shade_a", "k_wave_cast", "k_wave_guide", "k_wave_shade_b", "k_wave_shade")
 
 
@@ -23,6 +23,20 @@ def short(name):
         if k in name:
             return k
     return None
+
+
+def launches_per_pass(k, names):
+    """names: the full kernel names of the region's launches, one per launch.  The joint form's first launch walks the camera rays
+    itself (k_wave_shade<., true>): a region whose passes have no k_wave_trace<., true> beside their k_wave_shade<., true> has one
+    closest-hit launch less per pass than bounces.  (Counted, not tested for absence: the roofline region's first launch, a
+    k_wave_trace<., true>, stands ahead of the k_wave_guide launch the regions are told apart by.)"""
+    if k == "k_wave_tail":
+        return sum(1 for b in range(BOUNCES) if BOUNCES > 8 and b >= 4 and b + 1 < BOUNCES and (b < 8 or (b < 16 and b % 2 == 0) or b % 4 == 0))
+    first_shades = sum(1 for n in names if "k_wave_shade<" in n and ", true>" in n)
+    first_traces = sum(1 for n in names if "k_wave_trace<" in n and ", true>" in n)
+    if k == "k_wave_trace" and first_shades and 2 * first_traces < first_shades:
+        return BOUNCES - 1
+    return BOUNCES if k in PER_BOUNCE else 1
 
 
 def newest(pattern):
@@ -38,8 +52,10 @@ shutil.copy(os.path.join(src, "bench_under_trace.json"), os.path.join(dst, "benc
 # exact per-launch durations of the timed region from the trace (last 10 passes)
 trace = newest(f"{src}/trace/*/*kernel_trace.csv")[0]
 dur = collections.defaultdict(list)
+name_at = []
 for r in csv.DictReader(open(trace)):
     k = short(r["Kernel_Name"])
+    name_at.append((int(r["Start_Timestamp"]), r["Kernel_Name"]))
     if k:
         dur[k].append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]) - int(r["Start_Timestamp"])))
 # bench.py times two regions: the default form of the pipeline (one shading kernel per bounce, k_wave_shade), then the
@@ -48,16 +64,17 @@ for r in csv.DictReader(open(trace)):
 SPLIT_ONLY = ("k_wave_shade_a", "k_wave_cast", "k_wave_guide", "k_wave_shade_b")
 second_region = set(SPLIT_ONLY) if "k_wave_shade" in dur else {"k_wave_guide"}  # kernels that run in the second region only
 t_split = min((t for k in second_region for t, _ in dur.get(k, [])), default=None)
+if t_split is not None:  # (the first region ends with its last k_finish: the roofline region's first launch, k_wave_trace<., true>, stands ahead of its first k_wave_guide)
+    t_split = max((t for t, _ in dur.get("k_finish", []) if t < t_split), default=t_split - 1) + 1
 if t_split is not None:
     for k in list(dur):
         if k not in second_region:
             dur[k] = [(t, d) for t, d in dur[k] if t < t_split]
+trace_names = [n for t, n in name_at if t_split is None or t < t_split]  # (the first region's: the second runs k_wave_trace<., true>)
 trace_summary = {}
 for k, v in dur.items():
     v.sort()
-    per_pass = BOUNCES if k in PER_BOUNCE else 1
-    if k == "k_wave_tail":
-        per_pass = sum(1 for b in range(BOUNCES) if BOUNCES > 8 and b >= 4 and b + 1 < BOUNCES and (b < 8 or (b < 16 and b % 2 == 0) or b % 4 == 0))
+    per_pass = launches_per_pass(k, trace_names)
     last = [d for _, d in v[-10 * per_pass:]]
     trace_summary[k] = {"launches_in_timed_region": len(last), "avg_us": round(sum(last) / len(last) / 1e3, 2),
                         "min_us": round(min(last) / 1e3, 2), "max_us": round(max(last) / 1e3, 2)}
@@ -78,16 +95,17 @@ def agg(sub):
         names = {short(r["Kernel_Name"]) for r in rows}
         second = set(SPLIT_ONLY) if "k_wave_shade" in names else {"k_wave_guide"}
         first_second = min((int(r["Dispatch_Id"]) for r in rows if short(r["Kernel_Name"]) in second), default=None)
-        if first_second is not None:  # (see above: the other kernels over the first region only)
+        if first_second is not None:  # (see above: the other kernels over the first region only, which ends with its last k_finish)
+            first_second = max((int(r["Dispatch_Id"]) for r in rows if short(r["Kernel_Name"]) == "k_finish" and int(r["Dispatch_Id"]) < first_second),
+                               default=first_second - 1) + 1
             rows = [r for r in rows if short(r["Kernel_Name"]) in second or int(r["Dispatch_Id"]) < first_second]
         for r in rows:
             k = short(r["Kernel_Name"])
             if k:
                 d[k][r["Counter_Name"]].append(float(r["Counter_Value"]))
+        first_names = [r["Kernel_Name"] for r in rows if short(r["Kernel_Name"]) not in second]  # (the first region's launches)
         for k in d:
-            per_pass = BOUNCES if k in PER_BOUNCE else 1
-            if k == "k_wave_tail":
-                per_pass = sum(1 for b in range(BOUNCES) if BOUNCES > 8 and b >= 4 and b + 1 < BOUNCES and (b < 8 or (b < 16 and b % 2 == 0) or b % 4 == 0))
+            per_pass = launches_per_pass(k, first_names)
             for c in d[k]:
                 d[k][c] = d[k][c][-PMC_STEPS * per_pass:]
     return d
