@@ -335,7 +335,7 @@ int pg_process_and_splat(pg_context *ctx, uint64_t num_rays, int32_t max_depth, 
 		                                  l_final, *rec, ctx->n_cus, (hipStream_t)stream);
 	else
 		launch_process_and_splat(ctx->view(), ctx->f.accum_view(), ctx->store_nee, num_rays, max_depth, l_final,
-		                         *rec, ctx->dc_on ? ctx->dc : nullptr, (hipStream_t)stream);
+		                         *rec, ctx->dc_on ? ctx->dc : nullptr, ctx->n_cus, (hipStream_t)stream);
 	PG_LAUNCHED(ctx);
 	return PG_OK;
 }

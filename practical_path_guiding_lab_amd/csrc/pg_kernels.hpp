@@ -65,14 +65,15 @@ struct pg_list_records {
 	const uint2 *slot;         // {path direction's, emitter direction's} accumulator: kSlotNone / kSlotRoot / rec * 4 + child
 	const uint32_t *tree;      // quadtree of the vertex's KD leaf; bit 31: inside the root box (counted, kdtree.py:193)
 };
-// l_final (3, num_rays) planar, or -- when l_final_q is given -- one 16-byte entry per path
+// l_final (3, num_rays) planar, or -- when l_final_q is given -- one 16-byte entry per path; n_cus: the device's compute
+// units, which size every strided grid of the recording kernels
 void launch_splat_list(const TreeView &t, const AccumView &a, int store_nee, uint64_t num_rays, int32_t max_depth,
                        const float *l_final, const uint4 *l_final_q, const pg_list_records &rec, const uint32_t *live_count,
-                       hipStream_t s);
+                       int n_cus, hipStream_t s);
 
 void launch_process_and_splat(const TreeView &t, const AccumView &a, int store_nee,
                               uint64_t num_rays, int32_t max_depth, const float *l_final,
-                              const pg_dense_records &rec, DepthCounters *dc, hipStream_t s);
+                              const pg_dense_records &rec, DepthCounters *dc, int n_cus, hipStream_t s);
 
 // ---- recording through the training filters (pg_kernels_filter.hip; pg_set_splat_filter, include/pgsd.h) ----
 struct pg_filter_args {
@@ -93,6 +94,7 @@ void launch_splat_list_filtered(const TreeView &t, const AccumView &a, const pg_
                                 int32_t max_depth, const uint4 *l_final_q, const pg_list_records &rec, const pg_list_geometry &geo,
                                 const uint32_t *live_count, int n_cus, hipStream_t s);
 // the kept entries in pg_process_records' output layout, slot_out (may be nullptr) their dense slots; zeroes *d_count first
+// (no filter is applied: k_export_list_records stands beside k_process_records in pg_kernels_splat.hip)
 void launch_export_list_records(uint64_t num_rays, int32_t max_depth, const uint4 *l_final_q, const pg_list_records &rec,
                                 const pg_list_geometry &geo, const uint32_t *live_count, const pg_records_out &out, uint32_t *slot_out,
                                 uint32_t *d_count, int n_cus, hipStream_t s);

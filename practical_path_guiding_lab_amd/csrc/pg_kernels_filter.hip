@@ -25,9 +25,6 @@
 
 namespace pg {
 
-constexpr int kFBlock = 256;
-static_assert(kFBlock == kStageThreads, "stage_kd_planes copies one plane per thread");
-
 // the four child words of a record (0 = that child is a leaf)
 __device__ __forceinline__ uint4 load_children(const QuadRec *rec, uint32_t r)
 {
@@ -505,8 +502,18 @@ __device__ __forceinline__ void splat_filtered(const TreeView &t, const AccumVie
 	}
 }
 
+// A filtered kernel's LDS -- the staged KD planes, coop_add's exchange buffers, the waves' queues -- and the state of its
+// wave's own queue, which lives across the tiles of a strided kernel
+#define PG_FILTER_LDS()                                  \
+	__shared__ float s_planes[3 * kKdGridPlanes];        \
+	__shared__ long long s_val[kBlock * 4];              \
+	__shared__ unsigned long long s_ptr[kBlock];         \
+	__shared__ uint2 s_queue[(kBlock / 64) * kQueue];    \
+	uint2 *s_q = s_queue + (threadIdx.x >> 6) * kQueue;  \
+	uint32_t len = 0
+
 template <bool kOverlap>
-__global__ __launch_bounds__(kFBlock) void k_filter_splat(TreeView t, AccumView a, pg_filter_args f, int store_nee, uint64_t m,
+__global__ __launch_bounds__(kBlock) void k_filter_splat(TreeView t, AccumView a, pg_filter_args f, int store_nee, uint64_t m,
                                                           const float *__restrict__ pos, const float *__restrict__ dir,
                                                           const float *__restrict__ radiance,
                                                           const float *__restrict__ wo_pdf,
@@ -514,14 +521,9 @@ __global__ __launch_bounds__(kFBlock) void k_filter_splat(TreeView t, AccumView 
                                                           const float *__restrict__ nee_lum,
                                                           const uint32_t *__restrict__ d_count)
 {
-	__shared__ float s_planes[3 * kKdGridPlanes];
-	__shared__ long long s_val[kFBlock * 4];
-	__shared__ unsigned long long s_ptr[kFBlock];
-	__shared__ uint2 s_queue[(kFBlock / 64) * kQueue];
-	uint2 *s_q = s_queue + (threadIdx.x >> 6) * kQueue; // the wave's own queue
-	uint32_t len = 0;
+	PG_FILTER_LDS();
 	stage_kd_planes(s_planes, t);
-	const uint64_t i = (uint64_t)blockIdx.x * kFBlock + threadIdx.x;
+	const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
 	const uint64_t n_valid = d_count ? (uint64_t)*d_count : m; // plane stride stays m
 	const bool valid = i < n_valid && i < m;
 	float x = 0.0f, y = 0.0f, z = 0.0f, dx = 0.0f, dy = 0.0f, rad = 0.0f, wp = 0.0f, nx = 0.0f, ny = 0.0f, nl = 0.0f;
@@ -537,19 +539,14 @@ __global__ __launch_bounds__(kFBlock) void k_filter_splat(TreeView t, AccumView 
 
 // the dense record buffer (k_process_and_splat's loop over the tiles, pg_kernels_splat.hip); record number = dense slot g
 template <bool kOverlap>
-__global__ __launch_bounds__(kFBlock) void k_filter_process_and_splat(TreeView t, AccumView a, pg_filter_args f, int store_nee,
+__global__ __launch_bounds__(kBlock) void k_filter_process_and_splat(TreeView t, AccumView a, pg_filter_args f, int store_nee,
                                                                       uint64_t num_rays, int32_t max_depth,
                                                                       const float *__restrict__ l_final, pg_dense_records r)
 {
-	__shared__ float s_planes[3 * kKdGridPlanes];
-	__shared__ long long s_val[kFBlock * 4];
-	__shared__ unsigned long long s_ptr[kFBlock];
-	__shared__ uint2 s_queue[(kFBlock / 64) * kQueue];
-	uint2 *s_q = s_queue + (threadIdx.x >> 6) * kQueue; // the wave's own queue: it lives across the tiles
-	uint32_t len = 0;
+	PG_FILTER_LDS();
 	const uint64_t S = num_rays * (uint64_t)max_depth;
 	stage_kd_planes(s_planes, t);
-	for (uint64_t base = (uint64_t)blockIdx.x * kFBlock; base < S; base += (uint64_t)gridDim.x * kFBlock) {
+	for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < S; base += (uint64_t)gridDim.x * kBlock) {
 		const uint64_t g = base + threadIdx.x;
 		float radiance = 0.0f, nee_lum = 0.0f, wp = 0.0f;
 		bool keep = false;
@@ -566,66 +563,24 @@ __global__ __launch_bounds__(kFBlock) void k_filter_process_and_splat(TreeView t
 	queue_drain(a, s_q, len, s_val, s_ptr);
 }
 
-// ---- the renderer's own record list with its vertex geometry (pg_render_record_geometry) ----
-// processPathData + scatterDataIntoSDTree's filter for entry g of the list: what k_splat_list does ahead of its adds -- the
-// streaming loads, the one gather of the path's final radiance, the division chain of :434-453, the keep test of :470-478.
-// Returns keep; `ray` is the entry's path.
-__device__ __forceinline__ bool process_list_entry(uint64_t g, uint64_t S, const uint4 *__restrict__ l_final_q, const pg_list_records &r,
-                                                   uint32_t &ray, float &radiance, float &nee_lum, float &wp)
-{
-#define PG_LD(p) __builtin_nontemporal_load(p)
-	radiance = 0.0f; nee_lum = 0.0f; wp = 0.0f;
-	ray = PG_LD(r.ray_of + g);
-	if (ray == 0xffffffffu) return false; // the path left the scene at this entry
-	const uint4 q = l_final_q[ray];
-	const float lf[3] = {__uint_as_float(q.x), __uint_as_float(q.y), __uint_as_float(q.z)};
-	float in[3];
-#pragma unroll
-	for (int ch = 0; ch < 3; ++ch) {
-		float out = (lf[ch] - PG_LD(r.throughput_radiance + ch * S + g)) / PG_LD(r.throughput_bsdf + ch * S + g);
-		if (out != out) out = 0.0f;                         // :444
-		float v = out / PG_LD(r.bsdf + ch * S + g);
-		if (v != v) v = 0.0f;                               // :449
-		in[ch] = v;
-	}
-	radiance = luminance(in[0], in[1], in[2]);            // :452
-	if (radiance != radiance) radiance = 0.0f;            // :466
-	nee_lum = PG_LD(r.nee_lum + g);
-	wp = PG_LD(r.wo_pdf + g);
-#undef PG_LD
-	const bool both_zero = (radiance == 0.0f) && (nee_lum == 0.0f); // :470-472
-	return !both_zero && !(wp == 0.0f) && !(wp != wp);    // :475-478
-}
-
-// entries of the list: the first bounce visits every path, bounce b + 1 the survivors of bounce b (k_splat_list's count)
-__device__ __forceinline__ uint64_t list_entries(uint64_t num_rays, int32_t max_depth, const uint32_t *__restrict__ live_count)
-{
-	uint64_t total = num_rays;
-	for (int b = 0; b + 1 < max_depth; ++b) total += live_count[b];
-	return total;
-}
-
-// The list through the filters: every kept entry is the record pg_process_and_splat would have found in dense slot
-// ray * max_depth + depth of the reference's buffer, and that slot (modulo 2^32) is its record number for the jitter.
+// The renderer's own record list with its vertex geometry (pg_render_record_geometry) through the filters: every kept entry
+// (process_list_entry; such a pass keeps a path's final radiance in l_final_q) is the record pg_process_and_splat would have
+// found in dense slot ray * max_depth + depth of the reference's buffer, and that slot (modulo 2^32) is its record number
+// for the jitter.
 template <bool kOverlap>
-__global__ __launch_bounds__(kFBlock) void k_filter_splat_list(TreeView t, AccumView a, pg_filter_args f, int store_nee, uint64_t num_rays,
-                                                               int32_t max_depth, const uint4 *__restrict__ l_final_q, pg_list_records r,
-                                                               pg_list_geometry geo, const uint32_t *__restrict__ live_count)
+__global__ __launch_bounds__(kBlock) void k_filter_splat_list(TreeView t, AccumView a, pg_filter_args f, int store_nee, uint64_t num_rays,
+                                                              int32_t max_depth, const uint4 *__restrict__ l_final_q, pg_list_records r,
+                                                              pg_list_geometry geo, const uint32_t *__restrict__ live_count)
 {
-	__shared__ float s_planes[3 * kKdGridPlanes];
-	__shared__ long long s_val[kFBlock * 4];
-	__shared__ unsigned long long s_ptr[kFBlock];
-	__shared__ uint2 s_queue[(kFBlock / 64) * kQueue];
-	uint2 *s_q = s_queue + (threadIdx.x >> 6) * kQueue; // the wave's own queue: it lives across the tiles
-	uint32_t len = 0;
+	PG_FILTER_LDS();
 	const uint64_t S = num_rays * (uint64_t)max_depth;
 	const uint64_t total = list_entries(num_rays, max_depth, live_count);
 	stage_kd_planes(s_planes, t);
-	for (uint64_t base = (uint64_t)blockIdx.x * kFBlock; base < total; base += (uint64_t)gridDim.x * kFBlock) {
+	for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < total; base += (uint64_t)gridDim.x * kBlock) {
 		const uint64_t g = base + threadIdx.x;
 		float radiance = 0.0f, nee_lum = 0.0f, wp = 0.0f;
 		uint32_t ray = 0;
-		const bool keep = g < total && process_list_entry(g, S, l_final_q, r, ray, radiance, nee_lum, wp);
+		const bool keep = g < total && process_list_entry(g, S, num_rays, nullptr, l_final_q, r, ray, radiance, nee_lum, wp);
 		float x = 0.0f, y = 0.0f, z = 0.0f, dx = 0.0f, dy = 0.0f, nx = 0.0f, ny = 0.0f;
 		uint32_t index = 0;
 		if (keep) {
@@ -639,55 +594,10 @@ __global__ __launch_bounds__(kFBlock) void k_filter_splat_list(TreeView t, Accum
 	queue_drain(a, s_q, len, s_val, s_ptr);
 }
 
-// pg_render_export_records: the kept entries as pg_process_records would have compacted them out of the dense buffer (any
-// order; one atomic on the counter per wave), with their dense slots
-__global__ __launch_bounds__(kFBlock) void k_export_list_records(uint64_t num_rays, int32_t max_depth, const uint4 *__restrict__ l_final_q,
-                                                                 pg_list_records r, pg_list_geometry geo,
-                                                                 const uint32_t *__restrict__ live_count, pg_records_out o,
-                                                                 uint32_t *__restrict__ slot_out, uint32_t *__restrict__ d_count)
-{
-	const uint64_t S = num_rays * (uint64_t)max_depth;
-	const uint64_t total = list_entries(num_rays, max_depth, live_count);
-	for (uint64_t base = (uint64_t)blockIdx.x * kFBlock; base < total; base += (uint64_t)gridDim.x * kFBlock) {
-		const uint64_t g = base + threadIdx.x;
-		float radiance = 0.0f, nee_lum = 0.0f, wp = 0.0f;
-		uint32_t ray = 0;
-		const bool keep = g < total && process_list_entry(g, S, l_final_q, r, ray, radiance, nee_lum, wp);
-		const unsigned long long mask = __ballot(keep);
-		if (mask == 0ull) continue;
-		const unsigned lane = threadIdx.x & 63u, first = (unsigned)__builtin_ctzll(mask);
-		uint32_t off = 0;
-		if (lane == first) off = atomicAdd(d_count, (uint32_t)__popcll(mask));
-		off = __shfl(off, (int)first, 64);
-		if (keep) {
-			// (k < S: the list has at most S entries, and every kept one is counted once)
-			const uint64_t k = (uint64_t)off + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-			o.position[k] = geo.position[g];
-			o.position[S + k] = geo.position[S + g];
-			o.position[2 * S + k] = geo.position[2 * S + g];
-			o.direction[k] = geo.direction[g];
-			o.direction[S + k] = geo.direction[S + g];
-			o.direction_nee[k] = geo.direction_nee[g];
-			o.direction_nee[S + k] = geo.direction_nee[S + g];
-			o.radiance[k] = radiance;
-			o.wo_pdf[k] = wp;
-			o.radiance_nee_lum[k] = nee_lum;
-			if (slot_out) slot_out[k] = (uint32_t)((uint64_t)ray * (uint64_t)max_depth + geo.depth[g]);
-		}
-	}
-}
+#undef PG_FILTER_LDS
 
 // the kernels of PG_SPATIAL_OVERLAP_BOX are instances of their own: those of the other filters carry nothing of its walk
 static inline bool overlap(const pg_filter_args &f) { return f.spatial == PG_SPATIAL_OVERLAP_BOX; }
-
-static inline dim3 grid_for_f(uint64_t n) { return dim3((unsigned)((n + kFBlock - 1) / kFBlock)); }
-
-// a fixed grid striding over the tiles (the list's length is known only on the device)
-static inline dim3 strided_grid_f(uint64_t S, int n_cus)
-{
-	const uint64_t tiles = (S + kFBlock - 1) / kFBlock, cap = (uint64_t)(n_cus > 0 ? n_cus : 256) * 64u;
-	return dim3((unsigned)(tiles < cap ? tiles : cap));
-}
 
 void launch_splat_list_filtered(const TreeView &t, const AccumView &a, const pg_filter_args &f, int store_nee, uint64_t num_rays,
                                 int32_t max_depth, const uint4 *l_final_q, const pg_list_records &rec, const pg_list_geometry &geo,
@@ -696,19 +606,8 @@ void launch_splat_list_filtered(const TreeView &t, const AccumView &a, const pg_
 	const uint64_t S = num_rays * (uint64_t)max_depth;
 	if (S == 0) return;
 	const auto kernel = overlap(f) ? k_filter_splat_list<true> : k_filter_splat_list<false>;
-	hipLaunchKernelGGL(kernel, strided_grid_f(S, n_cus), dim3(kFBlock), 0, s, t, a, f, store_nee, num_rays, max_depth, l_final_q, rec, geo,
+	hipLaunchKernelGGL(kernel, strided_grid(S, n_cus), dim3(kBlock), 0, s, t, a, f, store_nee, num_rays, max_depth, l_final_q, rec, geo,
 	                   live_count);
-}
-
-void launch_export_list_records(uint64_t num_rays, int32_t max_depth, const uint4 *l_final_q, const pg_list_records &rec,
-                                const pg_list_geometry &geo, const uint32_t *live_count, const pg_records_out &out, uint32_t *slot_out,
-                                uint32_t *d_count, int n_cus, hipStream_t s)
-{
-	const uint64_t S = num_rays * (uint64_t)max_depth;
-	(void)hipMemsetAsync(d_count, 0, sizeof(uint32_t), s);
-	if (S == 0) return;
-	hipLaunchKernelGGL(k_export_list_records, strided_grid_f(S, n_cus), dim3(kFBlock), 0, s, num_rays, max_depth, l_final_q, rec, geo,
-	                   live_count, out, slot_out, d_count);
 }
 
 void launch_splat_filtered(const TreeView &t, const AccumView &a, const pg_filter_args &f, int store_nee, uint64_t m,
@@ -716,7 +615,7 @@ void launch_splat_filtered(const TreeView &t, const AccumView &a, const pg_filte
 {
 	if (m == 0) return;
 	const auto kernel = overlap(f) ? k_filter_splat<true> : k_filter_splat<false>;
-	hipLaunchKernelGGL(kernel, grid_for_f(m), dim3(kFBlock), 0, s, t, a, f, store_nee, m, rec.position, rec.direction,
+	hipLaunchKernelGGL(kernel, grid_for(m), dim3(kBlock), 0, s, t, a, f, store_nee, m, rec.position, rec.direction,
 	                   rec.radiance, rec.wo_pdf, rec.direction_nee, rec.radiance_nee_lum, d_count);
 }
 
@@ -726,10 +625,8 @@ void launch_process_and_splat_filtered(const TreeView &t, const AccumView &a, co
 {
 	const uint64_t S = num_rays * (uint64_t)max_depth;
 	if (S == 0) return;
-	const uint64_t tiles = (S + kFBlock - 1) / kFBlock, cap = (uint64_t)(n_cus > 0 ? n_cus : 256) * 64u;
 	const auto kernel = overlap(f) ? k_filter_process_and_splat<true> : k_filter_process_and_splat<false>;
-	hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(kFBlock), 0, s, t, a, f,
-	                   store_nee, num_rays, max_depth, l_final, rec);
+	hipLaunchKernelGGL(kernel, strided_grid(S, n_cus), dim3(kBlock), 0, s, t, a, f, store_nee, num_rays, max_depth, l_final, rec);
 }
 
 } // namespace pg

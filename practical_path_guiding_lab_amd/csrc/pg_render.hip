@@ -849,7 +849,7 @@ static int finish_pass(pg_context *ctx, int slot, const RenderArgs &a, uint8_t *
 			launch_splat_list_filtered(ctx->view(), ctx->f.accum_view(), ctx->filter_args(), ctx->store_nee, a.n_lanes, a.max_depth, a.Lq, lr,
 			                           list_geometry(b, a.n_lanes * (uint64_t)a.max_depth), b.live_count.p, ctx->n_cus, s);
 		else
-			launch_splat_list(ctx->view(), ctx->f.accum_view(), ctx->store_nee, a.n_lanes, a.max_depth, a.L, a.Lq, lr, b.live_count.p, s);
+			launch_splat_list(ctx->view(), ctx->f.accum_view(), ctx->store_nee, a.n_lanes, a.max_depth, a.L, a.Lq, lr, b.live_count.p, ctx->n_cus, s);
 		PG_HIP(ctx, hipGetLastError());
 	}
 	// (a mesh scene's pass with flags and sums whose spp divides the workgroup: one streaming kernel for both, below)
