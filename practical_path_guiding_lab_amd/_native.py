@@ -124,16 +124,19 @@ EXPORTS = (
     "pg_read_shade_phases", "pg_set_splat_filter", "pg_render_record_geometry", "pg_render_export_records",
     "pg_scene_intersect", "pg_bsdf_probe",
 )
+# every symbol include/pgsd_warp.h declares beside them (sample warping: same library, same ABI version)
+EXPORTS_WARP = ("pg_sample_warp", "pg_invert_warp", "pg_guide_bounce_warp")
 
 
 def source_hash() -> str:
-    """sha256 (16 hex digits) over the library's sources (csrc/*.hip, csrc/*.hpp, include/pgsd.h): names the code a
+    """sha256 (16 hex digits) over the library's sources (csrc/*.hip, csrc/*.hpp, include/pgsd.h, include/pgsd_warp.h): names the code a
     profile was taken of (profiles/pmc_traffic.json) so that bench.py never pairs old counters with new kernels."""
     import glob
     import hashlib
     h = hashlib.sha256()
     files = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
     files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd.h"))
+    files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_warp.h"))
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
@@ -233,7 +236,10 @@ def lib() -> C.CDLL:
     L.pg_render_split_pipeline.argtypes = [V, C.c_int32]
     L.pg_render_record_geometry.argtypes = [V, I32]
     L.pg_render_export_records.argtypes = [V, I32, C.POINTER(pg_records_out), V, V, V]
-    for name in EXPORTS:
+    L.pg_sample_warp.argtypes = [V, U64, V, V, V, V, V, V]
+    L.pg_invert_warp.argtypes = [V, U64, V, V, V, V, V, V]
+    L.pg_guide_bounce_warp.argtypes = [V, U64, V, V, V, V, V, V, V, V, V, V, V]
+    for name in EXPORTS + EXPORTS_WARP:
         if name not in ("pg_last_error", "pg_abi_version"):
             getattr(L, name).restype = C.c_int
     _lib = L

@@ -196,19 +196,6 @@ int pg_set_splat_filter(pg_context *ctx, int32_t spatial, int32_t directional, u
 	return PG_OK;
 }
 
-#define PG_READY(ctx)                                                                  \
-	do {                                                                               \
-		if (!(ctx)) return PG_ERR_INVALID;                                             \
-		if (!(ctx)->configured) return fail((ctx), PG_ERR_INVALID, "call pg_setup or pg_import first"); \
-		PG_HIP((ctx), hipSetDevice((ctx)->device));                                    \
-	} while (0)
-
-#define PG_LAUNCHED(ctx)                                                               \
-	do {                                                                               \
-		hipError_t e__ = hipGetLastError();                                            \
-		if (e__ != hipSuccess) return hip_fail((ctx), e__, "kernel launch");          \
-	} while (0)
-
 int pg_get_leaf_node_index(pg_context *ctx, uint64_t n, const float *p, const uint8_t *active,
                            uint32_t *node_out, void *stream)
 {

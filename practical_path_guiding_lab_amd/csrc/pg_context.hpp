@@ -215,3 +215,17 @@ int hip_fail(pg_context *ctx, hipError_t e, const char *what);
 		hipError_t e__ = (call);                                               \
 		if (e__ != hipSuccess) return pg::hip_fail((ctx), e__, #call);        \
 	} while (0)
+
+// what every query / recording entry point does before it launches, and behind the launch (pg_context.hip, pg_kernels_warp.hip)
+#define PG_READY(ctx)                                                                  \
+	do {                                                                               \
+		if (!(ctx)) return PG_ERR_INVALID;                                             \
+		if (!(ctx)->configured) return pg::fail((ctx), PG_ERR_INVALID, "call pg_setup or pg_import first"); \
+		PG_HIP((ctx), hipSetDevice((ctx)->device));                                    \
+	} while (0)
+
+#define PG_LAUNCHED(ctx)                                                               \
+	do {                                                                               \
+		hipError_t e__ = hipGetLastError();                                            \
+		if (e__ != hipSuccess) return pg::hip_fail((ctx), e__, "kernel launch");      \
+	} while (0)

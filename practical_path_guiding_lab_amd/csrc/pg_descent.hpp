@@ -29,6 +29,15 @@ __device__ __forceinline__ KdNode load_kd(const KdNode *kd, uint32_t i)
 	return n;
 }
 
+__device__ __forceinline__ TreeHead load_head(const TreeHead *h, uint32_t t)
+{
+	const uint2 v = gather8(h + t);
+	TreeHead r;
+	r.root_rec = v.x;
+	r.root_irr = __uint_as_float(v.y);
+	return r;
+}
+
 __device__ __forceinline__ bool inside_root(const TreeView &t, float x, float y, float z)
 {
 	// mi.BoundingBox3f.contains, inclusive; NaN fails (kdtree.py:446-447)

@@ -33,15 +33,6 @@ __device__ __forceinline__ void count_depths(DepthCounters *dc, unsigned kd_lv, 
 	}
 }
 
-__device__ __forceinline__ TreeHead load_head(const TreeHead *h, uint32_t t)
-{
-	const uint2 v = gather8(h + t);
-	TreeHead r;
-	r.root_rec = v.x;
-	r.root_irr = __uint_as_float(v.y);
-	return r;
-}
-
 __global__ __launch_bounds__(kBlock) void k_leaf_index(TreeView t, uint64_t n, const float *__restrict__ p,
                                                        const uint8_t *__restrict__ active,
                                                        uint32_t *__restrict__ node_out)

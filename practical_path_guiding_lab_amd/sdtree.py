@@ -191,6 +191,59 @@ class SDTree:
             ck(fn(*args, torch.cuda.current_stream().cuda_stream))
         return launch
 
+    # ---- sample warping (include/pgsd_warp.h; not in the reference) -------------------------
+    def sampleWarp(self, position: torch.Tensor, u: torch.Tensor, active: Optional[torch.Tensor] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The caller's 2-D points u (float32 (2, N), in [0,1)^2) warped through the quadtree of the KD leaf that holds each
+        position (pg_sample_warp): (direction (3, N), pdf (N,)).  The pdf is what pdf() returns for the direction."""
+        n = position.shape[1]
+        _f32(position, (3, n))
+        _f32(u, (2, n))
+        m, mp = _mask(active, n)
+        d = torch.empty((3, n), dtype=torch.float32, device=self.device)
+        pdf = torch.empty(n, dtype=torch.float32, device=self.device)
+        self._ck(self._lib.pg_sample_warp(self._h, n, position.data_ptr(), u.data_ptr(), mp, d.data_ptr(), pdf.data_ptr(),
+                                          _stream_ptr()))
+        return d, pdf
+
+    def invertWarp(self, position: torch.Tensor, direction: torch.Tensor, active: Optional[torch.Tensor] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The inverse of sampleWarp (pg_invert_warp): (u (2, N), pdf (N,)).  A direction of zero probability has no preimage:
+        its u is the limit point of the empty preimage and its pdf is 0."""
+        n = position.shape[1]
+        _f32(position, (3, n))
+        _f32(direction, (3, n))
+        m, mp = _mask(active, n)
+        u = torch.empty((2, n), dtype=torch.float32, device=self.device)
+        pdf = torch.empty(n, dtype=torch.float32, device=self.device)
+        self._ck(self._lib.pg_invert_warp(self._h, n, position.data_ptr(), direction.data_ptr(), mp, u.data_ptr(), pdf.data_ptr(),
+                                          _stream_ptr()))
+        return u, pdf
+
+    def guideBounceWarp(self, position, dir_nee, nee_active, select, dir_io, u, pdf_nee_out=None, pdf_out=None,
+                        lane_index=None, lane_count=None):
+        """guideBounce with the select == 2 lanes' directions warped from u (float32 (2, N)) instead of drawn from a sampler
+        (pg_guide_bounce_warp)."""
+        n = position.shape[1]
+        _f32(position, (3, n)); _f32(dir_nee, (3, n)); _f32(dir_io, (3, n)); _f32(u, (2, n))
+        na, nap = _mask(nee_active, n)
+        sl, slp = _mask(select, n)
+        if pdf_nee_out is None:
+            pdf_nee_out = torch.empty(n, dtype=torch.float32, device=self.device)
+        if pdf_out is None:
+            pdf_out = torch.empty(n, dtype=torch.float32, device=self.device)
+        lip = lcp = None
+        if (lane_index is None) != (lane_count is None):
+            raise ValueError("lane_index and lane_count go together")
+        if lane_index is not None:
+            if (lane_index.dtype != torch.int32 or lane_count.dtype != torch.int32 or lane_index.numel() < n
+                    or lane_count.numel() < 2):
+                raise ValueError("lane_index must be int32[n], lane_count int32[2] (from compactLanes)")
+            lip, lcp = lane_index.data_ptr(), lane_count.data_ptr()
+        self._ck(self._lib.pg_guide_bounce_warp(self._h, n, position.data_ptr(), dir_nee.data_ptr(), nap, slp, dir_io.data_ptr(),
+                                                u.data_ptr(), pdf_nee_out.data_ptr(), pdf_out.data_ptr(), lip, lcp, _stream_ptr()))
+        return pdf_nee_out, pdf_out
+
     def compactLanes(self, select: torch.Tensor, nee_active: Optional[torch.Tensor] = None,
                      idx_out: Optional[torch.Tensor] = None, count_out: Optional[torch.Tensor] = None):
         """Active-ray stream compaction (pg_compact_lanes): returns (idx int32[n], counts int32[2]);
