@@ -44,6 +44,15 @@ class pg_records_out(C.Structure):
         "position", "direction", "radiance", "wo_pdf", "direction_nee", "radiance_nee_lum")]
 
 
+class pg_fraction_params(C.Structure):  # include/pgsd_fraction.h
+    _fields_ = [("theta0", C.c_float), ("learning_rate", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("epsilon", C.c_float), ("l2", C.c_float), ("loss", C.c_int32)]
+
+
+class pg_fraction_records(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("position", "bsdf_pdf", "guide_pdf", "product", "wo_pdf", "is_delta")]
+
+
 class pg_tree_sizes(C.Structure):
     _fields_ = [("n_kd", C.c_uint64), ("n_quad", C.c_uint64), ("n_roots", C.c_uint64)]
 
@@ -126,10 +135,15 @@ EXPORTS = (
 )
 # every symbol include/pgsd_warp.h declares beside them (sample warping: same library, same ABI version)
 EXPORTS_WARP = ("pg_sample_warp", "pg_invert_warp", "pg_guide_bounce_warp")
+# and every symbol include/pgsd_fraction.h declares (the BSDF sampling fraction learned per KD leaf)
+EXPORTS_FRACTION = ("pg_fraction_enable", "pg_fraction_query", "pg_fraction_record", "pg_fraction_step",
+                    "pg_fraction_accumulators", "pg_fraction_export", "pg_fraction_import")
+PG_FRACTION_LOSS_KL, PG_FRACTION_LOSS_VARIANCE = 0, 1
 
 
 def source_hash() -> str:
-    """sha256 (16 hex digits) over the library's sources (csrc/*.hip, csrc/*.hpp, include/pgsd.h, include/pgsd_warp.h): names the code a
+    """sha256 (16 hex digits) over the library's sources (csrc/*.hip, csrc/*.hpp, include/pgsd.h, include/pgsd_warp.h,
+    include/pgsd_fraction.h): names the code a
     profile was taken of (profiles/pmc_traffic.json) so that bench.py never pairs old counters with new kernels."""
     import glob
     import hashlib
@@ -137,6 +151,7 @@ def source_hash() -> str:
     files = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
     files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd.h"))
     files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_warp.h"))
+    files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_fraction.h"))
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
@@ -239,7 +254,14 @@ def lib() -> C.CDLL:
     L.pg_sample_warp.argtypes = [V, U64, V, V, V, V, V, V]
     L.pg_invert_warp.argtypes = [V, U64, V, V, V, V, V, V]
     L.pg_guide_bounce_warp.argtypes = [V, U64, V, V, V, V, V, V, V, V, V, V, V]
-    for name in EXPORTS + EXPORTS_WARP:
+    L.pg_fraction_enable.argtypes = [V, C.POINTER(pg_fraction_params)]
+    L.pg_fraction_query.argtypes = [V, U64, V, V, V, V]
+    L.pg_fraction_record.argtypes = [V, U64, C.POINTER(pg_fraction_records), V, V]
+    L.pg_fraction_step.argtypes = [V, V]
+    L.pg_fraction_accumulators.argtypes = [V, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pg_fraction_export.argtypes = [V, U64, V, V, V, V, V, V, V]
+    L.pg_fraction_import.argtypes = [V, U64, V, V, V, V, V, V]
+    for name in EXPORTS + EXPORTS_WARP + EXPORTS_FRACTION:
         if name not in ("pg_last_error", "pg_abi_version"):
             getattr(L, name).restype = C.c_int
     _lib = L

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/pgsd.h"
+#include "../../include/pgsd_fraction.h"
 #include "pg_kernels.hpp"
 #include "pg_math.hpp"
 #include "pg_tree.hpp"
@@ -125,6 +126,30 @@ struct Forest {
 	}
 };
 
+// The learned BSDF sampling fraction (include/pgsd_fraction.h, pg_kernels_fraction.hip): off unless pg_fraction_enable switched it
+// on.  One table for the n_trees leaves of the forest, [ acc: n x kAccWords int64 | state: n x FracLeaf ], so that a refine
+// builds the next one in ONE spare buffer and commits it by one pointer swap (pg_refine.hip).
+struct alignas(32) FracLeaf {
+	float theta, m, v, p1, p2;
+	uint32_t steps;
+	uint32_t pad[2];
+};
+static_assert(sizeof(FracLeaf) == 4 * sizeof(long long), "a leaf's state is four words of the table");
+constexpr size_t kFracWords = kAccWords + sizeof(FracLeaf) / sizeof(long long); // words of the table per leaf
+struct Fraction {
+	bool on = false;
+	pg_fraction_params prm = {};
+	DevBuf<long long> tab, spare; // spare: the next refine's table (what a commit replaced)
+	long long *acc() const { return tab.p; }
+	FracLeaf *leaves(uint32_t n_trees) const { return reinterpret_cast<FracLeaf *>(tab.p + (size_t)n_trees * kAccWords); }
+	void disable()
+	{
+		on = false;
+		tab.release();
+		spare.release();
+	}
+};
+
 } // namespace pg
 
 struct pg_render_state; // pg_render.hip (its scene: pg_scene_state.hpp)
@@ -144,6 +169,7 @@ struct pg_context {
 	uint32_t filter_seed = 0;
 	double kd_max_leaf_size = 1.0;
 	pg::Forest f;
+	pg::Fraction frac;               // the learned sampling fraction (disabled by pg_setup / pg_import)
 	pg::DepthCounters *dc = nullptr; // device
 	bool dc_on = false;
 	bool ph_on = false;              // a probe build's phase stamps are on (pg_enable_depth_counters 1 or 2; never in the product build)
@@ -195,6 +221,9 @@ namespace pg {
 // pg_refine.hip
 int refine_and_swap(pg_context *ctx, hipStream_t s);
 int rebuild_jump(pg_context *ctx, hipStream_t s); // after every change of the quadtree records or heads
+// pg_kernels_fraction.hip: the table of the refined forest -- new leaf t takes the state of old leaf tree_src[t], zero accumulators
+void launch_fraction_carry(const long long *old_tab, uint32_t n_old, const uint32_t *tree_src, long long *new_tab, uint32_t n_new,
+                           hipStream_t s);
 // pg_render.hip
 void destroy_render_state(pg_context *ctx);
 // pg_render_wave.hip

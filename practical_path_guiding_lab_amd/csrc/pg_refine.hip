@@ -629,6 +629,14 @@ int refine_and_swap(pg_context *ctx, hipStream_t s)
 	const uint64_t new_acc_count = (uint64_t)off * 4 * kAccWords + (uint64_t)n_trees_new * kAccWords + n_trees_new;
 	PG_HIP(ctx, w.new_acc.ensure(new_acc_count, kGrow));
 	PG_HIP(ctx, hipMemsetAsync(w.new_acc.p, 0, new_acc_count * sizeof(long long), s));
+	// ---- the learned sampling fraction (pgsd_fraction.h), where it is on: the refined forest's table in the spare buffer, every
+	// new leaf with the state of the leaf it is a copy of, zero accumulators; the running table stays until the commit
+	Fraction &fr = ctx->frac;
+	if (fr.on) {
+		PG_HIP(ctx, fr.spare.ensure((size_t)n_trees_new * kFracWords, kGrow));
+		launch_fraction_carry(fr.tab.p, f.n_trees, w.tree_src.p, fr.spare.p, n_trees_new, s);
+		PG_HIP(ctx, hipGetLastError());
+	}
 	PG_HIP(ctx, hipStreamSynchronize(s)); // (the last call of the transaction that can fail)
 
 	// ======== B. commit: pointer swaps and counts, nothing here can fail ========
@@ -640,6 +648,7 @@ int refine_and_swap(pg_context *ctx, hipStream_t s)
 	f.head.swap(w.new_head);
 	f.tree_thr.swap(w.new_thr);
 	f.acc.swap(w.new_acc);
+	if (fr.on) fr.tab.swap(fr.spare);
 	f.n_rec = (uint32_t)off;
 	f.n_trees = n_trees_new;
 	f.n_kd = n_kd_new;

@@ -244,6 +244,80 @@ class SDTree:
                                                 u.data_ptr(), pdf_nee_out.data_ptr(), pdf_out.data_ptr(), lip, lcp, _stream_ptr()))
         return pdf_nee_out, pdf_out
 
+    # ---- the BSDF sampling fraction learned per KD leaf (include/pgsd_fraction.h; not in the reference) ----------------
+    _LOSS = {"kl": N.PG_FRACTION_LOSS_KL, "variance": N.PG_FRACTION_LOSS_VARIANCE}
+
+    def fractionEnable(self, fraction0: float = 0.5, learning_rate: float = 0.01, beta1: float = 0.9, beta2: float = 0.999,
+                       epsilon: float = 1e-8, l2: float = 0.01, loss: str = "kl"):
+        """Switches the learned fraction on with every leaf at fraction0 (pg_fraction_enable): theta0 = log(f / (1 - f)), 0 for
+        0.5.  The defaults are the publication's, chosen there for one Adam step per record; nobody has measured which
+        learning rate suits the batch step of fractionStep.  setup() and load() switch the feature off."""
+        if loss not in self._LOSS:
+            raise ValueError(f"loss must be one of {sorted(self._LOSS)}, got {loss!r}")
+        if not 0.0 < fraction0 < 1.0:
+            raise ValueError("fraction0 must lie strictly between 0 and 1")
+        theta0 = 0.0 if fraction0 == 0.5 else float(np.log(fraction0 / (1.0 - fraction0)))
+        prm = N.pg_fraction_params(max(-20.0, min(20.0, theta0)), learning_rate, beta1, beta2, epsilon, l2, self._LOSS[loss])
+        self._ck(self._lib.pg_fraction_enable(self._h, C.byref(prm)))
+
+    def fractionDisable(self):
+        self._ck(self._lib.pg_fraction_enable(self._h, None))
+
+    def fractionQuery(self, position: torch.Tensor, active: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The BSDF sampling fraction of the KD leaf that holds each position (pg_fraction_query), float32 (N,)."""
+        n = position.shape[1]
+        _f32(position, (3, n))
+        m, mp = _mask(active, n)
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        self._ck(self._lib.pg_fraction_query(self._h, n, position.data_ptr(), mp, out.data_ptr(), _stream_ptr()))
+        return out
+
+    def fractionRecord(self, rec: Dict[str, torch.Tensor], count: Optional[torch.Tensor] = None):
+        """Adds the records' gradients to their leaves' accumulators (pg_fraction_record).  rec: position (3, M); bsdf_pdf,
+        guide_pdf, product, wo_pdf (M,); optionally is_delta (M,) bool / uint8.  count: as addDataPropagate's."""
+        m = rec["position"].shape[1]
+        r = N.pg_fraction_records()
+        r.position = _f32(rec["position"], (3, m)).data_ptr()
+        for k in ("bsdf_pdf", "guide_pdf", "product", "wo_pdf"):
+            setattr(r, k, _f32(rec[k], (m,)).data_ptr())
+        delta, r.is_delta = _mask(rec.get("is_delta"), m)
+        cp = None
+        if count is not None:
+            if count.dtype != torch.int32 or not count.is_cuda:
+                raise ValueError("count must be a CUDA int32 tensor")
+            cp = count.data_ptr()
+        self._ck(self._lib.pg_fraction_record(self._h, m, C.byref(r), cp, _stream_ptr()))
+
+    def fractionStep(self):
+        """One Adam step for every leaf that received records since the last one (pg_fraction_step)."""
+        self._ck(self._lib.pg_fraction_step(self._h, _stream_ptr()))
+
+    def fractionAccumulators(self) -> torch.Tensor:
+        """int64 view of the gradient accumulators (n_roots * 4 words), for an element-wise sum over ranks before fractionStep."""
+        p = C.c_void_p()
+        n = C.c_uint64()
+        self._ck(self._lib.pg_fraction_accumulators(self._h, C.byref(p), C.byref(n)))
+        return _wrap_device_i64(p.value, n.value, self.device)
+
+    def fractionState(self) -> Dict[str, np.ndarray]:
+        """The per-leaf state (pg_fraction_export): theta, m, v, p1, p2 (float32), steps (uint32), acc (int64 (n_roots, 4)),
+        indexed by the tree number export() writes in kdtree_quadTreeRootIndex."""
+        n = int(self.sizes().n_roots)
+        st = {k: np.empty(n, np.float32) for k in ("theta", "m", "v", "p1", "p2")}
+        st["steps"] = np.empty(n, np.uint32)
+        st["acc"] = np.empty((n, 4), np.int64)
+        self._ck(self._lib.pg_fraction_export(self._h, n, *[st[k].ctypes.data for k in ("theta", "m", "v", "p1", "p2", "steps", "acc")]))
+        return st
+
+    def fractionLoadState(self, st: Dict[str, np.ndarray]):
+        """Loads theta, m, v, p1, p2 and steps (pg_fraction_import); the accumulators become zero."""
+        a = [np.ascontiguousarray(st[k], np.float32) for k in ("theta", "m", "v", "p1", "p2")]
+        a.append(np.ascontiguousarray(st["steps"], np.uint32))
+        n = a[0].shape[0]
+        if any(x.shape != (n,) for x in a):
+            raise ValueError("theta, m, v, p1, p2 and steps must have one entry per leaf")
+        self._ck(self._lib.pg_fraction_import(self._h, n, *[x.ctypes.data for x in a]))
+
     def compactLanes(self, select: torch.Tensor, nee_active: Optional[torch.Tensor] = None,
                      idx_out: Optional[torch.Tensor] = None, count_out: Optional[torch.Tensor] = None):
         """Active-ray stream compaction (pg_compact_lanes): returns (idx int32[n], counts int32[2]);
