@@ -139,11 +139,14 @@ EXPORTS_WARP = ("pg_sample_warp", "pg_invert_warp", "pg_guide_bounce_warp")
 EXPORTS_FRACTION = ("pg_fraction_enable", "pg_fraction_query", "pg_fraction_record", "pg_fraction_step",
                     "pg_fraction_accumulators", "pg_fraction_export", "pg_fraction_import")
 PG_FRACTION_LOSS_KL, PG_FRACTION_LOSS_VARIANCE = 0, 1
+# and every symbol include/pgsd_target.h declares (the variance-aware guiding target: sqrt of the leaves' second moments)
+EXPORTS_TARGET = ("pg_target_apply", "pg_target_applied")
+PG_TARGET_SECOND_MOMENT = 1
 
 
 def source_hash() -> str:
     """sha256 (16 hex digits) over the library's sources (csrc/*.hip, csrc/*.hpp, include/pgsd.h, include/pgsd_warp.h,
-    include/pgsd_fraction.h): names the code a
+    include/pgsd_fraction.h, include/pgsd_target.h): names the code a
     profile was taken of (profiles/pmc_traffic.json) so that bench.py never pairs old counters with new kernels."""
     import glob
     import hashlib
@@ -152,6 +155,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd.h"))
     files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_warp.h"))
     files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_fraction.h"))
+    files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_target.h"))
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
@@ -261,7 +265,9 @@ def lib() -> C.CDLL:
     L.pg_fraction_accumulators.argtypes = [V, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pg_fraction_export.argtypes = [V, U64, V, V, V, V, V, V, V]
     L.pg_fraction_import.argtypes = [V, U64, V, V, V, V, V, V]
-    for name in EXPORTS + EXPORTS_WARP + EXPORTS_FRACTION:
+    L.pg_target_apply.argtypes = [V, I32, V]
+    L.pg_target_applied.argtypes = [V, C.POINTER(I32)]
+    for name in EXPORTS + EXPORTS_WARP + EXPORTS_FRACTION + EXPORTS_TARGET:
         if name not in ("pg_last_error", "pg_abi_version"):
             getattr(L, name).restype = C.c_int
     _lib = L

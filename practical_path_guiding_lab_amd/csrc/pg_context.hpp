@@ -170,6 +170,7 @@ struct pg_context {
 	double kd_max_leaf_size = 1.0;
 	pg::Forest f;
 	pg::Fraction frac;               // the learned sampling fraction (disabled by pg_setup / pg_import)
+	int32_t target_applied = 0;      // the target pg_target_apply gave f.acc since the last refine commit / setup / import (pgsd_target.h)
 	pg::DepthCounters *dc = nullptr; // device
 	bool dc_on = false;
 	bool ph_on = false;              // a probe build's phase stamps are on (pg_enable_depth_counters 1 or 2; never in the product build)

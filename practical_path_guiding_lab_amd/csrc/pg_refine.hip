@@ -649,6 +649,7 @@ int refine_and_swap(pg_context *ctx, hipStream_t s)
 	f.tree_thr.swap(w.new_thr);
 	f.acc.swap(w.new_acc);
 	if (fr.on) fr.tab.swap(fr.spare);
+	ctx->target_applied = 0; // (the accumulators a target was applied to are consumed: pgsd_target.h)
 	f.n_rec = (uint32_t)off;
 	f.n_trees = n_trees_new;
 	f.n_kd = n_kd_new;

@@ -363,6 +363,35 @@ class SDTree:
             cp = count.data_ptr()
         self._ck(self._lib.pg_splat(self._h, m, C.byref(r), cp, _stream_ptr()))
 
+    # ---- the variance-aware guiding target (include/pgsd_target.h; not in the reference) ---------------------------------
+    _TARGET = {"second_moment": N.PG_TARGET_SECOND_MOMENT}
+
+    def addSecondMoments(self, rec: Dict[str, torch.Tensor], count: Optional[torch.Tensor] = None):
+        """addDataPropagate of the records' SECOND moments: radiance and radiance_nee_lum are squared (x * x in fp32, one
+        rounding each; the caller's tensors are not written), every other column and the splat filters apply unchanged.
+        Follow the iteration's last record (and the multi-GPU sum) by applyTarget("second_moment"), then refineAndPrepare."""
+        sq = dict(rec)
+        for k in ("radiance", "radiance_nee_lum"):
+            if k in rec:
+                sq[k] = _f32(rec[k], (rec["position"].shape[1],)) * rec[k]
+        self.addDataPropagate(sq, count)
+
+    def applyTarget(self, target: str = "second_moment"):
+        """pg_target_apply: every directional leaf's sum S of sdTree_current becomes 2^-depth * sqrt(S), in place, on the current
+        stream.  Once per iteration, after the last record and after the sum over ranks, before refineAndPrepare; a second
+        call before the refine raises and changes nothing."""
+        if target not in self._TARGET:
+            raise ValueError(f"target must be one of {sorted(self._TARGET)}, got {target!r}")
+        self._ck(self._lib.pg_target_apply(self._h, self._TARGET[target], _stream_ptr()))
+
+    @property
+    def targetApplied(self) -> Optional[str]:
+        """The target applied to the running iteration's accumulators ("second_moment"), or None: cleared by refineAndPrepare,
+        setup and load (pg_target_applied)."""
+        out = C.c_int32(0)
+        self._ck(self._lib.pg_target_applied(self._h, C.byref(out)))
+        return next((k for k, v in self._TARGET.items() if v == out.value), None)
+
     def exportPassRecords(self, slot: int = 0) -> Dict[str, torch.Tensor]:
         """The kept path-vertex records of the most recent render pass of buffer set `slot` (pg_render_export_records): a
         recording pass of a WavefrontScene(record_geometry=True); anything else raises.  Returns the columns addDataPropagate
