@@ -53,6 +53,10 @@ class pg_fraction_records(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("position", "bsdf_pdf", "guide_pdf", "product", "wo_pdf", "is_delta")]
 
 
+class pg_rr_params(C.Structure):  # include/pgsd_radiance.h
+    _fields_ = [("window", C.c_float), ("max_split", C.c_uint32)]
+
+
 class pg_tree_sizes(C.Structure):
     _fields_ = [("n_kd", C.c_uint64), ("n_quad", C.c_uint64), ("n_roots", C.c_uint64)]
 
@@ -142,11 +146,14 @@ PG_FRACTION_LOSS_KL, PG_FRACTION_LOSS_VARIANCE = 0, 1
 # and every symbol include/pgsd_target.h declares (the variance-aware guiding target: sqrt of the leaves' second moments)
 EXPORTS_TARGET = ("pg_target_apply", "pg_target_applied")
 PG_TARGET_SECOND_MOMENT = 1
+# and every symbol include/pgsd_radiance.h declares (radiance estimates and guided Russian roulette / splitting)
+EXPORTS_RADIANCE = ("pg_radiance_enable", "pg_radiance_status", "pg_radiance_export", "pg_radiance_import", "pg_radiance_query",
+                    "pg_radiance_rr")
 
 
 def source_hash() -> str:
     """sha256 (16 hex digits) over the library's sources (csrc/*.hip, csrc/*.hpp, include/pgsd.h, include/pgsd_warp.h,
-    include/pgsd_fraction.h, include/pgsd_target.h): names the code a
+    include/pgsd_fraction.h, include/pgsd_target.h, include/pgsd_radiance.h): names the code a
     profile was taken of (profiles/pmc_traffic.json) so that bench.py never pairs old counters with new kernels."""
     import glob
     import hashlib
@@ -156,6 +163,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_warp.h"))
     files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_fraction.h"))
     files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_target.h"))
+    files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_radiance.h"))
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
@@ -267,7 +275,13 @@ def lib() -> C.CDLL:
     L.pg_fraction_import.argtypes = [V, U64, V, V, V, V, V, V]
     L.pg_target_apply.argtypes = [V, I32, V]
     L.pg_target_applied.argtypes = [V, C.POINTER(I32)]
-    for name in EXPORTS + EXPORTS_WARP + EXPORTS_FRACTION + EXPORTS_TARGET:
+    L.pg_radiance_enable.argtypes = [V, I32]
+    L.pg_radiance_status.argtypes = [V, C.POINTER(I32), C.POINTER(I32), C.POINTER(I32)]
+    L.pg_radiance_export.argtypes = [V, U64, V]
+    L.pg_radiance_import.argtypes = [V, U64, V]
+    L.pg_radiance_query.argtypes = [V, U64, V, V, V, V, V, V]
+    L.pg_radiance_rr.argtypes = [V, U64, V, V, V, V, C.POINTER(pg_rr_params), V, V, V, V, V, V, V]
+    for name in EXPORTS + EXPORTS_WARP + EXPORTS_FRACTION + EXPORTS_TARGET + EXPORTS_RADIANCE:
         if name not in ("pg_last_error", "pg_abi_version"):
             getattr(L, name).restype = C.c_int
     _lib = L

@@ -150,6 +150,24 @@ struct Fraction {
 	}
 };
 
+// Radiance estimates (include/pgsd_radiance.h, pg_kernels_radiance.hip): off unless pg_radiance_enable switched it on.  One uint64
+// per quadtree of sdTree_prev, the number of in-box records its energies were resolved from; a refine builds the next table in the
+// spare buffer and commits it, with the two flags, by one pointer swap (pg_refine.hip).
+struct Radiance {
+	bool on = false;
+	int32_t valid = 0;     // the table describes sdTree_prev (a refine committed it, or pg_radiance_import loaded it)
+	int32_t of_target = 0; // pg_target_applied at the refine that built sdTree_prev: its energies are not radiance
+	DevBuf<unsigned long long> tab, spare; // spare: the next refine's table (what a commit replaced)
+	void disable()
+	{
+		on = false;
+		valid = 0;
+		of_target = 0;
+		tab.release();
+		spare.release();
+	}
+};
+
 } // namespace pg
 
 struct pg_render_state; // pg_render.hip (its scene: pg_scene_state.hpp)
@@ -170,6 +188,7 @@ struct pg_context {
 	double kd_max_leaf_size = 1.0;
 	pg::Forest f;
 	pg::Fraction frac;               // the learned sampling fraction (disabled by pg_setup / pg_import)
+	pg::Radiance rad;                // the quadtrees' statistical weights (disabled by pg_setup / pg_import)
 	int32_t target_applied = 0;      // the target pg_target_apply gave f.acc since the last refine commit / setup / import (pgsd_target.h)
 	pg::DepthCounters *dc = nullptr; // device
 	bool dc_on = false;
@@ -225,6 +244,9 @@ int rebuild_jump(pg_context *ctx, hipStream_t s); // after every change of the q
 // pg_kernels_fraction.hip: the table of the refined forest -- new leaf t takes the state of old leaf tree_src[t], zero accumulators
 void launch_fraction_carry(const long long *old_tab, uint32_t n_old, const uint32_t *tree_src, long long *new_tab, uint32_t n_new,
                            hipStream_t s);
+// pg_kernels_radiance.hip: the weights of the refined forest -- new tree t takes the count resolved for old tree tree_src[t]
+void launch_radiance_carry(const unsigned long long *tree_count, uint32_t n_old, const uint32_t *tree_src, unsigned long long *w_new,
+                           uint32_t n_new, hipStream_t s);
 // pg_render.hip
 void destroy_render_state(pg_context *ctx);
 // pg_render_wave.hip

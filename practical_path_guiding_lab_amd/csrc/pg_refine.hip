@@ -637,6 +637,14 @@ int refine_and_swap(pg_context *ctx, hipStream_t s)
 		launch_fraction_carry(fr.tab.p, f.n_trees, w.tree_src.p, fr.spare.p, n_trees_new, s);
 		PG_HIP(ctx, hipGetLastError());
 	}
+	// ---- the quadtrees' statistical weights (pgsd_radiance.h), where they are on: every new tree with the count that was
+	// resolved for the tree it comes from (w.tree_count, k_resolve_roots), in the spare buffer; the running table stays until the commit
+	Radiance &rad = ctx->rad;
+	if (rad.on) {
+		PG_HIP(ctx, rad.spare.ensure(n_trees_new, kGrow));
+		launch_radiance_carry(w.tree_count.p, f.n_trees, w.tree_src.p, rad.spare.p, n_trees_new, s);
+		PG_HIP(ctx, hipGetLastError());
+	}
 	PG_HIP(ctx, hipStreamSynchronize(s)); // (the last call of the transaction that can fail)
 
 	// ======== B. commit: pointer swaps and counts, nothing here can fail ========
@@ -649,6 +657,11 @@ int refine_and_swap(pg_context *ctx, hipStream_t s)
 	f.tree_thr.swap(w.new_thr);
 	f.acc.swap(w.new_acc);
 	if (fr.on) fr.tab.swap(fr.spare);
+	if (rad.on) {
+		rad.tab.swap(rad.spare);
+		rad.valid = 1;
+		rad.of_target = ctx->target_applied; // (what the new sdTree_prev's energies are: read before the line below clears it)
+	}
 	ctx->target_applied = 0; // (the accumulators a target was applied to are consumed: pgsd_target.h)
 	f.n_rec = (uint32_t)off;
 	f.n_trees = n_trees_new;

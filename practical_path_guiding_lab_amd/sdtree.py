@@ -392,6 +392,76 @@ class SDTree:
         self._ck(self._lib.pg_target_applied(self._h, C.byref(out)))
         return next((k for k, v in self._TARGET.items() if v == out.value), None)
 
+    # ---- radiance estimates and guided Russian roulette / splitting (include/pgsd_radiance.h; not in the reference) ------
+    def radianceEnable(self, on: bool = True):
+        """Switches the quadtrees' statistical weights on (pg_radiance_enable): from the next refineAndPrepare on, every
+        quadtree of sdTree_prev knows how many records its energies were resolved from, and radianceEstimate /
+        radianceRoulette answer.  Until then (or radianceLoadWeights) the weights are unknown and both raise.  setup() and
+        load() switch the feature off."""
+        self._ck(self._lib.pg_radiance_enable(self._h, int(bool(on))))
+
+    def radianceStatus(self) -> Dict[str, object]:
+        """{"enabled": bool, "valid": bool, "of_target": None | "second_moment"} (pg_radiance_status)."""
+        e, v, t = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._ck(self._lib.pg_radiance_status(self._h, C.byref(e), C.byref(v), C.byref(t)))
+        return {"enabled": bool(e.value), "valid": bool(v.value),
+                "of_target": next((k for k, x in self._TARGET.items() if x == t.value), None)}
+
+    def radianceWeights(self) -> np.ndarray:
+        """uint64 (n_roots,): the number of records behind every quadtree of sdTree_prev (pg_radiance_export), indexed by
+        the tree number export() writes in kdtree_quadTreeRootIndex."""
+        n = int(self.sizes().n_roots)
+        w = np.empty(n, np.uint64)
+        self._ck(self._lib.pg_radiance_export(self._h, n, w.ctypes.data))
+        return w
+
+    def radianceLoadWeights(self, w):
+        """Loads the weights of a tree that came from a file (pg_radiance_import), one per quadtree."""
+        w = np.ascontiguousarray(w, np.uint64)
+        if w.ndim != 1:
+            raise ValueError("one weight per quadtree")
+        self._ck(self._lib.pg_radiance_import(self._h, w.shape[0], w.ctypes.data))
+
+    def radianceEstimate(self, position: torch.Tensor, direction: Optional[torch.Tensor] = None,
+                         active: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+        """(L_dir, L_mean), float32 (N,) each (pg_radiance_query): the radiance arriving at `position` from `direction`, and
+        its mean over the sphere.  direction=None: L_dir is None, only the mean is computed and no quadtree is walked."""
+        n = position.shape[1]
+        _f32(position, (3, n))
+        m, mp = _mask(active, n)
+        L_mean = torch.empty(n, dtype=torch.float32, device=self.device)
+        L_dir, dp, lp = None, None, None
+        if direction is not None:
+            dp = _f32(direction, (3, n)).data_ptr()
+            L_dir = torch.empty(n, dtype=torch.float32, device=self.device)
+            lp = L_dir.data_ptr()
+        self._ck(self._lib.pg_radiance_query(self._h, n, position.data_ptr(), dp, mp, lp, L_mean.data_ptr(), _stream_ptr()))
+        return L_dir, L_mean
+
+    def radianceRoulette(self, position: torch.Tensor, direction: torch.Tensor, weight: torch.Tensor, reference: torch.Tensor,
+                         sampler: PCG32Sampler, window: float = 5.0, max_split: int = 1, active: Optional[torch.Tensor] = None
+                         ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(count int32 (N,), scale float32 (N,), L_dir float32 (N,)) (pg_radiance_rr): adjoint-driven Russian roulette and
+        splitting.  weight: the paths' throughput (a luminance) behind the bounce; reference: the estimate of their pixels'
+        values.  A path goes on `count` times (0: it ends) with its throughput multiplied by `scale`; E[count * scale] = 1.
+        One draw of `sampler` per active lane.  max_split=1: roulette only."""
+        n = position.shape[1]
+        _f32(position, (3, n))
+        _f32(direction, (3, n))
+        _f32(weight, (n,))
+        _f32(reference, (n,))
+        if sampler.n != n:
+            raise ValueError("the sampler must have one stream per lane")
+        m, mp = _mask(active, n)
+        count = torch.empty(n, dtype=torch.int32, device=self.device)
+        scale = torch.empty(n, dtype=torch.float32, device=self.device)
+        L_dir = torch.empty(n, dtype=torch.float32, device=self.device)
+        prm = N.pg_rr_params(float(window), int(max_split))
+        self._ck(self._lib.pg_radiance_rr(self._h, n, position.data_ptr(), direction.data_ptr(), weight.data_ptr(),
+                                          reference.data_ptr(), C.byref(prm), sampler.state.data_ptr(), sampler.inc.data_ptr(),
+                                          mp, count.data_ptr(), scale.data_ptr(), L_dir.data_ptr(), _stream_ptr()))
+        return count, scale, L_dir
+
     def exportPassRecords(self, slot: int = 0) -> Dict[str, torch.Tensor]:
         """The kept path-vertex records of the most recent render pass of buffer set `slot` (pg_render_export_records): a
         recording pass of a WavefrontScene(record_geometry=True); anything else raises.  Returns the columns addDataPropagate
