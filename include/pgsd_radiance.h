@@ -93,9 +93,11 @@
  *   of_target != 0 (sdTree_prev then holds roots of second moments, not radiance); a NULL required pointer; for pg_radiance_rr a
  *   window that is not finite or < 1, or a max_split outside 1 .. 65536.  n = 0 does nothing.
  *
- * NOT BUILT: a pg_guide_bounce variant that also returns the estimate; compacted lane lists (pg_compact_lanes); any use by the
- *   library's own renderer (pg_render_pass keeps its throughput-based roulette); estimates from a second-moment tree; and the
- *   npz schema of the tree files does not change -- a host that saves a tree saves pg_radiance_export's array beside it.
+ * ELSEWHERE: pgsd_bounce.h declares pg_bounce, the pg_guide_bounce variant that also returns the estimate of the continuation
+ *   direction (behind the same KD descent, with the list of pg_compact_lanes).
+ * NOT BUILT: compacted lane lists for the two query calls of this header; any use by the library's own renderer (pg_render_pass
+ *   keeps its throughput-based roulette); estimates from a second-moment tree; and the npz schema of the tree files does not
+ *   change -- a host that saves a tree saves pg_radiance_export's array beside it.
  */
 #ifndef PGSD_RADIANCE_H
 #define PGSD_RADIANCE_H

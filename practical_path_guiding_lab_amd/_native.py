@@ -57,6 +57,12 @@ class pg_rr_params(C.Structure):  # include/pgsd_radiance.h
     _fields_ = [("window", C.c_float), ("max_split", C.c_uint32)]
 
 
+class pg_bounce_args(C.Structure):  # include/pgsd_bounce.h
+    _fields_ = [(n, C.c_void_p) for n in (
+        "p", "dir_nee", "nee_active", "mode", "u_select", "u", "rng_state", "rng_inc", "lane_index", "d_lane_count",
+        "dir_io", "select_out", "fraction_out", "pdf_nee_out", "pdf_out", "L_dir_out", "L_mean_out")]
+
+
 class pg_tree_sizes(C.Structure):
     _fields_ = [("n_kd", C.c_uint64), ("n_quad", C.c_uint64), ("n_roots", C.c_uint64)]
 
@@ -149,11 +155,14 @@ PG_TARGET_SECOND_MOMENT = 1
 # and every symbol include/pgsd_radiance.h declares (radiance estimates and guided Russian roulette / splitting)
 EXPORTS_RADIANCE = ("pg_radiance_enable", "pg_radiance_status", "pg_radiance_export", "pg_radiance_import", "pg_radiance_query",
                     "pg_radiance_rr")
+# and the one symbol include/pgsd_bounce.h declares (fraction, selection, guide bounce and radiance estimate behind one KD descent)
+EXPORTS_BOUNCE = ("pg_bounce",)
+PG_BOUNCE_NONE, PG_BOUNCE_PDF, PG_BOUNCE_SAMPLE, PG_BOUNCE_CHOOSE = 0, 1, 2, 3
 
 
 def source_hash() -> str:
     """sha256 (16 hex digits) over the library's sources (csrc/*.hip, csrc/*.hpp, include/pgsd.h, include/pgsd_warp.h,
-    include/pgsd_fraction.h, include/pgsd_target.h, include/pgsd_radiance.h): names the code a
+    include/pgsd_fraction.h, include/pgsd_target.h, include/pgsd_radiance.h, include/pgsd_bounce.h): names the code a
     profile was taken of (profiles/pmc_traffic.json) so that bench.py never pairs old counters with new kernels."""
     import glob
     import hashlib
@@ -164,6 +173,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_fraction.h"))
     files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_target.h"))
     files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_radiance.h"))
+    files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_bounce.h"))
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
@@ -281,7 +291,8 @@ def lib() -> C.CDLL:
     L.pg_radiance_import.argtypes = [V, U64, V]
     L.pg_radiance_query.argtypes = [V, U64, V, V, V, V, V, V]
     L.pg_radiance_rr.argtypes = [V, U64, V, V, V, V, C.POINTER(pg_rr_params), V, V, V, V, V, V, V]
-    for name in EXPORTS + EXPORTS_WARP + EXPORTS_FRACTION + EXPORTS_TARGET + EXPORTS_RADIANCE:
+    L.pg_bounce.argtypes = [V, U64, C.POINTER(pg_bounce_args), V]
+    for name in EXPORTS + EXPORTS_WARP + EXPORTS_FRACTION + EXPORTS_TARGET + EXPORTS_RADIANCE + EXPORTS_BOUNCE:
         if name not in ("pg_last_error", "pg_abi_version"):
             getattr(L, name).restype = C.c_int
     _lib = L

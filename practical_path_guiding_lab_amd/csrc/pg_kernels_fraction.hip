@@ -19,6 +19,7 @@
 #include "../../include/pgsd_fraction.h"
 #include "pg_context.hpp"
 #include "pg_descent.hpp"
+#include "pg_guide_dev.hpp"
 
 #include <cmath>
 #include <vector>
@@ -30,13 +31,7 @@ static_assert(kFBlock == kStageThreads, "stage_kd_planes copies one plane per th
 
 constexpr float kThetaMax = PG_FRACTION_THETA_MAX;
 
-// logistic of pgsd_fraction.h
-__device__ __forceinline__ float logistic_f32(float theta)
-{
-	const float e = exp_f32(0.0f - theta);
-	return 1.0f / (1.0f + e);
-}
-
+// logistic_f32 (the logistic of pgsd_fraction.h): pg_guide_dev.hpp -- pg_kernels_bounce.hip inlines it too
 __device__ __forceinline__ float load_theta(const FracLeaf *leaves, uint32_t tree) { return leaves[tree].theta; }
 
 // ---- query -----------------------------------------------------------------------------------------------------------------

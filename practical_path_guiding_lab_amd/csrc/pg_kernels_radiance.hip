@@ -9,53 +9,15 @@
 #include "../../include/pgsd_radiance.h"
 #include "pg_context.hpp"
 #include "pg_descent.hpp"
+#include "pg_guide_dev.hpp"
 
 namespace pg {
 
 constexpr int kRadBlock = 256;
 static_assert(kRadBlock == kStageThreads, "stage_kd_planes copies one plane per thread");
 
-// The leaf that a record with canonical direction (cx, cy) adds to (addIrradiancePropagate, quadtree.py:398-441; the descent
-// of pdfQuadTree, quadtree.py:1095-1098): the highest-numbered containing child, level by level -- `last` of `quadrant`.  Its
-// energy and depth.  This is not quad_pdf_pre: that one multiplies energies of the LOWEST-numbered containing child on its
-// way; here no product is formed, only the last energy and the number of levels are kept.
-// pre.hit (the direction lies strictly inside a cell of the jump table: no tie on the levels the table covers): an entry that
-// has ended carries the leaf's energy in `irr` and its depth in bits 26-29 of `info` (k_build_jump); one that continues gives
-// the record to go on from, the energy of the node reached, and the cell.  Its "pdf undefined" bit says nothing about energies.
-struct RadLeaf {
-	float e;
-	uint32_t d;
-};
-__device__ __forceinline__ RadLeaf radiance_leaf(const QuadRec *rec, TreeHead head, float cx, float cy, const JumpPre &pre)
-{
-	uint32_t r = head.root_rec;
-	RadLeaf o;
-	o.e = head.root_irr;
-	o.d = 0;
-	float lox = 0.0f, loy = 0.0f, h = 0.5f;
-	if (pre.hit) {
-		r = pre.e.x;
-		o.e = __uint_as_float(pre.e.z);
-		o.d = (pre.e.w >> 26) & 15u;
-		lox = pre.jx; loy = pre.jy;
-		h = 0.5f / (float)(1 << pre.bits); // (an entry that continues took all the levels of the table)
-	}
-	for (int it = 0; it < kMaxLevels && r != kNoRecord; ++it) {
-		const QuadLoad q = load_rec(rec, r);
-		const float mx = lox + h, my = loy + h;
-		int first, last;
-		quadrant(cx, cy, mx, my, first, last);
-		if (last < 0) break; // outside every child: the walk ends at the node it stands on (pgsd_radiance.h)
-		++o.d;
-		o.e = sel4f(last, q.i0, q.i1, q.i2, q.i3);
-		const uint32_t c = sel4u(last, q.c0, q.c1, q.c2, q.c3);
-		if (last == 0 || last == 3) lox = mx;
-		if (last == 0 || last == 1) loy = my;
-		h *= 0.5f;
-		r = c == 0 ? kNoRecord : c;
-	}
-	return o;
-}
+// radiance_leaf (the leaf a record with a canonical direction adds to: its energy and depth): pg_guide_dev.hpp --
+// pg_kernels_bounce.hip inlines it too
 
 // what the decision needs beside the estimate (kDecide)
 struct RrArgs {

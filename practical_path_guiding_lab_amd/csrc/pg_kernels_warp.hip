@@ -9,83 +9,14 @@
 #include "../../include/pgsd_warp.h"
 #include "pg_context.hpp"
 #include "pg_descent.hpp"
+#include "pg_guide_dev.hpp"
 
 namespace pg {
 
 constexpr int kWBlock = 256;
 static_assert(kWBlock == kStageThreads, "stage_kd_planes copies one plane per thread");
 
-constexpr float kOneM = 0.99999994f; // 1 - 2^-24
-static_assert(kOneM < 1.0f && kOneM == 1.0f - 5.9604644775390625e-8f, "the largest float below 1");
-
-__device__ __forceinline__ float clamp_unit(float v) { return v > 0.0f ? (v < kOneM ? v : kOneM) : 0.0f; } // (NaN -> 0)
-
-// the row and column probabilities of one node (pgsd_warp.h: t, b, tot, the uniform fallback)
-struct WarpNode {
-	float eTL, eBL, t, b, tot;
-};
-__device__ __forceinline__ WarpNode warp_node(const QuadLoad &q)
-{
-	WarpNode w;
-	w.eTL = q.i1; w.eBL = q.i2;
-	w.t = q.i0 + q.i1;
-	w.b = q.i2 + q.i3;
-	w.tot = w.t + w.b;
-	if (!(w.tot > 0.0f) || !finite_f32(w.tot)) { w.eTL = 1.0f; w.eBL = 1.0f; w.t = 2.0f; w.b = 2.0f; w.tot = 4.0f; }
-	return w;
-}
-
-// WARP of pgsd_warp.h.  The pdf along the path is accumulated by quad_sample_t's operations (the REAL energies, also where the
-// choice fell back to uniform: the product then meets its 0/0 and the value is 0, as pdfQuadTree's is).
-__device__ __forceinline__ void quad_warp(const QuadRec *rec, JumpRef jump, uint32_t tree, TreeHead head, float ux, float uy,
-                                          float &dx, float &dy, float &dz, float &pdf_out)
-{
-	ux = clamp_unit(ux);
-	uy = clamp_unit(uy);
-	float x0 = 0.0f, y0 = 0.0f, s = 1.0f;
-	float pdf = 1.0f, node_irr = head.root_irr;
-	bool dead = false;
-	uint32_t r = head.root_rec;
-	for (int it = 0; it < kMaxLevels && r != kNoRecord; ++it) {
-		const QuadLoad q = load_rec(rec, r);
-		const WarpNode w = warp_node(q);
-		const float Py = w.t / w.tot;
-		const bool top = uy < Py;
-		float vy = top ? uy / Py : (uy - Py) / (1.0f - Py);
-		const float rs = top ? w.t : w.b, eL = top ? w.eTL : w.eBL;
-		const float Pl = eL / rs;
-		const bool left = ux < Pl;
-		float vx = left ? ux / Pl : (ux - Pl) / (1.0f - Pl);
-		vx = vx < kOneM ? vx : kOneM;
-		vy = vy < kOneM ? vy : kOneM;
-		const int k = top ? (left ? 1 : 0) : (left ? 2 : 3);
-		const float child_irr = sel4f(k, q.i0, q.i1, q.i2, q.i3);
-		if (!dead) {
-			pdf = pdf * ((4.0f * child_irr) / node_irr);
-			if (pdf != pdf) { pdf = 0.0f; dead = true; }
-		}
-		node_irr = child_irr;
-		const float h = s * 0.5f;
-		if (!left) x0 = x0 + h;
-		if (top) y0 = y0 + h;
-		s = h;
-		const uint32_t c = sel4u(k, q.c0, q.c1, q.c2, q.c3);
-		r = c == 0 ? kNoRecord : c;
-		ux = vx;
-		uy = vy;
-	}
-	const float px = x0 + ux * s, py = y0 + uy * s;
-	canonical_to_dir(px, py, dx, dy, dz);
-	float qx, qy;
-	dir_to_canonical(dx, dy, dz, qx, qy);
-	const bool strictly_inside = r == kNoRecord && qx > x0 && qx < x0 + s && qy > y0 && qy < y0 + s;
-	if (strictly_inside) {
-		pdf_out = dead ? 0.0f : pdf * kInvFourPiF;
-	} else {
-		uint32_t lv;
-		pdf_out = quad_pdf(rec, jump, tree, head, qx, qy, lv);
-	}
-}
+// clamp_unit, warp_node and quad_warp (the WARP of pgsd_warp.h): pg_guide_dev.hpp -- pg_kernels_bounce.hip inlines them too
 
 // INVERSE of pgsd_warp.h for the canonical position (cx, cy).  Every level's probabilities are needed, so the jump tables are
 // of no use: the walk starts at the root and forms the pdf on the way by quad_pdf_pre's operations in its order (the lowest-

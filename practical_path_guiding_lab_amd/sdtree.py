@@ -462,6 +462,54 @@ class SDTree:
                                           mp, count.data_ptr(), scale.data_ptr(), L_dir.data_ptr(), _stream_ptr()))
         return count, scale, L_dir
 
+    # ---- a whole guided bounce behind one KD descent (include/pgsd_bounce.h; not in the reference) -------------------------
+    def bounce(self, position, dir_nee, nee_active, dir_io, mode=None, u_select=None, sampler: Optional[PCG32Sampler] = None,
+               u=None, lanes=None, radiance: bool = False, out: Optional[Dict[str, torch.Tensor]] = None
+               ) -> Dict[str, torch.Tensor]:
+        """fractionQuery, the selection u_select > f, guideBounce / guideBounceWarp and radianceEstimate of the continuation
+        direction as ONE kernel (pg_bounce); every output is what that sequence gives, bit for bit.
+        mode: uint8 (N,) of N.PG_BOUNCE_NONE / PDF / SAMPLE / CHOOSE (None: every lane chooses on the device from its leaf's
+        fraction).  u_select: float32 (N,), the numbers the CHOOSE lanes compare with the fraction (None: one draw of
+        `sampler` per CHOOSE lane, PCG32 form only).  sampler: the lanes' PCG32 streams (the PCG32 form); u: float32 (2, N),
+        the warp form (guideBounceWarp's u).  lanes: (lane_index, lane_count) from compactLanes(mode, nee_active).
+        dir_io is written in place where a lane samples.  radiance=True also returns L_dir and L_mean (radianceEnable first).
+        Returns {"select" uint8, "fraction", "pdf_nee", "pdf" float32 (N,)} (+ "L_dir", "L_mean"); `out` may bring any of these
+        tensors pre-allocated (with a list, slots that are not listed keep their contents)."""
+        n = position.shape[1]
+        _f32(position, (3, n)); _f32(dir_nee, (3, n)); _f32(dir_io, (3, n))
+        na, nap = _mask(nee_active, n)
+        md, mdp = _mask(mode, n)
+        a = N.pg_bounce_args()
+        a.p, a.dir_nee, a.dir_io, a.nee_active, a.mode = position.data_ptr(), dir_nee.data_ptr(), dir_io.data_ptr(), nap, mdp
+        if u_select is not None:
+            a.u_select = _f32(u_select, (n,)).data_ptr()
+        if u is not None:
+            a.u = _f32(u, (2, n)).data_ptr()
+        if sampler is not None:
+            if sampler.n != n:
+                raise ValueError("the sampler must have one stream per lane")
+            a.rng_state, a.rng_inc = sampler.state.data_ptr(), sampler.inc.data_ptr()
+        if lanes is not None:
+            lane_index, lane_count = lanes
+            if (lane_index.dtype != torch.int32 or lane_count.dtype != torch.int32 or lane_index.numel() < n
+                    or lane_count.numel() < 2):
+                raise ValueError("lanes must be (int32[n], int32[2]) (from compactLanes)")
+            a.lane_index, a.d_lane_count = lane_index.data_ptr(), lane_count.data_ptr()
+        res = dict(out) if out else {}
+        names = ("select", "fraction", "pdf_nee", "pdf") + (("L_dir", "L_mean") if radiance else ())
+        for k in names:
+            dt = torch.uint8 if k == "select" else torch.float32
+            if k not in res:
+                res[k] = torch.empty(n, dtype=dt, device=self.device)
+            elif res[k].dtype != dt or not res[k].is_cuda or not res[k].is_contiguous() or tuple(res[k].shape) != (n,):
+                raise ValueError(f"out[{k!r}] must be a contiguous CUDA {dt} tensor of shape ({n},)")
+        a.select_out, a.fraction_out = res["select"].data_ptr(), res["fraction"].data_ptr()
+        a.pdf_nee_out, a.pdf_out = res["pdf_nee"].data_ptr(), res["pdf"].data_ptr()
+        if radiance:
+            a.L_dir_out, a.L_mean_out = res["L_dir"].data_ptr(), res["L_mean"].data_ptr()
+        self._ck(self._lib.pg_bounce(self._h, n, C.byref(a), _stream_ptr()))
+        return {k: res[k] for k in names}
+
     def exportPassRecords(self, slot: int = 0) -> Dict[str, torch.Tensor]:
         """The kept path-vertex records of the most recent render pass of buffer set `slot` (pg_render_export_records): a
         recording pass of a WavefrontScene(record_geometry=True); anything else raises.  Returns the columns addDataPropagate
