@@ -132,6 +132,19 @@ struct BvhStack {
 		if (sp >= n_lds) e = ovf[ovf_first + (uint32_t)(sp - n_lds)];
 		return e;
 	}
+	// an any-hit walk's entries are references alone (bvh_node_step): the distance word is neither written nor read
+	__device__ __forceinline__ void push_ref(int sp, uint32_t ref) const
+	{
+		if (sp < n_lds) lds[sp * (2 * kRBlock)] = ref;
+		else ovf[ovf_first + (uint32_t)(sp - n_lds)].x = ref;
+	}
+	__device__ __forceinline__ uint32_t ref_at(int sp) const
+	{
+		const volatile LdsWord *w = lds + (sp < n_lds ? sp : n_lds - 1) * (2 * kRBlock); // (see at)
+		uint32_t r = w[0];
+		if (sp >= n_lds) r = ovf[ovf_first + (uint32_t)(sp - n_lds)].x;
+		return r;
+	}
 };
 __device__ __forceinline__ BvhStack bvh_stack(uint2 *lds_column, uint2 *ovf, uint32_t ovf_first, int n_lds = kLdsStack)
 {
@@ -195,7 +208,14 @@ __device__ __forceinline__ void bvh_cswap(float &ta, uint32_t &ra, float &tb, ui
 
 // ---- ray casting ----
 // kAny: the caller asks whether anything is hit (shadow rays): the BVH walk stops at its first
-// triangle.  The answer is that of the closest-hit walk, which visits the same nodes until then.
+// triangle.  The answer -- a boolean, no caller uses the triangle -- is that of the closest-hit walk, but the steps
+// are not: an any-hit walk takes the children of a node in child order, unsorted (bvh_node_step<., true>).  No order
+// can change its answer.  Until the first triangle is found, and then the walk is over, the ray keeps its length
+// (bt = tmax); a child is pushed only if the ray reaches its box under that length, so the test of bvh_pop would hold
+// for every entry and nothing is ever dropped; a node is therefore opened if and only if the ray reaches the boxes of
+// all its ancestors, which no order enters, and the triangle tests are the same function of the same data.  An
+// unoccluded ray makes exactly the (node, triangle) tests of the ordered walk; an occluded one finds some occluder
+// either way -- which one, and after how many steps, may differ.  (tests/test_walk_model.py restates this in numpy.)
 
 // The shapes outside the BVH (quads, spheres, boxes), tested one after the other: updates bt / best.
 template <int kGeneral>
@@ -280,7 +300,8 @@ __device__ __forceinline__ void intersect_linear(const Shapes &sh, v3 o, v3 d, f
 // the reference itself, no node is read for it -- and the others wait on the stack with their entry
 // distance, farthest at the bottom, to be dropped when popped if the ray has become shorter than that.
 // The oracle visits the same nodes in the same order, so the first of several equally near triangles
-// is the same one in both.  pg_scene_set_ex has checked the tree: children follow their parent, and no
+// is the same one in both.  (An any-hit walk keeps no order and no distances: see "ray casting" above.)
+// pg_scene_set_ex has checked the tree: children follow their parent, and no
 // root-to-node path can leave more than kLdsStack + kOvfStack siblings waiting, so the walk opens every
 // node at most once and the stack cannot overflow; the budget is a second fence.
 struct BvhWalk {
@@ -313,8 +334,8 @@ __device__ __forceinline__ void bvh_begin(BvhWalk &w, const Shapes &sh, v3 o, v3
 	w.next = 0; // the root
 }
 
-// w.next is a node: test its children, push the farther ones, go on in the nearest
-template <bool kSlim = false>
+// w.next is a node: test its children, push the farther ones, go on in the nearest (kAny: push the later ones, go on in the first)
+template <bool kSlim = false, bool kAny = false>
 __device__ __forceinline__ void bvh_node_step(BvhWalk &w, const Shapes &sh, const BvhStack &stk)
 {
 	const float kInf = __builtin_huge_valf();
@@ -336,6 +357,10 @@ __device__ __forceinline__ void bvh_node_step(BvhWalk &w, const Shapes &sh, cons
 	// The walks are bound by the texture-address path -- seven 16-byte gathers per lane and node, 16 cycles of the unit
 	// each, whether they hit the L1 or not.  The nodes most rays open (mesh.build_bvh numbers them first) are read from a
 	// copy in LDS instead: closest hits 15.1 -> 11.9 ms per step of veach-ajar, shadow rays 7.9 -> 7.0 with 32 nodes.
+	// (Measured and removed: ONE arm per wave -- a wave with any lane outside the copy gathers every lane's rows from the table,
+	// so that a mixed wave does not issue both load groups with a drained wait between them.  k_wave_trace did not move, the
+	// step 44.28 -> 44.26 ms; in k_wave_shade the vote costs the register that costs the fifth wave.
+	// profiles/bvh_walk/README.md)
 	if (w.next < stk.n_top) {
 		const LdsQuad *T = stk.top + w.next * (uint32_t)kBvhNodeQuads;
 #define PG_Q(r) ({ const u32x4_t q_ = T[r]; make_uint4(q_.x, q_.y, q_.z, q_.w); })
@@ -360,6 +385,24 @@ __device__ __forceinline__ void bvh_node_step(BvhWalk &w, const Shapes &sh, cons
 	if (!(r1 != kBvhNone && h1)) { r1 = kBvhNone; t1 = kInf; }
 	if (!(r2 != kBvhNone && h2)) { r2 = kBvhNone; t2 = kInf; }
 	if (!(r3 != kBvhNone && h3)) { r3 = kBvhNone; t3 = kInf; }
+	if (kAny) {
+		// An any-hit walk's answer does not depend on the order of its steps (see "ray casting" above), so nothing is sorted and
+		// no distance is kept: the walk goes on in the first child the ray reaches, in child order, and the later ones wait as
+		// references alone.  Going on in the NEAREST child instead (one minimum over four, for the early exit of occluded rays)
+		// was measured too, and so was the full sort with references alone: the step of veach-ajar 44.16 -> 43.95 and 44.06 ms
+		// where this form gives 42.89 -- the lanes of a spatially sorted wave that stand at the same node go on in the same
+		// child, whatever side they look at it from.  profiles/bvh_walk/README.md
+		const bool n0 = r0 != kBvhNone, n1 = !n0 && r1 != kBvhNone, n2 = !n0 && !n1 && r2 != kBvhNone;
+		w.next = n0 ? r0 : (n1 ? r1 : (n2 ? r2 : r3));
+		if (n1) r1 = kBvhNone;
+		if (n2) r2 = kBvhNone;
+		if (!n0 && !n1 && !n2) r3 = kBvhNone;
+		if (r3 != kBvhNone) { stk.push_ref(w.sp, r3); ++w.sp; }
+		if (r2 != kBvhNone) { stk.push_ref(w.sp, r2); ++w.sp; }
+		if (r1 != kBvhNone) { stk.push_ref(w.sp, r1); ++w.sp; }
+		--w.budget;
+		return;
+	}
 	bvh_cswap(t0, r0, t1, r1);
 	bvh_cswap(t2, r2, t3, r3);
 	bvh_cswap(t0, r0, t2, r2);
@@ -393,6 +436,10 @@ __device__ __forceinline__ void bvh_tri_test(BvhWalk &w, v3 v0, v3 e1, v3 e2, in
 __device__ __forceinline__ void bvh_leaf_step(BvhWalk &w, const Shapes &sh, int tri_base)
 {
 	const uint32_t first = bvh_leaf_first(w.next), count = bvh_leaf_count(w.next);
+	// (Measured and removed: for the leaves of one or two triangles -- all that mesh.build_bvh makes -- BOTH triangles asked for
+	// before the first is tested, one round trip per leaf.  Eighteen values in flight cost k_wave_trace six registers and a wave
+	// (69 -> 75), k_wave_shade its fifth wave (96 -> 98) and k_wave_cast 12 bytes of scratch in the leanest of four forms tried;
+	// as built the step went 44.08 -> 46.62 ms.  profiles/bvh_walk/README.md)
 	for (uint32_t i = first; i < first + count; ++i) {
 		const float *T = sh.tris + (size_t)i * kTriStride;
 		v3 v0 = ld3(T + TRI_V0);
@@ -405,9 +452,18 @@ __device__ __forceinline__ void bvh_leaf_step(BvhWalk &w, const Shapes &sh, int 
 }
 
 // the nearest waiting child the (now shorter) ray still reaches, or kBvhNone: the walk is over
+template <bool kAny = false>
 __device__ __forceinline__ void bvh_pop(BvhWalk &w, const BvhStack &stk)
 {
 	w.next = kBvhNone;
+	if (kAny) { // (no entry of an any-hit walk is ever dropped: the ray is as long as it was when the entry was pushed)
+		if (w.sp && w.budget > 0) {
+			--w.sp;
+			w.next = stk.ref_at(w.sp);
+			--w.budget;
+		}
+		return;
+	}
 	while (w.sp && w.next == kBvhNone && w.budget > 0) {
 		--w.sp;
 		const uint2 e = stk.at(w.sp);
@@ -433,14 +489,14 @@ __device__ __forceinline__ int intersect(const Shapes &sh, v3 o, v3 d, float tma
 			// idling until the other lanes of its wave have found their leaves: closest hits 16.4 -> 15.6 ms per step,
 			// shadow rays 9.5 -> 8.6; the ray's own sequence of steps is the same)
 			while (!(w.next & kBvhLeafBit) && w.budget > 0) {
-				bvh_node_step<kSlim>(w, sh, stk);
-				if (w.next == kBvhNone) bvh_pop(w, stk);
+				bvh_node_step<kSlim, kAny>(w, sh, stk);
+				if (w.next == kBvhNone) bvh_pop<kAny>(w, stk);
 			}
 			if (w.next != kBvhNone && (w.next & kBvhLeafBit)) {
 				bvh_leaf_step(w, sh, tri_base);
 				if (kAny && w.best >= 0) break; // a shadow ray needs one occluder, not the nearest
 			}
-			bvh_pop(w, stk);
+			bvh_pop<kAny>(w, stk);
 			if (w.next == kBvhNone) break;
 		}
 		bt = w.bt; best = w.best;

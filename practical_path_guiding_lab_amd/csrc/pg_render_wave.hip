@@ -335,15 +335,15 @@ __global__ __launch_bounds__(kRBlock) __attribute__((amdgpu_waves_per_eu(7))) vo
 		if (has) {
 			bool done = false;
 			while (!(w.next & kBvhLeafBit) && w.budget > 0) { // (see intersect)
-				bvh_node_step(w, sh, stk);
-				if (w.next == kBvhNone) bvh_pop(w, stk);
+				bvh_node_step<false, true>(w, sh, stk);
+				if (w.next == kBvhNone) bvh_pop<true>(w, stk);
 			}
 			if (w.next != kBvhNone && (w.next & kBvhLeafBit)) {
 				bvh_leaf_step(w, sh, tri_base);
 				if (w.best >= 0) done = true; // a shadow ray needs one occluder, not the nearest
 			}
 			if (!done) {
-				bvh_pop(w, stk);
+				bvh_pop<true>(w, stk);
 				if (w.next == kBvhNone) done = true;
 			}
 			if (done) {
