@@ -674,6 +674,28 @@ int pg_bsdf_probe(pg_context *ctx, uint64_t n, uint64_t n_mat, const float *d_ma
                   const float *d_wi, const float *d_wo, const float *d_u, int32_t level, float *d_value, float *d_pdf,
                   float *d_sampled_wo, float *d_sampled_pdf, float *d_weight, float *d_eta, int32_t *d_delta, void *stream);
 
+/* The renderer's description of the surface at a hit by itself, for tests: lane i is a hit of shape d_prim[i] of the scene set
+ * on the context by the ray (d_origin[3 i ..], d_dir[3 i ..]) at distance d_t[i], with the barycentrics d_uv[2 i], d_uv[2 i + 1]
+ * where the shape is a triangle (what pg_scene_intersect reports for that ray), and d_ref[3 i ..] is the previous path vertex.
+ * The lane goes through the very device functions the render kernels call at every vertex, at the scene's feature level:
+ * the surface (point, shading and geometric normal, material, texture), the normal recomputed from the point alone, the
+ * shading frame, the ray direction taken into it and back, and the density emitter sampling has for the hit.
+ * d_out: PG_SURFACE_PROBE_FLOATS floats per lane --
+ *   0 p, 3 n (shading normal), 6 ng (geometric normal), 9 reflectance (a texture's colour where the material has one),
+ *   12 emitted radiance, 15 the normal of the shape at p as the next bounce recomputes it, 18 the solid-angle density of
+ *   emitter sampling from d_ref for this hit times 1 / (number of emitters) where the shape is an emitter, else 0,
+ *   19 s, 22 t of the frame (s, t, n), 25 wi = -d_dir in the frame, 28 wi taken back to the world;
+ * d_flags: four int32 per lane -- the material's row (-1 at feature level 0, whose kernels read none), its type as the level
+ * reads it, one-sided (0 / 1), emitter (0 / 1).
+ * A lane whose shape is an emitter divides by the number of emitters, which is then at least 1: the scene's emitter list is made
+ * from the same flags.  The shape numbers are read back and checked against the scene before a lane follows one; any float
+ * input (NaN, infinities, the zero direction) is safe.  n = 0 does nothing; n > 2^20, a shape number outside
+ * [0, shapes of the scene), a context without a scene and a NULL pointer are refused.  All pointers are device pointers.
+ * Synchronises the stream (before reading the shape numbers back, and after the kernel). */
+#define PG_SURFACE_PROBE_FLOATS 31
+int pg_surface_probe(pg_context *ctx, uint64_t n, const int32_t *d_prim, const float *d_origin, const float *d_dir,
+                     const float *d_t, const float *d_uv, const float *d_ref, float *d_out, int32_t *d_flags, void *stream);
+
 /* Per-kernel device time of pg_render_pass, measured with HIP events recorded on the launch
  * stream around each kernel (off by default).  pg_read_kernel_timing synchronises. */
 typedef struct pg_kernel_timing {

@@ -576,6 +576,60 @@ def intersect(scene_obj, o, d, tmax=None):
     return t, prim, u, v, waiting
 
 
+SURFACE_FIELDS = (("p", 0, 3), ("n", 3, 3), ("ng", 6, 3), ("refl", 9, 3), ("radiance", 12, 3), ("normal_at", 15, 3),
+                  ("emitter_pdf", 18, 1), ("s", 19, 3), ("t", 22, 3), ("wi", 25, 3), ("back", 28, 3))
+SURFACE_FLAGS = ("row", "type", "one_sided", "is_em")
+SURFACE_FLOATS = 31
+
+
+def feature_level(scene_obj) -> int:
+    """The feature level pg_scene_set_ex gives a scene (csrc/pg_scene.hip check_and_pack: decided by what the shapes USE):
+    1 with spheres or a rough conductor, 2 with meshes, 3 with any other non-diffuse type, a one-sided row or a
+    directional light, else 0."""
+    m = scene_obj.materials
+    level = 1 if len(scene_obj.spheres) else 0
+    tris = np.asarray(getattr(scene_obj, "tris", np.zeros((0, 16))), np.float32).reshape(-1, 16)
+    if m is not None:
+        m = np.asarray(m, np.float32)
+        used = np.unique(np.concatenate([np.asarray(scene_obj.quads, np.float32).reshape(-1, 24)[:, 22],
+                                         np.asarray(scene_obj.spheres, np.float32).reshape(-1, 12)[:, 4],
+                                         np.asarray(scene_obj.boxes, np.float32).reshape(-1, 32)[:, 21], tris[:, 12]]).astype(int))
+        if (m[used, 0] == 1).any():
+            level = max(level, 1)
+        if (m[used, 0] >= 2).any() or (m[used, 11] != 0).any():
+            level = 3
+    if len(getattr(scene_obj, "dir_lights", ())):
+        level = 3
+    return max(level, 2) if tris.shape[0] else level
+
+
+def split_surface(out, flags):
+    """the probe's two arrays as a dict of named columns (SURFACE_FIELDS, SURFACE_FLAGS)"""
+    r = {k: (out[:, a:a + w].copy() if w > 1 else out[:, a].copy()) for k, a, w in SURFACE_FIELDS}
+    r.update({k: flags[:, i].copy() for i, k in enumerate(SURFACE_FLAGS)})
+    return r
+
+
+def surface_probe(scene_obj, prim, o, d, t, ref, level=None):
+    """pgo_surface_probe: prim (n,) int32 shape numbers of the scene, o, d, ref (n,3), t (n,) float32 -> dict of the columns
+    SURFACE_FIELDS (float32) and SURFACE_FLAGS (int32).  level: the device's feature level (None: feature_level(scene))."""
+    lb = lib()
+    lb.pgo_surface_probe.argtypes = [C.POINTER(_Scene), C.c_size_t, C.c_int] + [_P] * 7
+    lb.pgo_surface_probe.restype = None
+    sc, keep = _scene_struct(scene_obj, None, None, None, None)
+    prim = np.ascontiguousarray(prim, np.int32).reshape(-1)
+    n = prim.shape[0]
+    n_shapes = keep[0].shape[0] + keep[1].shape[0] + 6 * keep[3].shape[0] + keep[4].shape[0]
+    assert n == 0 or (prim.min() >= 0 and prim.max() < n_shapes)
+    o, d, ref = (np.ascontiguousarray(x, np.float32).reshape(n, 3) for x in (o, d, ref))
+    t = np.ascontiguousarray(t, np.float32).reshape(n)
+    out, flags = np.zeros((n, SURFACE_FLOATS), np.float32), np.zeros((n, 4), np.int32)
+    lb.pgo_surface_probe(C.byref(sc), n, feature_level(scene_obj) if level is None else int(level), _ptr(prim), _ptr(o), _ptr(d),
+                         _ptr(t), _ptr(ref), _ptr(out), _ptr(flags))
+    del keep
+    return split_surface(out, flags)
+
+
 def render_pass(pair: "OracleSDTreePair", quads, cam, max_depth, rr_depth, iteration, is_final, seed, spp=1,
                 store_nee=True, bsdf_sampling_fraction=0.5, sumL=None, sumL2=None, spheres=None, materials=None,
                 boxes=None):

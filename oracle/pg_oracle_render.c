@@ -268,7 +268,7 @@ static v3 box_face_normal(const float *B, int face)
 
 /* ---- surface description at a hit ---- */
 typedef struct { int type; v3 refl; float alpha; v3 eta, k; int one_sided; int tex; } material;
-typedef struct { v3 p, n, ng; int is_em; v3 radiance; material m; } surface; /* n: shading normal, ng: geometric */
+typedef struct { v3 p, n, ng; int is_em; v3 radiance; material m; int row; } surface; /* n: shading normal, ng: geometric; row: of the material table, -1: none */
 
 static material load_material(const float *M)
 {
@@ -336,7 +336,7 @@ static surface surface_at(const pgo_scene *sc, int prim, v3 o, v3 d, float t)
 		s.n = ld3(Q + 9);
 		s.is_em = Q[15] != 0.0f;
 		s.radiance = ld3(Q + 19);
-		if (!sc->materials) { s.m.type = 0; s.m.refl = ld3(Q + 16); return s; }
+		if (!sc->materials) { s.m.type = 0; s.m.refl = ld3(Q + 16); s.row = -1; return s; }
 		mi = (int)Q[22];
 	} else if ((size_t)prim >= sc->n_quads + sc->n_spheres + 6 * sc->n_boxes) {
 		const size_t ti = (size_t)prim - sc->n_quads - sc->n_spheres - 6 * sc->n_boxes;
@@ -344,6 +344,7 @@ static surface surface_at(const pgo_scene *sc, int prim, v3 o, v3 d, float t)
 		s.p = vadd(o, vscale(d, t));
 		s.n = ld3(T + 9); /* face normal */
 		mi = (int)T[12];
+		s.row = mi;
 		s.m = load_material(sc->materials + (size_t)mi * PGO_MATERIAL_STRIDE);
 		const int textured = s.m.tex > 0 && sc->tri_uvs;
 		if (sc->tri_normals || textured) { /* the barycentrics of the hit, by the intersection's own formulas */
@@ -391,6 +392,7 @@ static surface surface_at(const pgo_scene *sc, int prim, v3 o, v3 d, float t)
 		s.radiance = ld3(S + 6);
 		mi = (int)S[4];
 	}
+	s.row = mi;
 	s.m = load_material(sc->materials + (size_t)mi * PGO_MATERIAL_STRIDE);
 	return s;
 }
@@ -418,6 +420,54 @@ static float emitter_hit_pdf(const pgo_scene *sc, int prim, v3 ref, v3 p, v3 n, 
 		else pdf = (d2 / fabsf(dp)) / ((4.0f * PI_F) * (S[3] * S[3]));
 	}
 	return pdf * inv_count;
+}
+
+/* The geometric normal of shape `prim` at its surface point p, from the shape's row and p alone: what a next bounce that
+ * keeps only (prim, p) of a vertex has to offset its ray by (the render pass above carries ng along instead; the two must agree
+ * bit for bit, which tests/test_surface_model.py asks) */
+static v3 normal_at(const pgo_scene *sc, int prim, v3 p)
+{
+	const size_t first_box = sc->n_quads + sc->n_spheres, first_tri = first_box + 6 * sc->n_boxes;
+	if ((size_t)prim >= first_tri) return ld3(sc->tris + ((size_t)prim - first_tri) * PGO_TRI_STRIDE + 9);
+	if ((size_t)prim >= first_box) return box_face_normal(sc->boxes + (((size_t)prim - first_box) / 6) * PGO_BOX_STRIDE, (int)(((size_t)prim - first_box) % 6));
+	if ((size_t)prim < sc->n_quads) return ld3(sc->quads + (size_t)prim * PGO_QUAD_STRIDE + 9);
+	return normalize3(vsub(p, ld3(sc->spheres + ((size_t)prim - sc->n_quads) * PGO_SPHERE_STRIDE)));
+}
+
+/* The surface at a hit by itself: lane i goes through surface_at, the ng substitution of the render pass, the frame,
+ * to_local / to_world and emitter_hit_pdf exactly as a vertex of pgo_render_pass_scene does (layout: pg_oracle_render.h). */
+void pgo_surface_probe(const pgo_scene *sc, size_t n, int level, const int32_t *prim, const float *origin, const float *dir,
+                       const float *t, const float *ref, float *out, int32_t *flags)
+{
+	size_t n_em = sc->n_dir_lights; /* the emitters of the render pass: flagged quads, flagged spheres, directional lights */
+	for (size_t q = 0; q < sc->n_quads; ++q) n_em += sc->quads[q * PGO_QUAD_STRIDE + 15] != 0.0f;
+	for (size_t s = 0; s < sc->n_spheres; ++s) n_em += sc->spheres[s * PGO_SPHERE_STRIDE + 5] != 0.0f;
+	const float inv_em_count = n_em > 0 ? 1.0f / (float)n_em : 0.0f;
+	for (size_t i = 0; i < n; ++i) {
+		const v3 ray_d = ld3(dir + 3 * i);
+		surface sf = surface_at(sc, prim[i], ld3(origin + 3 * i), ray_d, t[i]);
+		if (sf.ng.x == 0.0f && sf.ng.y == 0.0f && sf.ng.z == 0.0f) sf.ng = sf.n;
+		frame fr;
+		fr.n = sf.n;
+		frame_from_normal(sf.n, &fr.s, &fr.t);
+		const v3 wi = to_local(&fr, V(-ray_d.x, -ray_d.y, -ray_d.z));
+		const v3 back = to_world(&fr, wi);
+		const v3 nat = normal_at(sc, prim[i], sf.p);
+		const float pdf = sf.is_em ? emitter_hit_pdf(sc, prim[i], ld3(ref + 3 * i), sf.p, sf.n, inv_em_count) : 0.0f;
+		const v3 rows[11] = { sf.p, sf.n, sf.ng, sf.m.refl, sf.radiance, nat, V(pdf, 0, 0), fr.s, fr.t, wi, back };
+		float *o = out + PGO_SURFACE_PROBE_FLOATS * i;
+		int k = 0;
+		for (int r = 0; r < 11; ++r) {
+			o[k++] = rows[r].x;
+			if (r == 6) continue; /* the pdf is one float */
+			o[k++] = rows[r].y;
+			o[k++] = rows[r].z;
+		}
+		flags[4 * i] = level == 0 ? -1 : sf.row;
+		flags[4 * i + 1] = sf.m.type;
+		flags[4 * i + 2] = sf.m.one_sided;
+		flags[4 * i + 3] = sf.is_em;
+	}
 }
 
 /* scene.sample_emitter_direction(si, (e1, e2), test_visibility=True): uniform choice of one

@@ -130,6 +130,19 @@ void pgo_render_pass_scene(const pgo_tree *prev, pgo_tree *current, const pgo_sc
 void pgo_intersect(const pgo_scene *scene, size_t n, const float *origin, const float *dir, const float *tmax, float *t_out,
                    int32_t *prim_out, float *u_out, float *v_out, int32_t *waiting_out);
 
+/* The surface description of the render pass by itself: lane i is a hit of shape prim[i] (a valid shape number: the caller
+ * checks) by the ray (origin[3 i ..], dir[3 i ..]) at t[i], and ref[3 i ..] is the previous path vertex.  Triangles recompute
+ * their barycentrics from the ray, as the render pass does.  out: PGO_SURFACE_PROBE_FLOATS floats per lane --
+ *   0 p, 3 n (shading), 6 ng (geometric, n where the shape has no other), 9 reflectance (a texture's colour where there is one),
+ *   12 emitted radiance, 15 the geometric normal recomputed from (prim, p) alone, 18 the solid-angle density emitter sampling
+ *   from ref has for this hit times 1 / emitters (0 unless the shape is an emitter), 19 s, 22 t of the frame on n,
+ *   25 wi = to_local(-dir), 28 to_world(wi);
+ * flags: four per lane -- the material row (-1: no table, or level == 0, whose device kernels read none), its type,
+ * one-sided, emitter.  `level`: the feature level of the device kernels the scene runs on; it decides the row number only. */
+#define PGO_SURFACE_PROBE_FLOATS 31
+void pgo_surface_probe(const pgo_scene *scene, size_t n, int level, const int32_t *prim, const float *origin, const float *dir,
+                       const float *t, const float *ref, float *out, int32_t *flags);
+
 /* Texture `index` of the scene at (u, v): the reflectance a textured material takes there. */
 void pgo_texture_eval(const pgo_scene *scene, int index, float u, float v, float rgb[3]);
 

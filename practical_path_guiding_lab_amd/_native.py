@@ -141,7 +141,7 @@ EXPORTS = (
     "pg_render_split_pipeline", "pg_comm_info", "pg_exchange_pack", "pg_exchange_unpack", "pg_exchange_pack_words",
     "pg_exchange_unpack_words", "pg_sort_places", "pg_debug_fail_alloc", "pg_debug_fail_alloc_pending",
     "pg_read_shade_phases", "pg_set_splat_filter", "pg_render_record_geometry", "pg_render_export_records",
-    "pg_scene_intersect", "pg_bsdf_probe",
+    "pg_scene_intersect", "pg_bsdf_probe", "pg_surface_probe",
 )
 # every symbol include/pgsd_warp.h declares beside them (sample warping: same library, same ABI version)
 EXPORTS_WARP = ("pg_sample_warp", "pg_invert_warp", "pg_guide_bounce_warp")
@@ -269,6 +269,7 @@ def lib() -> C.CDLL:
     L.pg_sort_places.argtypes = [V, U64, V, V, V, V]
     L.pg_scene_intersect.argtypes = [V, U64, V, V, V, I32, I32, V, V, V, V]
     L.pg_bsdf_probe.argtypes = [V, U64, U64, V, V, V, V, V, I32, V, V, V, V, V, V, V, V]
+    L.pg_surface_probe.argtypes = [V, U64, V, V, V, V, V, V, V, V, V]
     L.pg_render_reserve.argtypes = [V, U64]
     L.pg_render_split_pipeline.argtypes = [V, C.c_int32]
     L.pg_render_record_geometry.argtypes = [V, I32]

@@ -2,8 +2,10 @@
 // of pg_render_dev.hpp -- the function the render kernels call, not a copy -- in the three forms those kernels give its walk:
 // the ray-casting kernels' (kLdsStack stack entries and kBvhTopNodes nodes in LDS), k_wave_shade's (kShadeStack entries,
 // kShadeTopNodes nodes, the kSlim walk) and one without staged nodes.  pg_bsdf_probe: the BSDF layer by itself -- one
-// (material row, wi, wo, u) per lane through load_material, bsdf_eval_pdf<> and bsdf_sample<> of the same header.  Nothing of
-// the product path launches these kernels.
+// (material row, wi, wo, u) per lane through load_material, bsdf_eval_pdf<> and bsdf_sample<> of the same header.
+// pg_surface_probe: the surface at a hit by itself -- one (shape, ray, t, barycentrics, previous vertex) per lane through
+// surface_at<>, normal_at<>, make_frame, to_local, to_world and emitter_hit_pdf<> as stage_a1 calls them.  Nothing of the
+// product path launches these kernels.
 #include <vector>
 
 #include "pg_render_dev.hpp"
@@ -100,7 +102,97 @@ __global__ __launch_bounds__(kRBlock) void k_probe_bsdf(BsdfProbeArgs p)
 	p.s_delta[tid] = delta ? 1 : 0;
 }
 
+struct SurfaceProbeArgs {
+	Shapes shapes;
+	const float *mats;
+	uint64_t n;
+	int n_emitters;
+	const int32_t *prim;            // (n) shape of lane i: checked against the shape count on the host
+	const float *o, *d, *t, *uv, *ref; // (n,3), (n,3), (n), (n,2), (n,3)
+	float *out;                     // (n, PG_SURFACE_PROBE_FLOATS)
+	int32_t *flags;                 // (n,4)
+};
+
+// No loop; every address is a function of tid < n and of a checked shape number (the rows a shape names -- material, texture,
+// texels -- were checked by pg_scene_set_ex, and texture_eval wraps its texel indices into the bitmap whatever the uv are).
+template <int kLevel>
+__global__ __launch_bounds__(kRBlock) void k_probe_surface(SurfaceProbeArgs p)
+{
+	const uint64_t tid = (uint64_t)blockIdx.x * kRBlock + threadIdx.x;
+	if (tid >= p.n) return;
+	const int prim = p.prim[tid];
+	const v3 ray_o = ld3(p.o + 3 * tid), ray_d = ld3(p.d + 3 * tid), prev_p = ld3(p.ref + 3 * tid);
+	const Surface sf = surface_at<kLevel>(p.shapes, p.mats, prim, ray_o, ray_d, p.t[tid], p.uv[2 * tid], p.uv[2 * tid + 1]);
+	const v3 n = sf.n;
+	const Frame fr = make_frame(n);
+	const v3 wi = to_local(fr, V(-ray_d.x, -ray_d.y, -ray_d.z));
+	const v3 back = to_world(fr, wi);
+	const v3 nat = normal_at<kLevel>(p.shapes, prim, sf.p);
+	const float inv_em_count = 1.0f / (float)p.n_emitters; // only used when an emitter was hit (there is one, then)
+	float emitter_pdf = 0.0f;
+	if (sf.is_em) emitter_pdf = emitter_hit_pdf<kLevel>(p.shapes, prim, prev_p, sf.p, n, inv_em_count);
+	float *o = p.out + (uint64_t)PG_SURFACE_PROBE_FLOATS * tid;
+	o[0] = sf.p.x; o[1] = sf.p.y; o[2] = sf.p.z;
+	o[3] = n.x; o[4] = n.y; o[5] = n.z;
+	o[6] = sf.ng.x; o[7] = sf.ng.y; o[8] = sf.ng.z;
+	o[9] = sf.m.refl.x; o[10] = sf.m.refl.y; o[11] = sf.m.refl.z;
+	o[12] = sf.radiance.x; o[13] = sf.radiance.y; o[14] = sf.radiance.z;
+	o[15] = nat.x; o[16] = nat.y; o[17] = nat.z;
+	o[18] = emitter_pdf;
+	o[19] = fr.s.x; o[20] = fr.s.y; o[21] = fr.s.z;
+	o[22] = fr.t.x; o[23] = fr.t.y; o[24] = fr.t.z;
+	o[25] = wi.x; o[26] = wi.y; o[27] = wi.z;
+	o[28] = back.x; o[29] = back.y; o[30] = back.z;
+	int32_t *f = p.flags + 4 * tid;
+	f[0] = kLevel ? (int32_t)((sf.m.M - p.mats) / kMaterialStride) : -1; // (level 0 reads no row for a quad)
+	f[1] = sf.m.type;
+	f[2] = sf.m.one_sided ? 1 : 0;
+	f[3] = sf.is_em ? 1 : 0;
+}
+static_assert(PG_SURFACE_PROBE_FLOATS == 31, "k_probe_surface writes 31 floats per lane");
+
 } // namespace
+
+int pg_surface_probe(pg_context *ctx, uint64_t n, const int32_t *d_prim, const float *d_origin, const float *d_dir,
+                     const float *d_t, const float *d_uv, const float *d_ref, float *d_out, int32_t *d_flags, void *stream)
+{
+	if (!ctx) return PG_ERR_INVALID;
+	if (!ctx->render || !scene_state(ctx).have_scene) return fail(ctx, PG_ERR_INVALID, "pg_surface_probe: call pg_scene_set first");
+	if (n > kProbeMaxRays) return fail(ctx, PG_ERR_INVALID, "pg_surface_probe: at most 2^20 lanes in one call");
+	if (n == 0) return PG_OK;
+	if (!d_prim || !d_origin || !d_dir || !d_t || !d_uv || !d_ref || !d_out || !d_flags)
+		return fail(ctx, PG_ERR_INVALID, "pg_surface_probe: NULL pointer");
+	PG_HIP(ctx, hipSetDevice(ctx->device));
+	const SceneState &sc = scene_state(ctx);
+	const hipStream_t s = (hipStream_t)stream;
+	PG_HIP(ctx, hipStreamSynchronize(s)); // (the caller's writes of the inputs, before the host reads them)
+	// the shape numbers are checked on the host before a lane follows them
+	const int64_t n_shapes = (int64_t)sc.n_quads + sc.n_spheres + 6 * (int64_t)sc.n_boxes + (int64_t)sc.n_tris;
+	std::vector<int32_t> prim(n);
+	PG_HIP(ctx, hipMemcpy(prim.data(), d_prim, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+	for (uint64_t i = 0; i < n; ++i)
+		if (prim[i] < 0 || (int64_t)prim[i] >= n_shapes) return fail(ctx, PG_ERR_INVALID, "pg_surface_probe: shape number outside the scene");
+	SurfaceProbeArgs p;
+	p.shapes.quads = sc.quads.p; p.shapes.spheres = sc.spheres.p; p.shapes.boxes = sc.boxes.p; p.shapes.tris = sc.tris.p;
+	p.shapes.tri_normals = sc.have_tri_normals ? sc.tri_normals.p : nullptr;
+	p.shapes.tri_uvs = sc.have_tri_uvs ? sc.tri_uvs.p : nullptr;
+	p.shapes.textures = sc.textures.p; p.shapes.texels = sc.texels.p; p.shapes.srgb_lut = sc.srgb_lut.p;
+	p.shapes.bvh = sc.bvh.p; p.shapes.n_bvh_nodes = sc.n_bvh_nodes;
+	p.shapes.n_quads = sc.n_quads; p.shapes.n_spheres = sc.n_spheres; p.shapes.n_boxes = sc.n_boxes;
+	p.mats = sc.mats.p;
+	p.n = n; p.n_emitters = sc.n_emitters; // (an emitter shape is in the scene's emitter list: n_emitters >= 1 wherever a lane divides by it)
+	p.prim = d_prim; p.o = d_origin; p.d = d_dir; p.t = d_t; p.uv = d_uv; p.ref = d_ref; p.out = d_out; p.flags = d_flags;
+	const dim3 grid((unsigned)((n + kRBlock - 1) / kRBlock));
+	switch (sc.general) {
+	case 0: hipLaunchKernelGGL((k_probe_surface<0>), grid, dim3(kRBlock), 0, s, p); break;
+	case 1: hipLaunchKernelGGL((k_probe_surface<1>), grid, dim3(kRBlock), 0, s, p); break;
+	case 2: hipLaunchKernelGGL((k_probe_surface<2>), grid, dim3(kRBlock), 0, s, p); break;
+	default: hipLaunchKernelGGL((k_probe_surface<3>), grid, dim3(kRBlock), 0, s, p); break;
+	}
+	PG_HIP(ctx, hipGetLastError());
+	PG_HIP(ctx, hipStreamSynchronize(s));
+	return PG_OK;
+}
 
 int pg_bsdf_probe(pg_context *ctx, uint64_t n, uint64_t n_mat, const float *d_materials, const int32_t *d_material_index,
                   const float *d_wi, const float *d_wo, const float *d_u, int32_t level, float *d_value, float *d_pdf,

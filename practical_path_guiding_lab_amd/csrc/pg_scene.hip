@@ -212,7 +212,7 @@ int pg_scene_set_ex(pg_context *ctx, const pg_scene_desc *sc, const pg_camera *c
 	if (rc != PG_OK) return rc;
 	// Stage 3, the commit
 	s.n_quads = (int)sc->n_quads; s.n_spheres = (int)sc->n_spheres; s.n_boxes = (int)sc->n_boxes;
-	s.n_bvh_nodes = (int)sc->n_bvh_nodes; s.n_emitters = (int)h.emitters.size();
+	s.n_bvh_nodes = (int)sc->n_bvh_nodes; s.n_emitters = (int)h.emitters.size(); s.n_tris = sc->n_tris;
 	s.have_tri_normals = h.tri_normals; s.have_tri_uvs = h.tri_uvs;
 	for (int c = 0; c < 4; ++c) s.bsphere[c] = sc->bsphere[c];
 	s.geometry = record_geometry_wanted(ctx); // pg_render_record_geometry: implies the split pipeline

@@ -18,6 +18,7 @@ struct SceneState {
 	bool have_tri_normals = false, have_tri_uvs = false;
 	float bsphere[4] = {0, 0, 0, 0};
 	int n_quads = 0, n_spheres = 0, n_emitters = 0, n_boxes = 0, n_bvh_nodes = 0;
+	uint64_t n_tris = 0; // (host-side checks only: the kernels find triangles through the BVH)
 	int general = 0; // feature level of the kernels to launch (0 cornell-box class, 1 veach-mis class, 2 meshes, 3 everything)
 	bool geometry = false; // pg_render_record_geometry was on when the scene was set: recording passes keep the vertices' geometry
 	pg_camera cam;

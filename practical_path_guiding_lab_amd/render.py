@@ -212,6 +212,27 @@ class WavefrontScene:
                                                       torch.cuda.current_stream().cuda_stream))
         return t, prim, uv
 
+    SURFACE_PROBE_FLOATS = 31  # PG_SURFACE_PROBE_FLOATS of include/pgsd.h
+
+    def surface_probe(self, tree, prim: torch.Tensor, origin: torch.Tensor, direction: torch.Tensor, t: torch.Tensor,
+                      uv: torch.Tensor, ref: torch.Tensor):
+        """pg_surface_probe: the renderer's surface description at a hit by itself, for tests -- prim (n,) int32 shape numbers,
+        origin, direction, ref (n,3), t (n,), uv (n,2) float32 cuda tensors (the hit as intersect() reports it, and the
+        previous path vertex).  Returns (out (n, 31) float32, flags (n, 4) int32) in the layout include/pgsd.h documents."""
+        self._upload(tree)
+        q = prim.to(torch.int32).contiguous()
+        n = q.shape[0]
+        o, d, r = (a.to(torch.float32).contiguous() for a in (origin, direction, ref))
+        tt, bc = t.to(torch.float32).contiguous(), uv.to(torch.float32).contiguous()
+        if q.shape != (n,) or o.shape != (n, 3) or d.shape != (n, 3) or r.shape != (n, 3) or tt.shape != (n,) or bc.shape != (n, 2):
+            raise ValueError("prim, t: (n,); origin, direction, ref: (n,3); uv: (n,2)")
+        out = torch.empty((n, self.SURFACE_PROBE_FLOATS), dtype=torch.float32, device=o.device)
+        flags = torch.empty((n, 4), dtype=torch.int32, device=o.device)
+        N.check(tree._h, tree._lib.pg_surface_probe(tree._h, n, q.data_ptr(), o.data_ptr(), d.data_ptr(), tt.data_ptr(), bc.data_ptr(),
+                                                    r.data_ptr(), out.data_ptr(), flags.data_ptr(),
+                                                    torch.cuda.current_stream().cuda_stream))
+        return out, flags
+
     def join(self) -> None:
         """in_flight = 2: the current stream waits for every pass issued so far (no host synchronisation)."""
         if self._streams is not None:

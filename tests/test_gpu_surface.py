@@ -1,0 +1,161 @@
+"""The device's surface description at a hit by itself (pg_surface_probe: surface_at<>, normal_at<>, texture_eval,
+box_face_normal, make_frame, to_local, to_world and emitter_hit_pdf<> of csrc/pg_render_dev.hpp as stage_a1 calls them, at
+the scene's feature level) against the CPU oracle's (pgo_surface_probe) bit for bit -- on broad sets of hits of five scenes,
+on the known-answer inputs of tests/test_surface_model.py (texel centres, the wrap, huge and non-finite coordinates, a
+checkerboard at one half, vertex normals that cancel, all faces of a rotated box, grazing emitters, the sphere's cap limit)
+and on degenerate inputs -- and against the float64 model of tests/surface_model.py directly, so that a change moving
+oracle and device together still fails a test.
+
+"Bit for bit" lets one thing differ: WHICH NaN a lane holds (0 / 0 is a negative quiet NaN on the host and a positive one on
+the device); where one side has a NaN the other must have one."""
+import functools
+
+import numpy as np
+import pytest
+
+import surface_model as SM
+import test_surface_model as TS
+
+pytestmark = pytest.mark.gpu
+
+SIZES = (1, 63, 64, 65, 257, 4099)
+
+
+@functools.lru_cache(maxsize=None)
+def tree():
+    from practical_path_guiding_lab_amd.sdtree import SDTree
+    return SDTree(0)
+
+
+@functools.lru_cache(maxsize=None)
+def device(name):
+    from practical_path_guiding_lab_amd.render import WavefrontScene
+    return WavefrontScene(TS.scene(name))
+
+
+def probe(ws, h):
+    import torch
+    from oracle import pg_oracle as po
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    ws._uploaded_to = None      # (one context serves every scene of this module: the scene is set again)
+    out, flags = ws.surface_probe(tree(), dev(h["prim"]), dev(h["o"]), dev(h["d"]), dev(h["t"]),
+                                  dev(np.stack([h["u"], h["v"]], axis=1)), dev(h["ref"]))
+    return po.split_surface(out.cpu().numpy(), flags.cpu().numpy())
+
+
+def _same(dev, ora, what):
+    from oracle import pg_oracle as po
+    assert set(dev) == set(ora)
+    for k in po.SURFACE_FLAGS:
+        if k in dev:
+            np.testing.assert_array_equal(dev[k], ora[k], err_msg="%s: %s" % (what, k))
+    for k in [f for f, _, _ in po.SURFACE_FIELDS if f in dev]:
+        a, b = dev[k], ora[k]
+        same = (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
+        assert same.all(), "%s: %s differs on lanes %s, e.g. device %r oracle %r" % (
+            what, k, np.unique(np.nonzero(~same)[0])[:8], a[~same][:3], b[~same][:3])
+
+
+def _oracle(sc, h):
+    from oracle import pg_oracle as po
+    return po.surface_probe(sc, h["prim"], h["o"], h["d"], h["t"], h["ref"])
+
+
+@pytest.mark.parametrize("name", TS.SCENES)
+def test_device_equals_oracle(name):
+    h = TS.hits(name)
+    assert h["prim"].shape[0] == SIZES[-1]
+    ora = TS.probe_oracle(name, h)
+    for n in SIZES:
+        _same(probe(device(name), {k: a[:n] for k, a in h.items()}), {k: a[:n] for k, a in ora.items()}, "%s n %d" % (name, n))
+
+
+def test_device_equals_oracle_on_the_known_answers():
+    from practical_path_guiding_lab_amd.render import WavefrontScene
+    count = 0
+    for label, sc, h in TS.known_cases():
+        _same(probe(WavefrontScene(sc), h), _oracle(sc, h), label)
+        count += 1
+    assert count > 60
+
+
+@pytest.mark.parametrize("name", ["veach-ajar", "mixed", "veach-mis"])
+def test_non_finite_and_degenerate_hits(name):
+    """NaN and inf in t, uv and ref, and d = 0: the oracle returns for them (tests/test_surface_model.py checks that on the
+    CPU); the device has no loop to run away in and takes no address from a float but the wrapped texel index.  The device is
+    GIVEN its barycentrics and the oracle recomputes its own from the ray, so on the lanes whose uv were spoiled, and on those
+    whose d = 0 spoils the oracle's (0 * inf), the columns that depend on a triangle's uv are left out."""
+    from oracle import pg_oracle as po
+    h = TS.degenerate_hits(name)
+    dev, ora = probe(device(name), h), TS.probe_oracle(name, h)
+    differ = np.zeros(96, bool)
+    differ[24:48] = differ[72:96] = True
+    differ &= TS.tables(name).kind(h["prim"]) == 3
+    assert name == "veach-mis" or (differ.sum() >= 8 and (~differ).sum() >= 48)
+    keep = lambda r, m, cols: {k: r[k][m] for k in cols}
+    every = [k for k, _, _ in po.SURFACE_FIELDS] + list(po.SURFACE_FLAGS)
+    _same(keep(dev, ~differ, every), keep(ora, ~differ, every), name + " degenerate")
+    free_of_uv = ["p", "ng", "radiance", "normal_at", "emitter_pdf"] + list(po.SURFACE_FLAGS)
+    _same(keep(dev, differ, free_of_uv), keep(ora, differ, free_of_uv), name + " degenerate, another uv")
+    assert (np.isnan(dev["refl"]) | ((dev["refl"] >= 0) & (dev["refl"] <= 1))).all()   # any uv: a blend of texels, or NaN weights
+
+
+@pytest.mark.parametrize("name", ["veach-ajar", "mixed"])
+def test_device_against_the_model(name):
+    from oracle import pg_oracle as po
+    h = {k: a[:2048] for k, a in TS.hits(name).items()}
+    T = TS.tables(name)
+    m = SM.surface(T, h["prim"], h["o"], h["d"], h["t"], h["u"], h["v"])
+    bad, ratio, amb = SM.judge(T, m, probe(device(name), h), h["d"], h["ref"], po.feature_level(TS.scene(name)))
+    print("%s: %.2f %% ambiguous; worst |difference| / bracket: %s" % (name, 100 * amb.mean(), ", ".join("%s %.2f" % (k, v.max()) for k, v in sorted(ratio.items()))))
+    assert not bad, {k: v[:8] for k, v in bad.items()}
+    assert amb.mean() <= SM.AMBIGUOUS_CAP
+    assert m.textured.sum() >= 32 and (T.kind(h["prim"]) == 3).sum() >= 256
+
+
+def test_a_blend_whose_squared_length_is_subnormal():
+    """vertex normals scaled so that the blend's squared length lands below 2^-126 and above 0 (2^-148, 2^-140), and so that
+    it underflows to 0 (2^-178): the device keeps subnormals as the host does -- the blend's direction where l2 > 0 holds, the
+    face normal where it does not"""
+    from practical_path_guiding_lab_amd.render import WavefrontScene
+    face = np.array([0, 0, 1], np.float32)
+    for scale, must_fall_back in TS.SUBNORMAL_CASES:
+        sc, h = TS.normal_scene("one float off", scale), TS.normal_hit("one float off")
+        dev, ora = probe(WavefrontScene(sc), h), _oracle(sc, h)
+        print("scale %g: device n %s, oracle n %s" % (scale, dev["n"][0], ora["n"][0]))
+        _same(dev, ora, "scale %g" % scale)
+        assert (dev["n"][0] == (face if must_fall_back else -face)).all() and (dev["ng"][0] == face).all()
+
+
+def test_misuse_is_refused_with_a_message():
+    import torch
+    from practical_path_guiding_lab_amd import _native as N
+    from practical_path_guiding_lab_amd.sdtree import SDTree
+    L = N.lib()
+    f = lambda n: torch.zeros(n, dtype=torch.float32, device="cuda")
+    prim, o, d, t, uv, ref = torch.zeros(16, dtype=torch.int32, device="cuda"), f(48), f(48) + 1, f(16) + 1, f(32), f(48)
+    out, flags = f(16 * 31), torch.zeros(64, dtype=torch.int32, device="cuda")
+
+    def refused(h, n, args, word):
+        rc = L.pg_surface_probe(h, n, *args)
+        assert rc < 0 and word in L.pg_last_error(h).decode(), (rc, L.pg_last_error(h))
+
+    good = [prim.data_ptr(), o.data_ptr(), d.data_ptr(), t.data_ptr(), uv.data_ptr(), ref.data_ptr(), out.data_ptr(), flags.data_ptr(), None]
+    bare = SDTree(0)
+    refused(bare._h, 16, good, "pg_scene_set")          # no scene
+    tr, ws = SDTree(0), device("cornell-box")
+    ws._uploaded_to = None
+    ws._upload(tr)
+    assert L.pg_surface_probe(tr._h, 16, *good) == 0
+    for k in range(8):
+        refused(tr._h, 16, good[:k] + [None] + good[k + 1:], "NULL")
+    refused(tr._h, (1 << 20) + 1, good, "2^20")
+    n_shapes = TS.tables("cornell-box").n_shapes
+    for wrong in (-1, n_shapes):
+        prim[7] = wrong
+        refused(tr._h, 16, good, "shape number")
+    prim[7] = n_shapes - 1
+    assert L.pg_surface_probe(tr._h, 16, *good) == 0      # the context stays usable, and the last shape is one
+    assert L.pg_surface_probe(tr._h, 0, None, None, None, None, None, None, None, None, None) == 0
+    torch.cuda.synchronize()
+    assert int(flags.view(16, 4)[7, 0]) == -1 and int(flags.view(16, 4)[0, 1]) == 0   # (level 0: no row; diffuse)
