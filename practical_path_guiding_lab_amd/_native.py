@@ -155,6 +155,9 @@ PG_TARGET_SECOND_MOMENT = 1
 # and every symbol include/pgsd_radiance.h declares (radiance estimates and guided Russian roulette / splitting)
 EXPORTS_RADIANCE = ("pg_radiance_enable", "pg_radiance_status", "pg_radiance_export", "pg_radiance_import", "pg_radiance_query",
                     "pg_radiance_rr")
+# and every symbol include/pgsd_irradiance.h declares (irradiance estimates per spatial leaf: order-2 spherical harmonics)
+EXPORTS_IRRADIANCE = ("pg_irradiance_build", "pg_irradiance_status", "pg_irradiance_export", "pg_irradiance_import",
+                      "pg_irradiance_query", "pg_irradiance_rr")
 # and the one symbol include/pgsd_bounce.h declares (fraction, selection, guide bounce and radiance estimate behind one KD descent)
 EXPORTS_BOUNCE = ("pg_bounce",)
 PG_BOUNCE_NONE, PG_BOUNCE_PDF, PG_BOUNCE_SAMPLE, PG_BOUNCE_CHOOSE = 0, 1, 2, 3
@@ -162,8 +165,8 @@ PG_BOUNCE_NONE, PG_BOUNCE_PDF, PG_BOUNCE_SAMPLE, PG_BOUNCE_CHOOSE = 0, 1, 2, 3
 
 def source_hash() -> str:
     """sha256 (16 hex digits) over the library's sources (csrc/*.hip, csrc/*.hpp, include/pgsd.h, include/pgsd_warp.h,
-    include/pgsd_fraction.h, include/pgsd_target.h, include/pgsd_radiance.h, include/pgsd_bounce.h): names the code a
-    profile was taken of (profiles/pmc_traffic.json) so that bench.py never pairs old counters with new kernels."""
+    include/pgsd_fraction.h, include/pgsd_target.h, include/pgsd_radiance.h, include/pgsd_irradiance.h, include/pgsd_bounce.h):
+    names the code a profile was taken of (profiles/pmc_traffic.json) so that bench.py never pairs old counters with new kernels."""
     import glob
     import hashlib
     h = hashlib.sha256()
@@ -174,6 +177,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_target.h"))
     files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_radiance.h"))
     files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_bounce.h"))
+    files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_irradiance.h"))
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
@@ -293,7 +297,13 @@ def lib() -> C.CDLL:
     L.pg_radiance_query.argtypes = [V, U64, V, V, V, V, V, V]
     L.pg_radiance_rr.argtypes = [V, U64, V, V, V, V, C.POINTER(pg_rr_params), V, V, V, V, V, V, V]
     L.pg_bounce.argtypes = [V, U64, C.POINTER(pg_bounce_args), V]
-    for name in EXPORTS + EXPORTS_WARP + EXPORTS_FRACTION + EXPORTS_TARGET + EXPORTS_RADIANCE + EXPORTS_BOUNCE:
+    L.pg_irradiance_build.argtypes = [V, V]
+    L.pg_irradiance_status.argtypes = [V, C.POINTER(I32)]
+    L.pg_irradiance_export.argtypes = [V, U64, V]
+    L.pg_irradiance_import.argtypes = [V, U64, V]
+    L.pg_irradiance_query.argtypes = [V, U64, V, V, V, V, V]
+    L.pg_irradiance_rr.argtypes = [V, U64, V, V, V, V, C.POINTER(pg_rr_params), V, V, V, V, V, V, V]
+    for name in EXPORTS + EXPORTS_WARP + EXPORTS_FRACTION + EXPORTS_TARGET + EXPORTS_RADIANCE + EXPORTS_BOUNCE + EXPORTS_IRRADIANCE:
         if name not in ("pg_last_error", "pg_abi_version"):
             getattr(L, name).restype = C.c_int
     _lib = L

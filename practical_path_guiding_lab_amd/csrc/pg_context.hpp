@@ -153,11 +153,31 @@ struct Fraction {
 // Radiance estimates (include/pgsd_radiance.h, pg_kernels_radiance.hip): off unless pg_radiance_enable switched it on.  One uint64
 // per quadtree of sdTree_prev, the number of in-box records its energies were resolved from; a refine builds the next table in the
 // spare buffer and commits it, with the two flags, by one pointer swap (pg_refine.hip).
+// Irradiance estimates (include/pgsd_irradiance.h, pg_kernels_irradiance.hip): nothing unless pg_irradiance_build /
+// pg_irradiance_import ran.  The projection of every quadtree of sdTree_prev onto the nine spherical harmonics up to order 2,
+// kIrrStride floats per tree (nine coefficients, padded to three 16-byte gathers).  It lives with the weights it was projected
+// with: whatever replaces them or the tree clears `built`.
+constexpr uint32_t kIrrCoeffs = 9, kIrrStride = 12;
+struct Irradiance {
+	int32_t built = 0;
+	DevBuf<float> tab;      // [n_trees][kIrrStride]
+	DevBuf<long long> sums; // [n_trees][kIrrCoeffs]: the build's exact sums, kept between builds
+	DevBuf<uint4> cells;    // one per quadtree record: (tree, ix, iy, depth) of the node's cell, kept between builds
+	void release()
+	{
+		built = 0;
+		tab.release();
+		sums.release();
+		cells.release();
+	}
+};
+
 struct Radiance {
 	bool on = false;
 	int32_t valid = 0;     // the table describes sdTree_prev (a refine committed it, or pg_radiance_import loaded it)
 	int32_t of_target = 0; // pg_target_applied at the refine that built sdTree_prev: its energies are not radiance
 	DevBuf<unsigned long long> tab, spare; // spare: the next refine's table (what a commit replaced)
+	Irradiance irr;        // built from tab and sdTree_prev on request
 	void disable()
 	{
 		on = false;
@@ -165,6 +185,7 @@ struct Radiance {
 		of_target = 0;
 		tab.release();
 		spare.release();
+		irr.release();
 	}
 };
 

@@ -1,7 +1,8 @@
 // pg_guide_dev.hpp -- device functions of the stand-alone guiding calls that more than one translation unit inlines: the learned
-// fraction's logistic (pgsd_fraction.h), the sample warp of one quadtree (pgsd_warp.h) and the radiance estimate's leaf walk
-// (pgsd_radiance.h).  Each moved here unchanged from the file that introduced it when pg_kernels_bounce.hip became its second
-// caller; the headers named state the semantics operation by operation.
+// fraction's logistic (pgsd_fraction.h), the sample warp of one quadtree (pgsd_warp.h), the radiance estimate's leaf walk and
+// the roulette / splitting decision (pgsd_radiance.h).  Each moved here unchanged from the file that introduced it when it got
+// a second caller (pg_kernels_bounce.hip; for the decision pg_kernels_irradiance.hip); the headers named state the semantics
+// operation by operation.
 #pragma once
 
 #include "pg_descent.hpp"
@@ -127,6 +128,40 @@ __device__ __forceinline__ RadLeaf radiance_leaf(const QuadRec *rec, TreeHead he
 		r = c == 0 ? kNoRecord : c;
 	}
 	return o;
+}
+
+// what the decision needs beside the estimate (the kDecide kernels of pg_kernels_radiance.hip and pg_kernels_irradiance.hip)
+struct RrArgs {
+	const float *weight, *reference;
+	uint64_t *rng_state;
+	const uint64_t *rng_inc;
+	uint32_t *count_out;
+	float *scale_out;
+	float lo, hi, max_split_f;
+	uint32_t max_split;
+};
+
+// DECISION of pgsd_radiance.h behind the lane's one draw xi: L the estimate (pgsd_irradiance.h: E), w the throughput, I the
+// reference.  count and scale arrive as 1 and 1 (no opinion) and are written where the lane has one.
+__device__ __forceinline__ void rr_decide(const RrArgs &rr, float xi, float L_dir, float w, float I, uint32_t &count, float &scale)
+{
+	if (L_dir > 0.0f && w > 0.0f && I > 0.0f && finite_f32(L_dir) && finite_f32(w) && finite_f32(I)) {
+		const float q = (w * L_dir) / I;
+		if (finite_f32(q)) {
+			if (q < rr.lo) { // roulette
+				const float P = q / rr.lo;
+				const bool survive = xi < P;
+				count = survive ? 1u : 0u;
+				scale = survive ? rr.lo / q : 0.0f;
+			} else if (q > rr.hi && rr.max_split > 1u) { // split
+				float r = q / rr.hi;
+				if (r > rr.max_split_f) r = rr.max_split_f;
+				const float k = __builtin_floorf(r);
+				count = (uint32_t)k + (xi < r - k ? 1u : 0u);
+				scale = 1.0f / r;
+			}
+		}
+	}
 }
 
 } // namespace pg

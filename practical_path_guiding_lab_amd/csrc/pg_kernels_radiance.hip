@@ -19,16 +19,8 @@ static_assert(kRadBlock == kStageThreads, "stage_kd_planes copies one plane per 
 // radiance_leaf (the leaf a record with a canonical direction adds to: its energy and depth): pg_guide_dev.hpp --
 // pg_kernels_bounce.hip inlines it too
 
-// what the decision needs beside the estimate (kDecide)
-struct RrArgs {
-	const float *weight, *reference;
-	uint64_t *rng_state;
-	const uint64_t *rng_inc;
-	uint32_t *count_out;
-	float *scale_out;
-	float lo, hi, max_split_f;
-	uint32_t max_split;
-};
+// RrArgs (what the decision needs beside the estimate, kDecide) and rr_decide (the decision): pg_guide_dev.hpp --
+// pg_kernels_irradiance.hip decides on its estimate the same way
 
 // dir == nullptr (uniform; never with kDecide): only the mean, no quadtree is walked.
 template <bool kDecide>
@@ -78,23 +70,7 @@ __global__ __launch_bounds__(kRadBlock) void k_radiance(TreeView t, const unsign
 		if (kDecide) {
 			const float xi = rng.next_f32(); // exactly one draw per active lane
 			rr.rng_state[i] = rng.state;
-			if (L_dir > 0.0f && w > 0.0f && I > 0.0f && finite_f32(L_dir) && finite_f32(w) && finite_f32(I)) {
-				const float q = (w * L_dir) / I;
-				if (finite_f32(q)) {
-					if (q < rr.lo) { // roulette
-						const float P = q / rr.lo;
-						const bool survive = xi < P;
-						count = survive ? 1u : 0u;
-						scale = survive ? rr.lo / q : 0.0f;
-					} else if (q > rr.hi && rr.max_split > 1u) { // split
-						float r = q / rr.hi;
-						if (r > rr.max_split_f) r = rr.max_split_f;
-						const float k = __builtin_floorf(r);
-						count = (uint32_t)k + (xi < r - k ? 1u : 0u);
-						scale = 1.0f / r;
-					}
-				}
-			}
+			rr_decide(rr, xi, L_dir, w, I, count, scale);
 		}
 	}
 	if (L_dir_out) L_dir_out[i] = L_dir;
@@ -151,7 +127,7 @@ int pg_radiance_enable(pg_context *ctx, int32_t on)
 	Radiance &r = ctx->rad;
 	if (!on) {
 		PG_HIP(ctx, hipDeviceSynchronize()); // (kernels that read the table have finished)
-		r.disable();
+		r.disable(); // (and with the weights the irradiance table built from them, pgsd_irradiance.h)
 		return PG_OK;
 	}
 	if (r.on) return PG_OK;
@@ -198,6 +174,7 @@ int pg_radiance_import(pg_context *ctx, uint64_t n_trees, const uint64_t *h_weig
 	PG_HIP(ctx, hipMemcpy(ctx->rad.tab.p, h_weight, (size_t)n_trees * sizeof(uint64_t), hipMemcpyHostToDevice));
 	ctx->rad.valid = 1;
 	ctx->rad.of_target = 0;
+	ctx->rad.irr.built = 0; // (pgsd_irradiance.h: its table was projected with the weights this call replaced)
 	return PG_OK;
 }
 

@@ -661,6 +661,7 @@ int refine_and_swap(pg_context *ctx, hipStream_t s)
 		rad.tab.swap(rad.spare);
 		rad.valid = 1;
 		rad.of_target = ctx->target_applied; // (what the new sdTree_prev's energies are: read before the line below clears it)
+		rad.irr.built = 0;                   // (pgsd_irradiance.h: the projection of the tree this commit replaces)
 	}
 	ctx->target_applied = 0; // (the accumulators a target was applied to are consumed: pgsd_target.h)
 	f.n_rec = (uint32_t)off;

@@ -462,6 +462,68 @@ class SDTree:
                                           mp, count.data_ptr(), scale.data_ptr(), L_dir.data_ptr(), _stream_ptr()))
         return count, scale, L_dir
 
+    # ---- irradiance estimates per spatial leaf (include/pgsd_irradiance.h; not in the reference) -----------------------------
+    def irradianceBuild(self):
+        """Projects every quadtree of sdTree_prev onto the nine spherical harmonics up to order 2 (pg_irradiance_build): needs
+        radianceEnable and known weights.  Whatever replaces the tree or its weights (refineAndPrepare, setup, load,
+        radianceEnable(False), radianceLoadWeights) discards the table."""
+        self._ck(self._lib.pg_irradiance_build(self._h, _stream_ptr()))
+
+    def irradianceStatus(self) -> bool:
+        """True while the table describes sdTree_prev (pg_irradiance_status)."""
+        b = C.c_int32(0)
+        self._ck(self._lib.pg_irradiance_status(self._h, C.byref(b)))
+        return bool(b.value)
+
+    def irradianceCoefficients(self) -> np.ndarray:
+        """float32 (n_roots, 9): the coefficients of every quadtree (pg_irradiance_export), indexed like radianceWeights."""
+        n = int(self.sizes().n_roots)
+        k = np.empty((n, 9), np.float32)
+        self._ck(self._lib.pg_irradiance_export(self._h, n, k.ctypes.data))
+        return k
+
+    def irradianceLoadCoefficients(self, k):
+        """Loads the coefficients of a tree that came from a file (pg_irradiance_import), nine per quadtree."""
+        k = np.ascontiguousarray(k, np.float32)
+        if k.ndim != 2 or k.shape[1] != 9:
+            raise ValueError("nine coefficients per quadtree")
+        self._ck(self._lib.pg_irradiance_import(self._h, k.shape[0], k.ctypes.data))
+
+    def irradianceEstimate(self, position: torch.Tensor, normal: Optional[torch.Tensor] = None,
+                           active: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """E float32 (N,) (pg_irradiance_query): the integral of the radiance arriving at `position` against the cosine around
+        `normal` (used as given: unit length is the caller's business).  normal=None: the mean over all orientations."""
+        n = position.shape[1]
+        _f32(position, (3, n))
+        m, mp = _mask(active, n)
+        np_ = _f32(normal, (3, n)).data_ptr() if normal is not None else None
+        E = torch.empty(n, dtype=torch.float32, device=self.device)
+        self._ck(self._lib.pg_irradiance_query(self._h, n, position.data_ptr(), np_, mp, E.data_ptr(), _stream_ptr()))
+        return E
+
+    def irradianceRoulette(self, position: torch.Tensor, normal: Optional[torch.Tensor], weight: torch.Tensor,
+                           reference: torch.Tensor, sampler: PCG32Sampler, window: float = 5.0, max_split: int = 1,
+                           active: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(count int32 (N,), scale float32 (N,), E float32 (N,)) (pg_irradiance_rr): radianceRoulette's decision on the
+        irradiance estimate, before a direction is sampled.  weight: the paths' throughput with rho / pi folded in.  One draw
+        of `sampler` per active lane."""
+        n = position.shape[1]
+        _f32(position, (3, n))
+        np_ = _f32(normal, (3, n)).data_ptr() if normal is not None else None
+        _f32(weight, (n,))
+        _f32(reference, (n,))
+        if sampler.n != n:
+            raise ValueError("the sampler must have one stream per lane")
+        m, mp = _mask(active, n)
+        count = torch.empty(n, dtype=torch.int32, device=self.device)
+        scale = torch.empty(n, dtype=torch.float32, device=self.device)
+        E = torch.empty(n, dtype=torch.float32, device=self.device)
+        prm = N.pg_rr_params(float(window), int(max_split))
+        self._ck(self._lib.pg_irradiance_rr(self._h, n, position.data_ptr(), np_, weight.data_ptr(), reference.data_ptr(),
+                                            C.byref(prm), sampler.state.data_ptr(), sampler.inc.data_ptr(), mp,
+                                            count.data_ptr(), scale.data_ptr(), E.data_ptr(), _stream_ptr()))
+        return count, scale, E
+
     # ---- a whole guided bounce behind one KD descent (include/pgsd_bounce.h; not in the reference) -------------------------
     def bounce(self, position, dir_nee, nee_active, dir_io, mode=None, u_select=None, sampler: Optional[PCG32Sampler] = None,
                u=None, lanes=None, radiance: bool = False, out: Optional[Dict[str, torch.Tensor]] = None
