@@ -126,58 +126,88 @@ class pg_depth_counters(C.Structure):
                 ("quad_levels", C.c_uint64), ("quad_queries", C.c_uint64), ("layout_bytes", C.c_uint64)]
 
 
-# every symbol include/pgsd.h declares (checked by tests/test_abi.py)
 ABI_VERSION = 6  # PGSD_ABI_VERSION of include/pgsd.h these bindings match
-
-EXPORTS = (
-    "pg_create", "pg_destroy", "pg_last_error", "pg_abi_version", "pg_setup", "pg_set_iteration",
-    "pg_get_leaf_node_index", "pg_sample", "pg_pdf", "pg_guide_bounce", "pg_compact_lanes", "pg_rng_seed", "pg_splat",
-    "pg_process_records", "pg_process_and_splat", "pg_refine_and_swap", "pg_accumulators",
-    "pg_export_sizes", "pg_export", "pg_import", "pg_export_accumulators", "pg_get_stats",
-    "pg_enable_depth_counters", "pg_read_depth_counters", "pg_scene_set", "pg_render_pass",
-    "pg_enable_kernel_timing", "pg_read_kernel_timing", "pg_render_live_counts", "pg_film_tent",
-    "pg_math_eval", "pg_scene_set_ex", "pg_film", "pg_film_stripes", "pg_film_batched", "pg_film_batched_accumulate", "pg_render_overlap", "pg_render_sort", "pg_render_stages",
-    "pg_comm_unique_id", "pg_comm_init", "pg_comm_attach", "pg_comm_destroy", "pg_allreduce", "pg_render_reserve",
-    "pg_render_split_pipeline", "pg_comm_info", "pg_exchange_pack", "pg_exchange_unpack", "pg_exchange_pack_words",
-    "pg_exchange_unpack_words", "pg_sort_places", "pg_debug_fail_alloc", "pg_debug_fail_alloc_pending",
-    "pg_read_shade_phases", "pg_set_splat_filter", "pg_render_record_geometry", "pg_render_export_records",
-    "pg_scene_intersect", "pg_bsdf_probe", "pg_surface_probe",
-)
-# every symbol include/pgsd_warp.h declares beside them (sample warping: same library, same ABI version)
-EXPORTS_WARP = ("pg_sample_warp", "pg_invert_warp", "pg_guide_bounce_warp")
-# and every symbol include/pgsd_fraction.h declares (the BSDF sampling fraction learned per KD leaf)
-EXPORTS_FRACTION = ("pg_fraction_enable", "pg_fraction_query", "pg_fraction_record", "pg_fraction_step",
-                    "pg_fraction_accumulators", "pg_fraction_export", "pg_fraction_import")
 PG_FRACTION_LOSS_KL, PG_FRACTION_LOSS_VARIANCE = 0, 1
-# and every symbol include/pgsd_target.h declares (the variance-aware guiding target: sqrt of the leaves' second moments)
-EXPORTS_TARGET = ("pg_target_apply", "pg_target_applied")
 PG_TARGET_SECOND_MOMENT = 1
-# and every symbol include/pgsd_radiance.h declares (radiance estimates and guided Russian roulette / splitting)
-EXPORTS_RADIANCE = ("pg_radiance_enable", "pg_radiance_status", "pg_radiance_export", "pg_radiance_import", "pg_radiance_query",
-                    "pg_radiance_rr")
-# and every symbol include/pgsd_irradiance.h declares (irradiance estimates per spatial leaf: order-2 spherical harmonics)
-EXPORTS_IRRADIANCE = ("pg_irradiance_build", "pg_irradiance_status", "pg_irradiance_export", "pg_irradiance_import",
-                      "pg_irradiance_query", "pg_irradiance_rr")
-# and the one symbol include/pgsd_bounce.h declares (fraction, selection, guide bounce and radiance estimate behind one KD descent)
-EXPORTS_BOUNCE = ("pg_bounce",)
 PG_BOUNCE_NONE, PG_BOUNCE_PDF, PG_BOUNCE_SAMPLE, PG_BOUNCE_CHOOSE = 0, 1, 2, 3
+
+V, U64, I32, U32, F32, P = C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_float, C.POINTER
+_RR = [V, U64, V, V, V, V, P(pg_rr_params), V, V, V, V, V, V, V]  # pg_radiance_rr and pg_irradiance_rr
+_FILM = [V, I32, U32, I32, V, V, U32, U32, U32, V]  # pg_film_stripes and pg_film_batched
+
+# The public surface, declared once: header of include/ -> entry point -> argtypes, in the order of the headers and of their
+# EXPORTS* tuples below.  lib() binds from it, source_hash() takes its headers from it, tests/test_abi.py holds every header, the
+# library and the probe build to it.  restype is c_int unless RESTYPES says otherwise.
+SURFACE = {
+    "pgsd.h": {
+        "pg_create": [P(V), C.c_int], "pg_destroy": [V], "pg_last_error": [V], "pg_abi_version": [],
+        "pg_setup": [V, V, V, U64, I32, I32, I32, I32, F32], "pg_set_iteration": [V, I32, I32],
+        "pg_get_leaf_node_index": [V, U64, V, V, V, V], "pg_sample": [V, U64, V, V, V, V, V, V, V],
+        "pg_pdf": [V, U64, V, V, V, V, V], "pg_guide_bounce": [V, U64, V, V, V, V, V, V, V, V, V, V, V, V],
+        "pg_compact_lanes": [V, U64, V, V, V, V, V], "pg_rng_seed": [V, U64, U32, U32, V, V, V],
+        "pg_splat": [V, U64, P(pg_records), V, V],
+        "pg_process_records": [V, U64, I32, V, P(pg_dense_records), P(pg_records_out), V, V],
+        "pg_process_and_splat": [V, U64, I32, V, P(pg_dense_records), V], "pg_refine_and_swap": [V, V],
+        "pg_accumulators": [V, P(V), P(U64)], "pg_export_sizes": [V, P(pg_tree_sizes)],
+        "pg_export": [V, P(pg_tree_sizes), P(pg_tree_columns)], "pg_import": [V, P(pg_tree_sizes), P(pg_tree_columns)],
+        "pg_export_accumulators": [V, P(pg_tree_sizes), V, V, V], "pg_get_stats": [V, P(pg_stats)],
+        "pg_enable_depth_counters": [V, I32], "pg_read_depth_counters": [V, P(pg_depth_counters), I32],
+        "pg_scene_set": [V, U64, V, P(pg_camera)], "pg_render_pass": [V, P(pg_pass_params), V, V, V, V, V],
+        "pg_enable_kernel_timing": [V, I32], "pg_read_kernel_timing": [V, P(pg_kernel_timing), I32],
+        "pg_render_live_counts": [V, P(U32), I32], "pg_film_tent": [V, U32, I32, V, V, V],
+        "pg_math_eval": [V, I32, U64, V, V, V], "pg_scene_set_ex": [V, P(pg_scene_desc), P(pg_camera)],
+        "pg_film": [V, I32, U32, I32, V, V, V], "pg_film_stripes": _FILM, "pg_film_batched": _FILM,
+        "pg_film_batched_accumulate": [V, I32, U32, I32, V, V, F32, I32, U32, U32, U32, V],
+        "pg_render_overlap": [V, I32], "pg_render_sort": [V, I32], "pg_render_stages": [V, I32],
+        "pg_comm_unique_id": [V, V], "pg_comm_init": [V, I32, I32, V], "pg_comm_attach": [V, V, I32], "pg_comm_destroy": [V],
+        "pg_allreduce": [V, V], "pg_render_reserve": [V, U64], "pg_render_split_pipeline": [V, I32],
+        "pg_comm_info": [V, P(I32), P(I32)], "pg_exchange_pack": [V, P(V), P(U64), V], "pg_exchange_unpack": [V, V],
+        "pg_exchange_pack_words": [V, U64, V], "pg_exchange_unpack_words": [V, U64, V], "pg_sort_places": [V, U64, V, V, V, V],
+        "pg_debug_fail_alloc": [C.c_int64], "pg_debug_fail_alloc_pending": [],
+        "pg_read_shade_phases": [V, P(U64), I32], "pg_set_splat_filter": [V, I32, I32, U32],
+        "pg_render_record_geometry": [V, I32], "pg_render_export_records": [V, I32, P(pg_records_out), V, V, V],
+        "pg_scene_intersect": [V, U64, V, V, V, I32, I32, V, V, V, V],
+        "pg_bsdf_probe": [V, U64, U64, V, V, V, V, V, I32, V, V, V, V, V, V, V, V],
+        "pg_surface_probe": [V, U64, V, V, V, V, V, V, V, V, V],
+    },
+    "pgsd_warp.h": {  # sample warping: same library, same ABI version
+        "pg_sample_warp": [V, U64, V, V, V, V, V, V], "pg_invert_warp": [V, U64, V, V, V, V, V, V],
+        "pg_guide_bounce_warp": [V, U64, V, V, V, V, V, V, V, V, V, V, V],
+    },
+    "pgsd_fraction.h": {  # the BSDF sampling fraction learned per KD leaf
+        "pg_fraction_enable": [V, P(pg_fraction_params)], "pg_fraction_query": [V, U64, V, V, V, V],
+        "pg_fraction_record": [V, U64, P(pg_fraction_records), V, V], "pg_fraction_step": [V, V],
+        "pg_fraction_accumulators": [V, P(V), P(U64)], "pg_fraction_export": [V, U64, V, V, V, V, V, V, V],
+        "pg_fraction_import": [V, U64, V, V, V, V, V, V],
+    },
+    "pgsd_target.h": {  # the variance-aware guiding target: sqrt of the leaves' second moments
+        "pg_target_apply": [V, I32, V], "pg_target_applied": [V, P(I32)],
+    },
+    "pgsd_radiance.h": {  # radiance estimates and guided Russian roulette / splitting
+        "pg_radiance_enable": [V, I32], "pg_radiance_status": [V, P(I32), P(I32), P(I32)], "pg_radiance_export": [V, U64, V],
+        "pg_radiance_import": [V, U64, V], "pg_radiance_query": [V, U64, V, V, V, V, V, V], "pg_radiance_rr": _RR,
+    },
+    "pgsd_bounce.h": {  # fraction, selection, guide bounce and radiance estimate behind one KD descent
+        "pg_bounce": [V, U64, P(pg_bounce_args), V],
+    },
+    "pgsd_irradiance.h": {  # irradiance estimates per spatial leaf: order-2 spherical harmonics
+        "pg_irradiance_build": [V, V], "pg_irradiance_status": [V, P(I32)], "pg_irradiance_export": [V, U64, V],
+        "pg_irradiance_import": [V, U64, V], "pg_irradiance_query": [V, U64, V, V, V, V, V], "pg_irradiance_rr": _RR,
+    },
+}
+RESTYPES = {"pg_last_error": C.c_char_p}  # (pg_abi_version returns the c_int of all the others: it only has no context to fail on)
+EXPORTS, EXPORTS_WARP, EXPORTS_FRACTION, EXPORTS_TARGET, EXPORTS_RADIANCE, EXPORTS_BOUNCE, EXPORTS_IRRADIANCE = (
+    tuple(entry_points) for entry_points in SURFACE.values())
 
 
 def source_hash() -> str:
-    """sha256 (16 hex digits) over the library's sources (csrc/*.hip, csrc/*.hpp, include/pgsd.h, include/pgsd_warp.h,
-    include/pgsd_fraction.h, include/pgsd_target.h, include/pgsd_radiance.h, include/pgsd_irradiance.h, include/pgsd_bounce.h):
+    """sha256 (16 hex digits) over the library's sources (csrc/*.hip, csrc/*.hpp, then the headers of SURFACE in its order):
     names the code a profile was taken of (profiles/pmc_traffic.json) so that bench.py never pairs old counters with new kernels."""
     import glob
     import hashlib
     h = hashlib.sha256()
     files = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
-    files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd.h"))
-    files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_warp.h"))
-    files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_fraction.h"))
-    files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_target.h"))
-    files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_radiance.h"))
-    files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_bounce.h"))
-    files.append(os.path.join(os.path.dirname(_PKG), "include", "pgsd_irradiance.h"))
+    files += [os.path.join(os.path.dirname(_PKG), "include", header) for header in SURFACE]
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
@@ -212,100 +242,15 @@ def lib() -> C.CDLL:
     except ImportError:
         pass
     L = C.CDLL(LIB_PATH)
-    V, U64, I32, U32 = C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32
-    L.pg_last_error.restype = C.c_char_p
-    L.pg_last_error.argtypes = [V]
     L.pg_abi_version.restype = C.c_int
     if L.pg_abi_version() != ABI_VERSION:  # (a library left over from an older build: its structs have other layouts)
         raise ImportError(f"{LIB_PATH} has ABI version {L.pg_abi_version()}, these bindings are written for {ABI_VERSION}: "
                           "rebuild it with `python -c 'import __graft_entry__ as g; g.build()'`")
-    L.pg_create.argtypes = [C.POINTER(V), C.c_int]
-    L.pg_destroy.argtypes = [V]
-    L.pg_setup.argtypes = [V, V, V, U64, I32, I32, I32, I32, C.c_float]
-    L.pg_set_iteration.argtypes = [V, I32, I32]
-    L.pg_set_splat_filter.argtypes = [V, I32, I32, U32]
-    L.pg_get_leaf_node_index.argtypes = [V, U64, V, V, V, V]
-    L.pg_sample.argtypes = [V, U64, V, V, V, V, V, V, V]
-    L.pg_pdf.argtypes = [V, U64, V, V, V, V, V]
-    L.pg_guide_bounce.argtypes = [V, U64, V, V, V, V, V, V, V, V, V, V, V, V]
-    L.pg_compact_lanes.argtypes = [V, U64, V, V, V, V, V]
-    L.pg_rng_seed.argtypes = [V, U64, U32, U32, V, V, V]
-    L.pg_splat.argtypes = [V, U64, C.POINTER(pg_records), V, V]
-    L.pg_process_records.argtypes = [V, U64, I32, V, C.POINTER(pg_dense_records), C.POINTER(pg_records_out), V, V]
-    L.pg_process_and_splat.argtypes = [V, U64, I32, V, C.POINTER(pg_dense_records), V]
-    L.pg_refine_and_swap.argtypes = [V, V]
-    L.pg_debug_fail_alloc.argtypes = [C.c_int64]
-    L.pg_read_shade_phases.argtypes = [V, C.POINTER(C.c_uint64), I32]
-    L.pg_debug_fail_alloc_pending.argtypes = []
-    L.pg_accumulators.argtypes = [V, C.POINTER(V), C.POINTER(U64)]
-    L.pg_export_sizes.argtypes = [V, C.POINTER(pg_tree_sizes)]
-    L.pg_export.argtypes = [V, C.POINTER(pg_tree_sizes), C.POINTER(pg_tree_columns)]
-    L.pg_import.argtypes = [V, C.POINTER(pg_tree_sizes), C.POINTER(pg_tree_columns)]
-    L.pg_export_accumulators.argtypes = [V, C.POINTER(pg_tree_sizes), V, V, V]
-    L.pg_get_stats.argtypes = [V, C.POINTER(pg_stats)]
-    L.pg_enable_depth_counters.argtypes = [V, I32]
-    L.pg_read_depth_counters.argtypes = [V, C.POINTER(pg_depth_counters), I32]
-    L.pg_scene_set.argtypes = [V, U64, V, C.POINTER(pg_camera)]
-    L.pg_render_pass.argtypes = [V, C.POINTER(pg_pass_params), V, V, V, V, V]
-    L.pg_enable_kernel_timing.argtypes = [V, I32]
-    L.pg_read_kernel_timing.argtypes = [V, C.POINTER(pg_kernel_timing), I32]
-    L.pg_render_live_counts.argtypes = [V, C.POINTER(C.c_uint32), I32]
-    L.pg_film_tent.argtypes = [V, U32, I32, V, V, V]
-    L.pg_film.argtypes = [V, I32, U32, I32, V, V, V]
-    L.pg_film_stripes.argtypes = [V, I32, U32, I32, V, V, U32, U32, U32, V]
-    L.pg_film_batched.argtypes = [V, I32, U32, I32, V, V, U32, U32, U32, V]
-    L.pg_film_batched_accumulate.argtypes = [V, I32, U32, I32, V, V, C.c_float, I32, U32, U32, U32, V]
-    L.pg_render_overlap.argtypes = [V, I32]
-    L.pg_render_sort.argtypes = [V, I32]
-    L.pg_render_stages.argtypes = [V, I32]
-    L.pg_math_eval.argtypes = [V, I32, U64, V, V, V]
-    L.pg_scene_set_ex.argtypes = [V, C.POINTER(pg_scene_desc), C.POINTER(pg_camera)]
-    L.pg_comm_unique_id.argtypes = [V, V]
-    L.pg_comm_init.argtypes = [V, I32, I32, V]
-    L.pg_comm_attach.argtypes = [V, V, I32]
-    L.pg_comm_destroy.argtypes = [V]
-    L.pg_allreduce.argtypes = [V, V]
-    L.pg_comm_info.argtypes = [V, C.POINTER(I32), C.POINTER(I32)]
-    L.pg_exchange_pack.argtypes = [V, C.POINTER(V), C.POINTER(U64), V]
-    L.pg_exchange_unpack.argtypes = [V, V]
-    L.pg_exchange_pack_words.argtypes = [V, U64, V]
-    L.pg_exchange_unpack_words.argtypes = [V, U64, V]
-    L.pg_sort_places.argtypes = [V, U64, V, V, V, V]
-    L.pg_scene_intersect.argtypes = [V, U64, V, V, V, I32, I32, V, V, V, V]
-    L.pg_bsdf_probe.argtypes = [V, U64, U64, V, V, V, V, V, I32, V, V, V, V, V, V, V, V]
-    L.pg_surface_probe.argtypes = [V, U64, V, V, V, V, V, V, V, V, V]
-    L.pg_render_reserve.argtypes = [V, U64]
-    L.pg_render_split_pipeline.argtypes = [V, C.c_int32]
-    L.pg_render_record_geometry.argtypes = [V, I32]
-    L.pg_render_export_records.argtypes = [V, I32, C.POINTER(pg_records_out), V, V, V]
-    L.pg_sample_warp.argtypes = [V, U64, V, V, V, V, V, V]
-    L.pg_invert_warp.argtypes = [V, U64, V, V, V, V, V, V]
-    L.pg_guide_bounce_warp.argtypes = [V, U64, V, V, V, V, V, V, V, V, V, V, V]
-    L.pg_fraction_enable.argtypes = [V, C.POINTER(pg_fraction_params)]
-    L.pg_fraction_query.argtypes = [V, U64, V, V, V, V]
-    L.pg_fraction_record.argtypes = [V, U64, C.POINTER(pg_fraction_records), V, V]
-    L.pg_fraction_step.argtypes = [V, V]
-    L.pg_fraction_accumulators.argtypes = [V, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-    L.pg_fraction_export.argtypes = [V, U64, V, V, V, V, V, V, V]
-    L.pg_fraction_import.argtypes = [V, U64, V, V, V, V, V, V]
-    L.pg_target_apply.argtypes = [V, I32, V]
-    L.pg_target_applied.argtypes = [V, C.POINTER(I32)]
-    L.pg_radiance_enable.argtypes = [V, I32]
-    L.pg_radiance_status.argtypes = [V, C.POINTER(I32), C.POINTER(I32), C.POINTER(I32)]
-    L.pg_radiance_export.argtypes = [V, U64, V]
-    L.pg_radiance_import.argtypes = [V, U64, V]
-    L.pg_radiance_query.argtypes = [V, U64, V, V, V, V, V, V]
-    L.pg_radiance_rr.argtypes = [V, U64, V, V, V, V, C.POINTER(pg_rr_params), V, V, V, V, V, V, V]
-    L.pg_bounce.argtypes = [V, U64, C.POINTER(pg_bounce_args), V]
-    L.pg_irradiance_build.argtypes = [V, V]
-    L.pg_irradiance_status.argtypes = [V, C.POINTER(I32)]
-    L.pg_irradiance_export.argtypes = [V, U64, V]
-    L.pg_irradiance_import.argtypes = [V, U64, V]
-    L.pg_irradiance_query.argtypes = [V, U64, V, V, V, V, V]
-    L.pg_irradiance_rr.argtypes = [V, U64, V, V, V, V, C.POINTER(pg_rr_params), V, V, V, V, V, V, V]
-    for name in EXPORTS + EXPORTS_WARP + EXPORTS_FRACTION + EXPORTS_TARGET + EXPORTS_RADIANCE + EXPORTS_BOUNCE + EXPORTS_IRRADIANCE:
-        if name not in ("pg_last_error", "pg_abi_version"):
-            getattr(L, name).restype = C.c_int
+    for entry_points in SURFACE.values():
+        for name, argtypes in entry_points.items():
+            fn = getattr(L, name)  # (a missing symbol is an AttributeError here)
+            fn.argtypes = list(argtypes)
+            fn.restype = RESTYPES.get(name, C.c_int)
     _lib = L
     return L
 

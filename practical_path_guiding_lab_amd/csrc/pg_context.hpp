@@ -192,6 +192,10 @@ struct Radiance {
 } // namespace pg
 
 struct pg_render_state; // pg_render.hip (its scene: pg_scene_state.hpp)
+struct pg_rr_params;    // include/pgsd_radiance.h
+namespace pg {
+struct RrArgs;          // pg_guide_dev.hpp
+}
 
 struct pg_context {
 	pg_render_state *render = nullptr;
@@ -268,6 +272,11 @@ void launch_fraction_carry(const long long *old_tab, uint32_t n_old, const uint3
 // pg_kernels_radiance.hip: the weights of the refined forest -- new tree t takes the count resolved for old tree tree_src[t]
 void launch_radiance_carry(const unsigned long long *tree_count, uint32_t n_old, const uint32_t *tree_src, unsigned long long *w_new,
                            uint32_t n_new, hipStream_t s);
+// the host checks the calls on the estimates share (pg_radiance_query / _rr, pg_irradiance_build / _import, pg_bounce), each
+// PG_OK or the refusal with `who` in front: radiance is enabled, its weights are known, the tree is not a second-moment tree;
+int radiance_source(pg_context *ctx, const char *who);
+// and pg_rr_params are valid, which fills the window (lo, hi) and the split limit (max_split, max_split_f) of rr
+int rr_window(pg_context *ctx, const char *who, const pg_rr_params *params, RrArgs &rr);
 // pg_render.hip
 void destroy_render_state(pg_context *ctx);
 // pg_render_wave.hip

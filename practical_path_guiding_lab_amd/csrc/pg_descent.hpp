@@ -75,6 +75,11 @@ __device__ __forceinline__ uint32_t kd_descend(const KdNode *kd, float x, float 
 // thread copies ONE plane (195 of 256 threads) -- written with `i += blockDim.x` the copy compiled to three loops (a vectorised
 // one, its two remainders), each load -> wait -> store, at the head of every kernel that walks the KD tree (round 6, from the listings).
 constexpr int kStageThreads = 256;
+// The one-lane-per-query kernels (pg_kernels_query / _warp / _fraction / _radiance / _irradiance / _bounce.hip): their workgroup
+// and the grid that covers n lanes.
+constexpr int kQueryBlock = 256;
+static_assert(kQueryBlock == kStageThreads, "stage_kd_planes copies one plane per thread");
+static inline dim3 query_grid(uint64_t n) { return dim3((unsigned)((n + kQueryBlock - 1) / kQueryBlock)); }
 __device__ __forceinline__ void stage_kd_planes(float *s_planes, const TreeView &t)
 {
 	static_assert(3 * kKdGridPlanes <= kStageThreads, "one plane per thread");

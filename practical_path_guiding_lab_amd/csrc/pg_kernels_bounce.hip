@@ -17,9 +17,6 @@
 
 namespace pg {
 
-constexpr int kBBlock = 256;
-static_assert(kBBlock == kStageThreads, "stage_kd_planes copies one plane per thread");
-
 // what the kernel needs beside the caller's arrays
 struct BounceTables {
 	const FracLeaf *leaves;            // nullptr: the learned fraction is off, f = f_const
@@ -56,14 +53,14 @@ __device__ __forceinline__ void jump_prefetch_pair(JumpRef jump, uint32_t tree, 
 // kWarp: the select == 2 lanes warp u (pg_guide_bounce_warp) instead of drawing from their PCG32 stream (pg_guide_bounce).
 // kRadiance: L_dir_out or L_mean_out is given.
 template <bool kWarp, bool kRadiance>
-__global__ __launch_bounds__(kBBlock) void k_guided_bounce(TreeView t, uint64_t n, pg_bounce_args a, BounceTables tb)
+__global__ __launch_bounds__(kQueryBlock) void k_guided_bounce(TreeView t, uint64_t n, pg_bounce_args a, BounceTables tb)
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
-	const uint64_t tid = (uint64_t)blockIdx.x * kBBlock + threadIdx.x;
+	const uint64_t tid = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
 	// the compacted list of k_guide_bounce: [0, front) from the start of lane_index, the next `back` entries from its end
 	const uint64_t front = a.lane_index ? (uint64_t)a.d_lane_count[0] : n;
 	const uint64_t live = a.lane_index ? front + (uint64_t)a.d_lane_count[1] : n;
-	if ((uint64_t)blockIdx.x * kBBlock >= live) return; // whole workgroup idle (uniform)
+	if ((uint64_t)blockIdx.x * kQueryBlock >= live) return; // whole workgroup idle (uniform)
 	stage_kd_planes(s_planes, t);
 	if (!(tid < live && tid < n)) return;
 	const uint64_t i = a.lane_index ? (uint64_t)a.lane_index[tid < front ? tid : n - 1 - (tid - front)] : tid;
@@ -165,7 +162,7 @@ __global__ __launch_bounds__(kBBlock) void k_guided_bounce(TreeView t, uint64_t 
 template <bool kWarp, bool kRadiance>
 static void launch_guided_bounce(const TreeView &t, uint64_t n, const pg_bounce_args &a, const BounceTables &tb, hipStream_t s)
 {
-	hipLaunchKernelGGL((k_guided_bounce<kWarp, kRadiance>), dim3((unsigned)((n + kBBlock - 1) / kBBlock)), dim3(kBBlock), 0, s, t, n, a, tb);
+	hipLaunchKernelGGL((k_guided_bounce<kWarp, kRadiance>), query_grid(n), dim3(kQueryBlock), 0, s, t, n, a, tb);
 }
 
 } // namespace pg
@@ -190,13 +187,8 @@ int pg_bounce(pg_context *ctx, uint64_t n, const pg_bounce_args *args, void *str
 		return fail(ctx, PG_ERR_INVALID, "pg_bounce: u_select is NULL in the warp form, which has no stream to draw the selection from");
 	if (!a.u_select && !streams) return fail(ctx, PG_ERR_INVALID, "pg_bounce: u_select is NULL and so are rng_state / rng_inc");
 	const bool radiance = a.L_dir_out != nullptr || a.L_mean_out != nullptr;
-	if (radiance) { // (pg_radiance_query's reasons)
-		if (!ctx->rad.on) return fail(ctx, PG_ERR_INVALID, "pg_bounce: a radiance output is requested: call pg_radiance_enable first");
-		if (!ctx->rad.valid)
-			return fail(ctx, PG_ERR_INVALID, "pg_bounce: a radiance output is requested: the weights of this tree are unknown (no refine since pg_radiance_enable, no pg_radiance_import)");
-		if (ctx->rad.of_target)
-			return fail(ctx, PG_ERR_INVALID, "pg_bounce: a radiance output is requested: sdTree_prev was refined from a second-moment target (pg_target_apply): it holds roots of second moments, not radiance");
-	}
+	if (radiance) // (pg_radiance_query's reasons)
+		if (int rc = radiance_source(ctx, "pg_bounce: a radiance output is requested")) return rc;
 	if (n == 0) return PG_OK;
 	BounceTables tb;
 	tb.leaves = ctx->frac.on ? ctx->frac.leaves(ctx->f.n_trees) : nullptr;

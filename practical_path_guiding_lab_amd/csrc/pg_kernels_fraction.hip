@@ -26,23 +26,20 @@
 
 namespace pg {
 
-constexpr int kFBlock = 256;
-static_assert(kFBlock == kStageThreads, "stage_kd_planes copies one plane per thread");
-
 constexpr float kThetaMax = PG_FRACTION_THETA_MAX;
 
 // logistic_f32 (the logistic of pgsd_fraction.h): pg_guide_dev.hpp -- pg_kernels_bounce.hip inlines it too
 __device__ __forceinline__ float load_theta(const FracLeaf *leaves, uint32_t tree) { return leaves[tree].theta; }
 
 // ---- query -----------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kFBlock) void k_fraction_query(TreeView t, const FracLeaf *__restrict__ leaves, float theta0,
+__global__ __launch_bounds__(kQueryBlock) void k_fraction_query(TreeView t, const FracLeaf *__restrict__ leaves, float theta0,
                                                             uint64_t n, const float *__restrict__ p,
                                                             const uint8_t *__restrict__ active,
                                                             float *__restrict__ fraction_out)
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
 	stage_kd_planes(s_planes, t);
-	const uint64_t i = (uint64_t)blockIdx.x * kFBlock + threadIdx.x;
+	const uint64_t i = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
 	if (i >= n) return;
 	const bool act = active ? active[i] != 0 : true;
 	float theta = theta0;
@@ -64,7 +61,7 @@ constexpr int kWaveRounds = 4;     // distinct trees of a wave merged in registe
 constexpr int kTableSlots = 512;   // LDS hash table of the workgroup: tree -> four words
 constexpr int kProbes = 4;         // linear probes before a lane gives up on the table and adds to the device itself
 constexpr unsigned kRecordGroupsPerCu = 8;
-static_assert((kTableSlots & (kTableSlots - 1)) == 0 && kTableSlots % (kFBlock / 4) == 0, "the flush takes 64 slots per pass");
+static_assert((kTableSlots & (kTableSlots - 1)) == 0 && kTableSlots % (kQueryBlock / 4) == 0, "the flush takes 64 slots per pass");
 
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 {
@@ -123,22 +120,22 @@ __device__ __forceinline__ void table_add(uint32_t *s_key, unsigned long long *s
 	}
 }
 
-__global__ __launch_bounds__(kFBlock) void k_fraction_record(TreeView t, const FracLeaf *__restrict__ leaves,
+__global__ __launch_bounds__(kQueryBlock) void k_fraction_record(TreeView t, const FracLeaf *__restrict__ leaves,
                                                              long long *__restrict__ acc, int loss, uint64_t m,
                                                              pg_fraction_records r, const uint32_t *__restrict__ d_count)
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
 	__shared__ uint32_t s_key[kTableSlots];
 	__shared__ unsigned long long s_val[kTableSlots * 4];
-	for (int k = threadIdx.x; k < kTableSlots; k += kFBlock) s_key[k] = kNoTree;
-	for (int k = threadIdx.x; k < kTableSlots * 4; k += kFBlock) s_val[k] = 0ull;
+	for (int k = threadIdx.x; k < kTableSlots; k += kQueryBlock) s_key[k] = kNoTree;
+	for (int k = threadIdx.x; k < kTableSlots * 4; k += kQueryBlock) s_val[k] = 0ull;
 	stage_kd_planes(s_planes, t); // (holds the barrier behind the table's initialisation)
 	uint64_t valid = d_count ? (uint64_t)*d_count : m; // plane stride stays m
 	if (valid > m) valid = m;
-	const uint64_t tiles = (valid + kFBlock - 1) / kFBlock;
+	const uint64_t tiles = (valid + kQueryBlock - 1) / kQueryBlock;
 	const unsigned lane = threadIdx.x & 63u;
 	for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) { // (uniform over the workgroup)
-		const uint64_t i = tile * kFBlock + threadIdx.x;
+		const uint64_t i = tile * kQueryBlock + threadIdx.x;
 		uint32_t tree = kNoTree;
 		Limbs q = {0, 0, 0};
 		if (i < valid) {
@@ -179,7 +176,7 @@ __global__ __launch_bounds__(kFBlock) void k_fraction_record(TreeView t, const F
 	__syncthreads();
 	const unsigned word = threadIdx.x & 3u;
 #pragma unroll 1
-	for (int base = 0; base < kTableSlots; base += kFBlock / 4) {
+	for (int base = 0; base < kTableSlots; base += kQueryBlock / 4) {
 		const int slot = base + (int)(threadIdx.x >> 2);
 		const uint32_t key = s_key[slot];
 		const unsigned long long v = s_val[4 * slot + word];
@@ -189,10 +186,10 @@ __global__ __launch_bounds__(kFBlock) void k_fraction_record(TreeView t, const F
 }
 
 // ---- step ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kFBlock) void k_fraction_step(FracLeaf *__restrict__ leaves, long long *__restrict__ acc,
+__global__ __launch_bounds__(kQueryBlock) void k_fraction_step(FracLeaf *__restrict__ leaves, long long *__restrict__ acc,
                                                            uint32_t n_trees, pg_fraction_params prm)
 {
-	const uint32_t t = blockIdx.x * kFBlock + threadIdx.x;
+	const uint32_t t = blockIdx.x * kQueryBlock + threadIdx.x;
 	if (t >= n_trees) return;
 	long long *a = acc + (size_t)kAccWords * t;
 	const long long count = a[3];
@@ -215,9 +212,9 @@ __global__ __launch_bounds__(kFBlock) void k_fraction_step(FracLeaf *__restrict_
 
 // ---- tables ----------------------------------------------------------------------------------------------------------------
 // every leaf at its start values, zero accumulators (pg_fraction_enable)
-__global__ __launch_bounds__(kFBlock) void k_fraction_init(long long *__restrict__ tab, uint32_t n_trees, float theta0)
+__global__ __launch_bounds__(kQueryBlock) void k_fraction_init(long long *__restrict__ tab, uint32_t n_trees, float theta0)
 {
-	const uint32_t t = blockIdx.x * kFBlock + threadIdx.x;
+	const uint32_t t = blockIdx.x * kQueryBlock + threadIdx.x;
 	if (t >= n_trees) return;
 	long long *a = tab + (size_t)kAccWords * t;
 	a[0] = 0; a[1] = 0; a[2] = 0; a[3] = 0;
@@ -227,11 +224,11 @@ __global__ __launch_bounds__(kFBlock) void k_fraction_init(long long *__restrict
 }
 
 // the table of a refined forest: new leaf t is a copy of old leaf tree_src[t] (pg_refine.hip), its accumulator zero
-__global__ __launch_bounds__(kFBlock) void k_fraction_carry(const long long *__restrict__ old_tab, uint32_t n_old,
+__global__ __launch_bounds__(kQueryBlock) void k_fraction_carry(const long long *__restrict__ old_tab, uint32_t n_old,
                                                             const uint32_t *__restrict__ tree_src,
                                                             long long *__restrict__ new_tab, uint32_t n_new)
 {
-	const uint32_t t = blockIdx.x * kFBlock + threadIdx.x;
+	const uint32_t t = blockIdx.x * kQueryBlock + threadIdx.x;
 	if (t >= n_new) return;
 	long long *a = new_tab + (size_t)kAccWords * t;
 	a[0] = 0; a[1] = 0; a[2] = 0; a[3] = 0;
@@ -241,13 +238,11 @@ __global__ __launch_bounds__(kFBlock) void k_fraction_carry(const long long *__r
 	    reinterpret_cast<const FracLeaf *>(old_tab + (size_t)n_old * kAccWords)[src];
 }
 
-static inline dim3 frac_grid(uint64_t n) { return dim3((unsigned)((n + kFBlock - 1) / kFBlock)); }
-
 void launch_fraction_carry(const long long *old_tab, uint32_t n_old, const uint32_t *tree_src, long long *new_tab, uint32_t n_new,
                            hipStream_t s)
 {
 	if (n_new == 0) return;
-	hipLaunchKernelGGL(k_fraction_carry, frac_grid(n_new), dim3(kFBlock), 0, s, old_tab, n_old, tree_src, new_tab, n_new);
+	hipLaunchKernelGGL(k_fraction_carry, query_grid(n_new), dim3(kQueryBlock), 0, s, old_tab, n_old, tree_src, new_tab, n_new);
 }
 
 static bool params_ok(const pg_fraction_params &p)
@@ -287,7 +282,7 @@ int pg_fraction_enable(pg_context *ctx, const pg_fraction_params *params)
 		fr.disable();
 		return hip_fail(ctx, e, "pg_fraction_enable: table");
 	}
-	hipLaunchKernelGGL(k_fraction_init, frac_grid(n), dim3(kFBlock), 0, nullptr, fr.tab.p, n, params->theta0);
+	hipLaunchKernelGGL(k_fraction_init, query_grid(n), dim3(kQueryBlock), 0, nullptr, fr.tab.p, n, params->theta0);
 	PG_LAUNCHED(ctx);
 	PG_HIP(ctx, hipDeviceSynchronize());
 	fr.prm = *params;
@@ -299,9 +294,9 @@ int pg_fraction_query(pg_context *ctx, uint64_t n, const float *p, const uint8_t
 {
 	PG_FRACTION_ON(ctx, "pg_fraction_query");
 	if (n && (!p || !fraction_out)) return fail(ctx, PG_ERR_INVALID, "pg_fraction_query: NULL pointer");
-	if (n > 0xffffffffull * kFBlock) return fail(ctx, PG_ERR_INVALID, "pg_fraction_query: too many lanes for one launch");
+	if (n > 0xffffffffull * kQueryBlock) return fail(ctx, PG_ERR_INVALID, "pg_fraction_query: too many lanes for one launch");
 	if (n == 0) return PG_OK;
-	hipLaunchKernelGGL(k_fraction_query, frac_grid(n), dim3(kFBlock), 0, (hipStream_t)stream, ctx->view(),
+	hipLaunchKernelGGL(k_fraction_query, query_grid(n), dim3(kQueryBlock), 0, (hipStream_t)stream, ctx->view(),
 	                   ctx->frac.leaves(ctx->f.n_trees), ctx->frac.prm.theta0, n, p, active, fraction_out);
 	PG_LAUNCHED(ctx);
 	return PG_OK;
@@ -316,8 +311,8 @@ int pg_fraction_record(pg_context *ctx, uint64_t m, const pg_fraction_records *r
 	if (m >= 0xffffffffull) return fail(ctx, PG_ERR_INVALID, "pg_fraction_record: more than 2^32 - 1 records in one call");
 	if (m == 0) return PG_OK;
 	// a persistent grid: a block merges all its tiles in LDS before it sends a leaf's sum out
-	const uint64_t tiles = (m + kFBlock - 1) / kFBlock, cap = (uint64_t)ctx->n_cus * kRecordGroupsPerCu;
-	hipLaunchKernelGGL(k_fraction_record, dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(kFBlock), 0, (hipStream_t)stream,
+	const uint64_t tiles = (m + kQueryBlock - 1) / kQueryBlock, cap = (uint64_t)ctx->n_cus * kRecordGroupsPerCu;
+	hipLaunchKernelGGL(k_fraction_record, dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(kQueryBlock), 0, (hipStream_t)stream,
 	                   ctx->view(), ctx->frac.leaves(ctx->f.n_trees), ctx->frac.acc(), (int)ctx->frac.prm.loss, m, *rec, d_count);
 	PG_LAUNCHED(ctx);
 	return PG_OK;
@@ -327,7 +322,7 @@ int pg_fraction_step(pg_context *ctx, void *stream)
 {
 	PG_FRACTION_ON(ctx, "pg_fraction_step");
 	const uint32_t n = ctx->f.n_trees;
-	hipLaunchKernelGGL(k_fraction_step, frac_grid(n), dim3(kFBlock), 0, (hipStream_t)stream, ctx->frac.leaves(n), ctx->frac.acc(), n,
+	hipLaunchKernelGGL(k_fraction_step, query_grid(n), dim3(kQueryBlock), 0, (hipStream_t)stream, ctx->frac.leaves(n), ctx->frac.acc(), n,
 	                   ctx->frac.prm);
 	PG_LAUNCHED(ctx);
 	return PG_OK;

@@ -16,8 +16,6 @@
 
 namespace pg {
 
-constexpr int kIrrBlock = 256;
-static_assert(kIrrBlock == kStageThreads, "stage_kd_planes copies one plane per thread");
 static_assert(kIrrStride * sizeof(float) == 3 * 16 && kIrrCoeffs <= kIrrStride, "a tree's coefficients leave as three 16-byte gathers");
 constexpr uint32_t kIrrNoTree = 0xffffffffu; // a record no root reaches (the cells are set to it before every build)
 constexpr uint32_t kIrrMaxDepth = 31;        // (ix, iy) of a cell are 32-bit: deeper than any descent of the library goes
@@ -126,10 +124,10 @@ __device__ __forceinline__ void store16(void *p, uint32_t a, uint32_t b, uint32_
 
 // ---- the build -------------------------------------------------------------------------------------------------------------
 // per tree: its sums start at zero; the root record of a tree that has one gets the whole square
-__global__ __launch_bounds__(kIrrBlock) void k_irr_roots(const TreeHead *__restrict__ head, uint32_t n_trees, uint32_t n_rec,
+__global__ __launch_bounds__(kQueryBlock) void k_irr_roots(const TreeHead *__restrict__ head, uint32_t n_trees, uint32_t n_rec,
                                                          long long *__restrict__ sums, uint4 *__restrict__ cells)
 {
-	const uint32_t t = blockIdx.x * kIrrBlock + threadIdx.x;
+	const uint32_t t = blockIdx.x * kQueryBlock + threadIdx.x;
 	if (t >= n_trees) return;
 #pragma unroll
 	for (uint32_t j = 0; j < kIrrCoeffs; ++j) sums[(size_t)t * kIrrCoeffs + j] = 0;
@@ -139,11 +137,11 @@ __global__ __launch_bounds__(kIrrBlock) void k_irr_roots(const TreeHead *__restr
 
 // per record of one level [begin, end): children that have records get their cells (they lie in later levels: a child index
 // that does not is not followed), leaf children are projected
-__global__ __launch_bounds__(kIrrBlock) void k_irr_level(const QuadRec *__restrict__ rec, const TreeHead *__restrict__ head,
+__global__ __launch_bounds__(kQueryBlock) void k_irr_level(const QuadRec *__restrict__ rec, const TreeHead *__restrict__ head,
                                                          uint32_t n_trees, uint32_t n_rec, uint32_t begin, uint32_t end,
                                                          uint4 *__restrict__ cells, long long *__restrict__ sums)
 {
-	const uint32_t r = begin + blockIdx.x * kIrrBlock + threadIdx.x; // (begin + grid < 2^32 + 256: the host keeps n_rec below 2^32 - 16)
+	const uint32_t r = begin + blockIdx.x * kQueryBlock + threadIdx.x; // (begin + grid < 2^32 + 256: the host keeps n_rec below 2^32 - 16)
 	uint32_t tree = kIrrNoTree;
 	long long acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 	if (r >= begin && r < end) {
@@ -191,10 +189,10 @@ __global__ __launch_bounds__(kIrrBlock) void k_irr_level(const QuadRec *__restri
 }
 
 // per tree: a root that is the leaf is its own one cell; then the conversion
-__global__ __launch_bounds__(kIrrBlock) void k_irr_finish(const TreeHead *__restrict__ head, const unsigned long long *__restrict__ wtab,
+__global__ __launch_bounds__(kQueryBlock) void k_irr_finish(const TreeHead *__restrict__ head, const unsigned long long *__restrict__ wtab,
                                                           uint32_t n_trees, const long long *__restrict__ sums, float *__restrict__ tab)
 {
-	const uint32_t t = blockIdx.x * kIrrBlock + threadIdx.x;
+	const uint32_t t = blockIdx.x * kQueryBlock + threadIdx.x;
 	if (t >= n_trees) return;
 	const TreeHead h = load_head(head, t);
 	const uint2 wv = gather8(wtab + t);
@@ -228,13 +226,13 @@ __global__ __launch_bounds__(kIrrBlock) void k_irr_finish(const TreeHead *__rest
 // ---- the estimate and the decision -------------------------------------------------------------------------------------------
 // normal == nullptr (uniform): the mean over all orientations, k0.
 template <bool kDecide>
-__global__ __launch_bounds__(kIrrBlock) void k_irradiance(TreeView t, const float *__restrict__ tab, uint64_t n,
+__global__ __launch_bounds__(kQueryBlock) void k_irradiance(TreeView t, const float *__restrict__ tab, uint64_t n,
                                                           const float *__restrict__ p, const float *__restrict__ normal,
                                                           const uint8_t *__restrict__ active, float *__restrict__ E_out, RrArgs rr)
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
 	stage_kd_planes(s_planes, t);
-	const uint64_t i = (uint64_t)blockIdx.x * kIrrBlock + threadIdx.x;
+	const uint64_t i = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
 	if (i >= n) return;
 	const bool act = active ? active[i] != 0 : true;
 	float E = 0.0f;
@@ -288,22 +286,9 @@ __global__ __launch_bounds__(kIrrBlock) void k_irradiance(TreeView t, const floa
 	}
 }
 
-static inline dim3 irr_grid(uint64_t n) { return dim3((unsigned)((n + kIrrBlock - 1) / kIrrBlock)); }
-
 } // namespace pg
 
 using namespace pg;
-
-// PG_READY and what the estimates of pgsd_radiance.h need: the table is projected with the statistical weights
-#define PG_IRRADIANCE_SOURCE(ctx, who)                                                                                        \
-	do {                                                                                                                      \
-		PG_READY(ctx);                                                                                                        \
-		if (!(ctx)->rad.on) return fail((ctx), PG_ERR_INVALID, who ": call pg_radiance_enable first");                       \
-		if (!(ctx)->rad.valid)                                                                                                \
-			return fail((ctx), PG_ERR_INVALID, who ": the weights of this tree are unknown (no refine since pg_radiance_enable, no pg_radiance_import)"); \
-		if ((ctx)->rad.of_target)                                                                                             \
-			return fail((ctx), PG_ERR_INVALID, who ": sdTree_prev was refined from a second-moment target (pg_target_apply): it holds roots of second moments, not radiance"); \
-	} while (0)
 
 #define PG_IRRADIANCE_BUILT(ctx, who)                                                                                         \
 	do {                                                                                                                      \
@@ -316,7 +301,8 @@ extern "C" {
 
 int pg_irradiance_build(pg_context *ctx, void *stream)
 {
-	PG_IRRADIANCE_SOURCE(ctx, "pg_irradiance_build");
+	PG_READY(ctx);
+	if (int rc = radiance_source(ctx, "pg_irradiance_build")) return rc; // (the table is projected with the statistical weights)
 	Forest &f = ctx->f;
 	Irradiance &ir = ctx->rad.irr;
 	hipStream_t s = (hipStream_t)stream;
@@ -328,14 +314,14 @@ int pg_irradiance_build(pg_context *ctx, void *stream)
 	PG_HIP(ctx, ir.sums.ensure((size_t)f.n_trees * kIrrCoeffs, 1.25));
 	PG_HIP(ctx, ir.cells.ensure(f.n_rec, 1.25));
 	if (f.n_rec) PG_HIP(ctx, hipMemsetAsync(ir.cells.p, 0xff, (size_t)f.n_rec * sizeof(uint4), s));
-	hipLaunchKernelGGL(k_irr_roots, irr_grid(f.n_trees), dim3(kIrrBlock), 0, s, f.head.p, f.n_trees, f.n_rec, ir.sums.p, ir.cells.p);
+	hipLaunchKernelGGL(k_irr_roots, query_grid(f.n_trees), dim3(kQueryBlock), 0, s, f.head.p, f.n_trees, f.n_rec, ir.sums.p, ir.cells.p);
 	for (size_t l = 0; l < levels; ++l) {
 		const uint32_t begin = f.level_off[l], end = f.level_off[l + 1];
 		if (end <= begin) continue;
-		hipLaunchKernelGGL(k_irr_level, irr_grid(end - begin), dim3(kIrrBlock), 0, s, f.rec.p, f.head.p, f.n_trees, f.n_rec, begin, end,
+		hipLaunchKernelGGL(k_irr_level, query_grid(end - begin), dim3(kQueryBlock), 0, s, f.rec.p, f.head.p, f.n_trees, f.n_rec, begin, end,
 		                   ir.cells.p, ir.sums.p);
 	}
-	hipLaunchKernelGGL(k_irr_finish, irr_grid(f.n_trees), dim3(kIrrBlock), 0, s, f.head.p, ctx->rad.tab.p, f.n_trees, ir.sums.p, ir.tab.p);
+	hipLaunchKernelGGL(k_irr_finish, query_grid(f.n_trees), dim3(kQueryBlock), 0, s, f.head.p, ctx->rad.tab.p, f.n_trees, ir.sums.p, ir.tab.p);
 	PG_LAUNCHED(ctx);
 	ir.built = 1;
 	return PG_OK;
@@ -363,7 +349,8 @@ int pg_irradiance_export(pg_context *ctx, uint64_t n_trees, float *h_coeff)
 
 int pg_irradiance_import(pg_context *ctx, uint64_t n_trees, const float *h_coeff)
 {
-	PG_IRRADIANCE_SOURCE(ctx, "pg_irradiance_import");
+	PG_READY(ctx);
+	if (int rc = radiance_source(ctx, "pg_irradiance_import")) return rc; // (the table is projected with the statistical weights)
 	if (n_trees != ctx->f.n_trees) return fail(ctx, PG_ERR_INVALID, "pg_irradiance_import: n_trees does not match pg_export_sizes' n_roots");
 	if (!h_coeff) return fail(ctx, PG_ERR_INVALID, "pg_irradiance_import: NULL pointer");
 	PG_HIP(ctx, hipDeviceSynchronize());
@@ -382,10 +369,10 @@ int pg_irradiance_query(pg_context *ctx, uint64_t n, const float *p, const float
 {
 	PG_IRRADIANCE_BUILT(ctx, "pg_irradiance_query");
 	if (n && (!p || !E_out)) return fail(ctx, PG_ERR_INVALID, "pg_irradiance_query: NULL pointer");
-	if (n > 0xffffffffull * kIrrBlock) return fail(ctx, PG_ERR_INVALID, "pg_irradiance_query: too many lanes for one launch");
+	if (n > 0xffffffffull * kQueryBlock) return fail(ctx, PG_ERR_INVALID, "pg_irradiance_query: too many lanes for one launch");
 	if (n == 0) return PG_OK;
 	RrArgs rr = {};
-	hipLaunchKernelGGL(k_irradiance<false>, irr_grid(n), dim3(kIrrBlock), 0, (hipStream_t)stream, ctx->view(), ctx->rad.irr.tab.p, n, p,
+	hipLaunchKernelGGL(k_irradiance<false>, query_grid(n), dim3(kQueryBlock), 0, (hipStream_t)stream, ctx->view(), ctx->rad.irr.tab.p, n, p,
 	                   normal, active, E_out, rr);
 	PG_LAUNCHED(ctx);
 	return PG_OK;
@@ -396,25 +383,16 @@ int pg_irradiance_rr(pg_context *ctx, uint64_t n, const float *p, const float *n
                      uint32_t *count_out, float *scale_out, float *E_out, void *stream)
 {
 	PG_IRRADIANCE_BUILT(ctx, "pg_irradiance_rr");
-	if (!params) return fail(ctx, PG_ERR_INVALID, "pg_irradiance_rr: NULL params");
-	if (!(std::isfinite(params->window) && params->window >= 1.0f))
-		return fail(ctx, PG_ERR_INVALID, "pg_irradiance_rr: window must be finite and >= 1");
-	if (params->max_split < 1u || params->max_split > 65536u)
-		return fail(ctx, PG_ERR_INVALID, "pg_irradiance_rr: max_split must lie in 1 .. 65536");
+	RrArgs rr;
+	if (int rc = rr_window(ctx, "pg_irradiance_rr", params, rr)) return rc;
 	if (n && (!p || !weight || !reference || !rng_state || !rng_inc || !count_out || !scale_out))
 		return fail(ctx, PG_ERR_INVALID, "pg_irradiance_rr: NULL pointer");
-	if (n > 0xffffffffull * kIrrBlock) return fail(ctx, PG_ERR_INVALID, "pg_irradiance_rr: too many lanes for one launch");
+	if (n > 0xffffffffull * kQueryBlock) return fail(ctx, PG_ERR_INVALID, "pg_irradiance_rr: too many lanes for one launch");
 	if (n == 0) return PG_OK;
-	RrArgs rr;
 	rr.weight = weight; rr.reference = reference;
 	rr.rng_state = rng_state; rr.rng_inc = rng_inc;
 	rr.count_out = count_out; rr.scale_out = scale_out;
-	const float s = params->window; // (fp32, each operation rounded on its own: pg_radiance_rr's window)
-	rr.lo = 2.0f / (1.0f + s);
-	rr.hi = s * rr.lo;
-	rr.max_split = params->max_split;
-	rr.max_split_f = (float)params->max_split;
-	hipLaunchKernelGGL(k_irradiance<true>, irr_grid(n), dim3(kIrrBlock), 0, (hipStream_t)stream, ctx->view(), ctx->rad.irr.tab.p, n, p,
+	hipLaunchKernelGGL(k_irradiance<true>, query_grid(n), dim3(kQueryBlock), 0, (hipStream_t)stream, ctx->view(), ctx->rad.irr.tab.p, n, p,
 	                   normal, active, E_out, rr);
 	PG_LAUNCHED(ctx);
 	return PG_OK;

@@ -7,9 +7,6 @@
 
 namespace pg {
 
-constexpr int kBlock = 256;
-static_assert(kBlock == kStageThreads, "stage_kd_planes copies one plane per thread");
-
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
 {
 #pragma unroll
@@ -33,13 +30,13 @@ __device__ __forceinline__ void count_depths(DepthCounters *dc, unsigned kd_lv, 
 	}
 }
 
-__global__ __launch_bounds__(kBlock) void k_leaf_index(TreeView t, uint64_t n, const float *__restrict__ p,
+__global__ __launch_bounds__(kQueryBlock) void k_leaf_index(TreeView t, uint64_t n, const float *__restrict__ p,
                                                        const uint8_t *__restrict__ active,
                                                        uint32_t *__restrict__ node_out)
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
 	stage_kd_planes(s_planes, t);
-	const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+	const uint64_t i = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
 	if (i >= n) return;
 	const float x = p[i], y = p[n + i], z = p[2 * n + i];
 	const bool act = active ? active[i] != 0 : true;
@@ -48,7 +45,7 @@ __global__ __launch_bounds__(kBlock) void k_leaf_index(TreeView t, uint64_t n, c
 	node_out[i] = kd_descend_grid(t, s_planes, x, y, z, act && inside_root(t, x, y, z), leaf, lv);
 }
 
-__global__ __launch_bounds__(kBlock) void k_sample(TreeView t, uint64_t n, const float *__restrict__ p,
+__global__ __launch_bounds__(kQueryBlock) void k_sample(TreeView t, uint64_t n, const float *__restrict__ p,
                                                    uint64_t *__restrict__ rng_state,
                                                    const uint64_t *__restrict__ rng_inc,
                                                    const uint8_t *__restrict__ active,
@@ -57,7 +54,7 @@ __global__ __launch_bounds__(kBlock) void k_sample(TreeView t, uint64_t n, const
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
 	stage_kd_planes(s_planes, t);
-	const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+	const uint64_t i = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
 	unsigned kd_lv = 0, q_lv = 0, did = 0;
 	if (i < n) {
 		const bool act = active ? active[i] != 0 : true;
@@ -79,14 +76,14 @@ __global__ __launch_bounds__(kBlock) void k_sample(TreeView t, uint64_t n, const
 	count_depths(dc, kd_lv, did, q_lv, did);
 }
 
-__global__ __launch_bounds__(kBlock) void k_pdf(TreeView t, uint64_t n, const float *__restrict__ p,
+__global__ __launch_bounds__(kQueryBlock) void k_pdf(TreeView t, uint64_t n, const float *__restrict__ p,
                                                 const float *__restrict__ dir,
                                                 const uint8_t *__restrict__ active,
                                                 float *__restrict__ pdf_out, DepthCounters *dc)
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
 	stage_kd_planes(s_planes, t);
-	const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+	const uint64_t i = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
 	unsigned kd_lv = 0, q_lv = 0, did = 0;
 	if (i < n) {
 		const bool act = active ? active[i] != 0 : true;
@@ -115,7 +112,7 @@ __global__ __launch_bounds__(kBlock) void k_pdf(TreeView t, uint64_t n, const fl
 // lane_index/d_lane_count (optional): a compacted list of live ray slots produced by
 // k_compact_lanes.  Thread i then serves ray lane_index[i]; threads past *d_lane_count retire at
 // once, so a late bounce with few live rays costs few waves without a host round trip.
-__global__ __launch_bounds__(kBlock) void k_guide_bounce(TreeView t, uint64_t n, const float *__restrict__ p,
+__global__ __launch_bounds__(kQueryBlock) void k_guide_bounce(TreeView t, uint64_t n, const float *__restrict__ p,
                                                          const float *__restrict__ dir_nee,
                                                          const uint8_t *__restrict__ nee_active,
                                                          const uint8_t *__restrict__ select,
@@ -129,12 +126,12 @@ __global__ __launch_bounds__(kBlock) void k_guide_bounce(TreeView t, uint64_t n,
                                                          DepthCounters *dc)
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
-	const uint64_t tid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+	const uint64_t tid = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
 	// compacted list: [0, front) from the start of lane_index (sample lanes), the next `back`
 	// entries from its end, walking down (pdf-only lanes): waves are homogeneous in `select`
 	const uint64_t front = lane_index ? (uint64_t)d_lane_count[0] : n;
 	const uint64_t live = lane_index ? front + (uint64_t)d_lane_count[1] : n;
-	if ((uint64_t)blockIdx.x * kBlock >= live) return; // whole workgroup idle (uniform)
+	if ((uint64_t)blockIdx.x * kQueryBlock >= live) return; // whole workgroup idle (uniform)
 	stage_kd_planes(s_planes, t);
 	unsigned kd_lv = 0, kd_q = 0, q_lv = 0, q_q = 0;
 	if (tid < live && tid < n) {
@@ -193,7 +190,7 @@ __global__ __launch_bounds__(kBlock) void k_guide_bounce(TreeView t, uint64_t n,
 // workgroup.  A single counter word takes ~11 ns per atomic (MI355X_MICROARCH.md, "dequeue"), so
 // one atomic per wave would cost 45 us at 2^18 lanes; per 4096 lanes it is < 1 us.
 constexpr int kCompactItems = 16;
-constexpr int kCompactTile = kBlock * kCompactItems;
+constexpr int kCompactTile = kQueryBlock * kCompactItems;
 
 __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v)
 {
@@ -206,12 +203,12 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v)
 	return v;
 }
 
-__global__ __launch_bounds__(kBlock) void k_compact_lanes(uint64_t n, const uint8_t *__restrict__ select,
+__global__ __launch_bounds__(kQueryBlock) void k_compact_lanes(uint64_t n, const uint8_t *__restrict__ select,
                                                           const uint8_t *__restrict__ nee_active,
                                                           uint32_t *__restrict__ idx_out,
                                                           uint32_t *__restrict__ d_count /*[2]*/)
 {
-	__shared__ uint32_t s_wave[2][kBlock / 64];
+	__shared__ uint32_t s_wave[2][kQueryBlock / 64];
 	__shared__ uint32_t s_base[2];
 	const uint64_t base = (uint64_t)blockIdx.x * kCompactTile + (uint64_t)threadIdx.x * kCompactItems;
 	alignas(16) uint8_t sel[kCompactItems];
@@ -241,7 +238,7 @@ __global__ __launch_bounds__(kBlock) void k_compact_lanes(uint64_t n, const uint
 	__syncthreads();
 	uint32_t off_f = inf - nf, off_b = inb - nb, tot_f = 0, tot_b = 0;
 #pragma unroll
-	for (unsigned w = 0; w < kBlock / 64; ++w) {
+	for (unsigned w = 0; w < kQueryBlock / 64; ++w) {
 		if (w < wid) { off_f += s_wave[0][w]; off_b += s_wave[1][w]; }
 		tot_f += s_wave[0][w];
 		tot_b += s_wave[1][w];
@@ -260,10 +257,10 @@ __global__ __launch_bounds__(kBlock) void k_compact_lanes(uint64_t n, const uint
 	}
 }
 
-__global__ __launch_bounds__(kBlock) void k_rng_seed(uint64_t n, uint32_t seed, uint32_t lane0,
+__global__ __launch_bounds__(kQueryBlock) void k_rng_seed(uint64_t n, uint32_t seed, uint32_t lane0,
                                                      uint64_t *__restrict__ state, uint64_t *__restrict__ inc)
 {
-	const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+	const uint64_t i = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
 	if (i >= n) return;
 	const Pcg32 r = pcg32_seed(seed, lane0 + (uint32_t)i);
 	state[i] = r.state;
@@ -281,7 +278,7 @@ __global__ __launch_bounds__(kBlock) void k_rng_seed(uint64_t n, uint32_t seed, 
 // corner) and writes the three others to positions no level-l entry occupies.
 // Quadrants (quadtree.py:153-175; `quadrant` in pg_descent.hpp): child 0 = (x >= mid, y >= mid), 1 = (x <= mid, y >= mid),
 // 2 = (x <= mid, y <= mid), 3 = (x >= mid, y <= mid).
-__global__ __launch_bounds__(kBlock) void k_build_jump(TreeView t, QuadJump *__restrict__ out, int bits)
+__global__ __launch_bounds__(kQueryBlock) void k_build_jump(TreeView t, QuadJump *__restrict__ out, int bits)
 {
 	extern __shared__ u32x4_t s_tab[]; // 4^bits entries
 	const uint32_t tree = blockIdx.x;
@@ -303,7 +300,7 @@ __global__ __launch_bounds__(kBlock) void k_build_jump(TreeView t, QuadJump *__r
 		const uint32_t n_par = 1u << (2 * l);
 		const int shift = bits - l;            // a level-l cell spans 2^shift table cells per axis
 		const uint32_t half = 1u << (shift - 1);
-		for (uint32_t p = threadIdx.x; p < n_par; p += kBlock) {
+		for (uint32_t p = threadIdx.x; p < n_par; p += kQueryBlock) {
 			const uint32_t iy = p >> l, ix = p & ((1u << l) - 1u);
 			const uint32_t pos = ((iy << shift) << bits) | (ix << shift);
 			const u32x4_t e = s_tab[pos];
@@ -339,16 +336,16 @@ __global__ __launch_bounds__(kBlock) void k_build_jump(TreeView t, QuadJump *__r
 		__syncthreads();
 	}
 	u32x4_t *dst = reinterpret_cast<u32x4_t *>(out + ((size_t)tree << (2 * bits)));
-	for (uint32_t i = threadIdx.x; i < cells; i += kBlock) dst[i] = s_tab[i];
+	for (uint32_t i = threadIdx.x; i < cells; i += kQueryBlock) dst[i] = s_tab[i];
 }
 
 // One thread per cell of the KD jump grid: descend with the cell's interval for as long as every point
 // strictly inside the cell takes the same branch.  Two more threads write the ROOT entries behind the
 // cells (kd_descend_grid): the root as a searching lane that is in no cell starts from it, and the root
 // as a lane that does not search returns it.
-__global__ __launch_bounds__(kBlock) void k_build_kd_grid(TreeView t, KdGridEntry *__restrict__ out)
+__global__ __launch_bounds__(kQueryBlock) void k_build_kd_grid(TreeView t, KdGridEntry *__restrict__ out)
 {
-	const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
+	const uint32_t c = blockIdx.x * kQueryBlock + threadIdx.x;
 	const uint32_t n_cells = 1u << (3 * t.grid_bits);
 	if (c >= n_cells + kKdGridRootEntries) return;
 	uint32_t node = 0, levels = 0;
@@ -381,11 +378,9 @@ __global__ __launch_bounds__(kBlock) void k_build_kd_grid(TreeView t, KdGridEntr
 	out[c] = e;
 }
 
-static inline dim3 grid_for(uint64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
-
 void launch_build_kd_grid(const TreeView &t, KdGridEntry *out, hipStream_t s)
 {
-	hipLaunchKernelGGL(k_build_kd_grid, grid_for((1ull << (3 * t.grid_bits)) + kKdGridRootEntries), dim3(kBlock), 0, s, t, out);
+	hipLaunchKernelGGL(k_build_kd_grid, query_grid((1ull << (3 * t.grid_bits)) + kKdGridRootEntries), dim3(kQueryBlock), 0, s, t, out);
 }
 
 // false: the device refuses the dynamic LDS a table of this resolution is built in (nothing was launched; the caller
@@ -400,7 +395,7 @@ bool launch_build_jump(const TreeView &t, QuadJump *out, int bits, hipStream_t s
 		(void)hipGetLastError();
 		return false;
 	}
-	hipLaunchKernelGGL(k_build_jump, dim3(t.n_trees), dim3(kBlock), lds, s, t, out, bits);
+	hipLaunchKernelGGL(k_build_jump, dim3(t.n_trees), dim3(kQueryBlock), lds, s, t, out, bits);
 	return true;
 }
 
@@ -408,7 +403,7 @@ void launch_leaf_index(const TreeView &t, uint64_t n, const float *p, const uint
                        uint32_t *node_out, hipStream_t s)
 {
 	if (n == 0) return;
-	hipLaunchKernelGGL(k_leaf_index, grid_for(n), dim3(kBlock), 0, s, t, n, p, active, node_out);
+	hipLaunchKernelGGL(k_leaf_index, query_grid(n), dim3(kQueryBlock), 0, s, t, n, p, active, node_out);
 }
 
 void launch_sample(const TreeView &t, uint64_t n, const float *p, uint64_t *rng_state,
@@ -416,7 +411,7 @@ void launch_sample(const TreeView &t, uint64_t n, const float *p, uint64_t *rng_
                    DepthCounters *dc, hipStream_t s)
 {
 	if (n == 0) return;
-	hipLaunchKernelGGL(k_sample, grid_for(n), dim3(kBlock), 0, s, t, n, p, rng_state, rng_inc, active,
+	hipLaunchKernelGGL(k_sample, query_grid(n), dim3(kQueryBlock), 0, s, t, n, p, rng_state, rng_inc, active,
 	                   dir_out, pdf_out, dc);
 }
 
@@ -424,7 +419,7 @@ void launch_pdf(const TreeView &t, uint64_t n, const float *p, const float *dir,
                 float *pdf_out, DepthCounters *dc, hipStream_t s)
 {
 	if (n == 0) return;
-	hipLaunchKernelGGL(k_pdf, grid_for(n), dim3(kBlock), 0, s, t, n, p, dir, active, pdf_out, dc);
+	hipLaunchKernelGGL(k_pdf, query_grid(n), dim3(kQueryBlock), 0, s, t, n, p, dir, active, pdf_out, dc);
 }
 
 void launch_guide_bounce(const TreeView &t, uint64_t n, const float *p, const float *dir_nee,
@@ -434,7 +429,7 @@ void launch_guide_bounce(const TreeView &t, uint64_t n, const float *p, const fl
                          DepthCounters *dc, hipStream_t s)
 {
 	if (n == 0) return;
-	hipLaunchKernelGGL(k_guide_bounce, grid_for(n), dim3(kBlock), 0, s, t, n, p, dir_nee, nee_active,
+	hipLaunchKernelGGL(k_guide_bounce, query_grid(n), dim3(kQueryBlock), 0, s, t, n, p, dir_nee, nee_active,
 	                   select, dir_io, rng_state, rng_inc, pdf_nee_out, pdf_out, lane_index, d_lane_count, dc);
 }
 
@@ -443,7 +438,7 @@ void launch_compact_lanes(uint64_t n, const uint8_t *select, const uint8_t *nee_
 {
 	(void)hipMemsetAsync(d_count, 0, 2 * sizeof(uint32_t), s);
 	if (n == 0) return;
-	hipLaunchKernelGGL(k_compact_lanes, dim3((unsigned)((n + kCompactTile - 1) / kCompactTile)), dim3(kBlock), 0, s, n,
+	hipLaunchKernelGGL(k_compact_lanes, dim3((unsigned)((n + kCompactTile - 1) / kCompactTile)), dim3(kQueryBlock), 0, s, n,
 	                   select, nee_active, idx_out, d_count);
 }
 
@@ -451,7 +446,7 @@ void launch_rng_seed(uint64_t n, uint32_t seed, uint32_t lane0, uint64_t *state,
                      hipStream_t s)
 {
 	if (n == 0) return;
-	hipLaunchKernelGGL(k_rng_seed, grid_for(n), dim3(kBlock), 0, s, n, seed, lane0, state, inc);
+	hipLaunchKernelGGL(k_rng_seed, query_grid(n), dim3(kQueryBlock), 0, s, n, seed, lane0, state, inc);
 }
 
 } // namespace pg

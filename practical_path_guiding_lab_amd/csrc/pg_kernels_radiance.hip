@@ -13,9 +13,6 @@
 
 namespace pg {
 
-constexpr int kRadBlock = 256;
-static_assert(kRadBlock == kStageThreads, "stage_kd_planes copies one plane per thread");
-
 // radiance_leaf (the leaf a record with a canonical direction adds to: its energy and depth): pg_guide_dev.hpp --
 // pg_kernels_bounce.hip inlines it too
 
@@ -24,14 +21,14 @@ static_assert(kRadBlock == kStageThreads, "stage_kd_planes copies one plane per 
 
 // dir == nullptr (uniform; never with kDecide): only the mean, no quadtree is walked.
 template <bool kDecide>
-__global__ __launch_bounds__(kRadBlock) void k_radiance(TreeView t, const unsigned long long *__restrict__ wtab, uint64_t n,
+__global__ __launch_bounds__(kQueryBlock) void k_radiance(TreeView t, const unsigned long long *__restrict__ wtab, uint64_t n,
                                                         const float *__restrict__ p, const float *__restrict__ dir,
                                                         const uint8_t *__restrict__ active, float *__restrict__ L_dir_out,
                                                         float *__restrict__ L_mean_out, RrArgs rr)
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
 	stage_kd_planes(s_planes, t);
-	const uint64_t i = (uint64_t)blockIdx.x * kRadBlock + threadIdx.x;
+	const uint64_t i = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
 	if (i >= n) return;
 	const bool act = active ? active[i] != 0 : true;
 	const bool walk = dir != nullptr;
@@ -84,40 +81,52 @@ __global__ __launch_bounds__(kRadBlock) void k_radiance(TreeView t, const unsign
 
 // the table of a refined forest (pg_refine.hip): new tree t is a copy or refinement of old tree tree_src[t], whose energies
 // were resolved from accumulators that had received tree_count[tree_src[t]] in-box records (k_resolve_roots)
-__global__ __launch_bounds__(kRadBlock) void k_radiance_carry(const unsigned long long *__restrict__ tree_count, uint32_t n_old,
+__global__ __launch_bounds__(kQueryBlock) void k_radiance_carry(const unsigned long long *__restrict__ tree_count, uint32_t n_old,
                                                               const uint32_t *__restrict__ tree_src,
                                                               unsigned long long *__restrict__ w_new, uint32_t n_new)
 {
-	const uint32_t t = blockIdx.x * kRadBlock + threadIdx.x;
+	const uint32_t t = blockIdx.x * kQueryBlock + threadIdx.x;
 	if (t >= n_new) return;
 	uint32_t src = tree_src[t];
 	if (src >= n_old) src = 0; // (never: tree_src names pre-refine trees)
 	w_new[t] = tree_count[src];
 }
 
-static inline dim3 rad_grid(uint64_t n) { return dim3((unsigned)((n + kRadBlock - 1) / kRadBlock)); }
-
 void launch_radiance_carry(const unsigned long long *tree_count, uint32_t n_old, const uint32_t *tree_src, unsigned long long *w_new,
                            uint32_t n_new, hipStream_t s)
 {
 	if (n_new == 0) return;
-	hipLaunchKernelGGL(k_radiance_carry, rad_grid(n_new), dim3(kRadBlock), 0, s, tree_count, n_old, tree_src, w_new, n_new);
+	hipLaunchKernelGGL(k_radiance_carry, query_grid(n_new), dim3(kQueryBlock), 0, s, tree_count, n_old, tree_src, w_new, n_new);
+}
+
+int radiance_source(pg_context *ctx, const char *who)
+{
+	const std::string w = std::string(who) + ": ";
+	if (!ctx->rad.on) return fail(ctx, PG_ERR_INVALID, w + "call pg_radiance_enable first");
+	if (!ctx->rad.valid)
+		return fail(ctx, PG_ERR_INVALID, w + "the weights of this tree are unknown (no refine since pg_radiance_enable, no pg_radiance_import)");
+	if (ctx->rad.of_target)
+		return fail(ctx, PG_ERR_INVALID, w + "sdTree_prev was refined from a second-moment target (pg_target_apply): it holds roots of second moments, not radiance");
+	return PG_OK;
+}
+
+int rr_window(pg_context *ctx, const char *who, const pg_rr_params *params, RrArgs &rr)
+{
+	const std::string w = std::string(who) + ": ";
+	if (!params) return fail(ctx, PG_ERR_INVALID, w + "NULL params");
+	if (!(std::isfinite(params->window) && params->window >= 1.0f)) return fail(ctx, PG_ERR_INVALID, w + "window must be finite and >= 1");
+	if (params->max_split < 1u || params->max_split > 65536u) return fail(ctx, PG_ERR_INVALID, w + "max_split must lie in 1 .. 65536");
+	const float s = params->window; // (fp32, each operation rounded on its own: the build's -ffp-contract=off holds for the host too)
+	rr.lo = 2.0f / (1.0f + s);
+	rr.hi = s * rr.lo;
+	rr.max_split = params->max_split;
+	rr.max_split_f = (float)params->max_split;
+	return PG_OK;
 }
 
 } // namespace pg
 
 using namespace pg;
-
-// PG_READY, the feature is on, and its table describes a tree of radiance
-#define PG_RADIANCE_USABLE(ctx, who)                                                                                          \
-	do {                                                                                                                      \
-		PG_READY(ctx);                                                                                                        \
-		if (!(ctx)->rad.on) return fail((ctx), PG_ERR_INVALID, who ": call pg_radiance_enable first");                       \
-		if (!(ctx)->rad.valid)                                                                                                \
-			return fail((ctx), PG_ERR_INVALID, who ": the weights of this tree are unknown (no refine since pg_radiance_enable, no pg_radiance_import)"); \
-		if ((ctx)->rad.of_target)                                                                                             \
-			return fail((ctx), PG_ERR_INVALID, who ": sdTree_prev was refined from a second-moment target (pg_target_apply): it holds roots of second moments, not radiance"); \
-	} while (0)
 
 extern "C" {
 
@@ -181,14 +190,15 @@ int pg_radiance_import(pg_context *ctx, uint64_t n_trees, const uint64_t *h_weig
 int pg_radiance_query(pg_context *ctx, uint64_t n, const float *p, const float *dir, const uint8_t *active, float *L_dir_out,
                       float *L_mean_out, void *stream)
 {
-	PG_RADIANCE_USABLE(ctx, "pg_radiance_query");
+	PG_READY(ctx);
+	if (int rc = radiance_source(ctx, "pg_radiance_query")) return rc;
 	if ((dir == nullptr) != (L_dir_out == nullptr))
 		return fail(ctx, PG_ERR_INVALID, "pg_radiance_query: dir and L_dir_out are given together or both NULL");
 	if (n && (!p || (!dir && !L_mean_out))) return fail(ctx, PG_ERR_INVALID, "pg_radiance_query: NULL pointer");
-	if (n > 0xffffffffull * kRadBlock) return fail(ctx, PG_ERR_INVALID, "pg_radiance_query: too many lanes for one launch");
+	if (n > 0xffffffffull * kQueryBlock) return fail(ctx, PG_ERR_INVALID, "pg_radiance_query: too many lanes for one launch");
 	if (n == 0) return PG_OK;
 	RrArgs rr = {};
-	hipLaunchKernelGGL(k_radiance<false>, rad_grid(n), dim3(kRadBlock), 0, (hipStream_t)stream, ctx->view(), ctx->rad.tab.p, n, p, dir,
+	hipLaunchKernelGGL(k_radiance<false>, query_grid(n), dim3(kQueryBlock), 0, (hipStream_t)stream, ctx->view(), ctx->rad.tab.p, n, p, dir,
 	                   active, L_dir_out, L_mean_out, rr);
 	PG_LAUNCHED(ctx);
 	return PG_OK;
@@ -198,26 +208,18 @@ int pg_radiance_rr(pg_context *ctx, uint64_t n, const float *p, const float *dir
                    const pg_rr_params *params, uint64_t *rng_state, const uint64_t *rng_inc, const uint8_t *active,
                    uint32_t *count_out, float *scale_out, float *L_dir_out, void *stream)
 {
-	PG_RADIANCE_USABLE(ctx, "pg_radiance_rr");
-	if (!params) return fail(ctx, PG_ERR_INVALID, "pg_radiance_rr: NULL params");
-	if (!(std::isfinite(params->window) && params->window >= 1.0f))
-		return fail(ctx, PG_ERR_INVALID, "pg_radiance_rr: window must be finite and >= 1");
-	if (params->max_split < 1u || params->max_split > 65536u)
-		return fail(ctx, PG_ERR_INVALID, "pg_radiance_rr: max_split must lie in 1 .. 65536");
+	PG_READY(ctx);
+	if (int rc = radiance_source(ctx, "pg_radiance_rr")) return rc;
+	RrArgs rr;
+	if (int rc = rr_window(ctx, "pg_radiance_rr", params, rr)) return rc;
 	if (n && (!p || !dir || !weight || !reference || !rng_state || !rng_inc || !count_out || !scale_out))
 		return fail(ctx, PG_ERR_INVALID, "pg_radiance_rr: NULL pointer");
-	if (n > 0xffffffffull * kRadBlock) return fail(ctx, PG_ERR_INVALID, "pg_radiance_rr: too many lanes for one launch");
+	if (n > 0xffffffffull * kQueryBlock) return fail(ctx, PG_ERR_INVALID, "pg_radiance_rr: too many lanes for one launch");
 	if (n == 0) return PG_OK;
-	RrArgs rr;
 	rr.weight = weight; rr.reference = reference;
 	rr.rng_state = rng_state; rr.rng_inc = rng_inc;
 	rr.count_out = count_out; rr.scale_out = scale_out;
-	const float s = params->window; // (fp32, each operation rounded on its own: the build's -ffp-contract=off holds for the host too)
-	rr.lo = 2.0f / (1.0f + s);
-	rr.hi = s * rr.lo;
-	rr.max_split = params->max_split;
-	rr.max_split_f = (float)params->max_split;
-	hipLaunchKernelGGL(k_radiance<true>, rad_grid(n), dim3(kRadBlock), 0, (hipStream_t)stream, ctx->view(), ctx->rad.tab.p, n, p, dir,
+	hipLaunchKernelGGL(k_radiance<true>, query_grid(n), dim3(kQueryBlock), 0, (hipStream_t)stream, ctx->view(), ctx->rad.tab.p, n, p, dir,
 	                   active, L_dir_out, (float *)nullptr, rr);
 	PG_LAUNCHED(ctx);
 	return PG_OK;

@@ -13,9 +13,6 @@
 
 namespace pg {
 
-constexpr int kWBlock = 256;
-static_assert(kWBlock == kStageThreads, "stage_kd_planes copies one plane per thread");
-
 // clamp_unit, warp_node and quad_warp (the WARP of pgsd_warp.h): pg_guide_dev.hpp -- pg_kernels_bounce.hip inlines them too
 
 // INVERSE of pgsd_warp.h for the canonical position (cx, cy).  Every level's probabilities are needed, so the jump tables are
@@ -64,14 +61,14 @@ __device__ __forceinline__ void quad_unwarp(const QuadRec *rec, TreeHead head, f
 	pdf_out = dead ? 0.0f : (r == kNoRecord ? pdf * kInvFourPiF : pdf); // (a walk that reached no leaf: pdfQuadTree's value there)
 }
 
-__global__ __launch_bounds__(kWBlock) void k_sample_warp(TreeView t, uint64_t n, const float *__restrict__ p,
+__global__ __launch_bounds__(kQueryBlock) void k_sample_warp(TreeView t, uint64_t n, const float *__restrict__ p,
                                                          const float *__restrict__ u,
                                                          const uint8_t *__restrict__ active,
                                                          float *__restrict__ dir_out, float *__restrict__ pdf_out)
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
 	stage_kd_planes(s_planes, t);
-	const uint64_t i = (uint64_t)blockIdx.x * kWBlock + threadIdx.x;
+	const uint64_t i = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
 	if (i >= n) return;
 	const bool act = active ? active[i] != 0 : true;
 	float dx = 0.0f, dy = 0.0f, dz = -1.0f, pdf = 1.0f; // inactive lanes: pg_sample's values
@@ -89,14 +86,14 @@ __global__ __launch_bounds__(kWBlock) void k_sample_warp(TreeView t, uint64_t n,
 	pdf_out[i] = pdf;
 }
 
-__global__ __launch_bounds__(kWBlock) void k_invert_warp(TreeView t, uint64_t n, const float *__restrict__ p,
+__global__ __launch_bounds__(kQueryBlock) void k_invert_warp(TreeView t, uint64_t n, const float *__restrict__ p,
                                                          const float *__restrict__ dir,
                                                          const uint8_t *__restrict__ active,
                                                          float *__restrict__ u_out, float *__restrict__ pdf_out)
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
 	stage_kd_planes(s_planes, t);
-	const uint64_t i = (uint64_t)blockIdx.x * kWBlock + threadIdx.x;
+	const uint64_t i = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
 	if (i >= n) return;
 	const bool act = active ? active[i] != 0 : true;
 	float ux = 0.0f, uy = 0.0f, pdf = 1.0f;
@@ -116,7 +113,7 @@ __global__ __launch_bounds__(kWBlock) void k_invert_warp(TreeView t, uint64_t n,
 
 // k_guide_bounce (pg_kernels_query.hip) with the warp where it samples: the same lanes, the same list of pg_compact_lanes,
 // the same two pdf walks; no depth counters.
-__global__ __launch_bounds__(kWBlock) void k_guide_bounce_warp(TreeView t, uint64_t n, const float *__restrict__ p,
+__global__ __launch_bounds__(kQueryBlock) void k_guide_bounce_warp(TreeView t, uint64_t n, const float *__restrict__ p,
                                                                const float *__restrict__ dir_nee,
                                                                const uint8_t *__restrict__ nee_active,
                                                                const uint8_t *__restrict__ select,
@@ -127,10 +124,10 @@ __global__ __launch_bounds__(kWBlock) void k_guide_bounce_warp(TreeView t, uint6
                                                                const uint32_t *__restrict__ d_lane_count)
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
-	const uint64_t tid = (uint64_t)blockIdx.x * kWBlock + threadIdx.x;
+	const uint64_t tid = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
 	const uint64_t front = lane_index ? (uint64_t)d_lane_count[0] : n;
 	const uint64_t live = lane_index ? front + (uint64_t)d_lane_count[1] : n;
-	if ((uint64_t)blockIdx.x * kWBlock >= live) return; // whole workgroup idle (uniform)
+	if ((uint64_t)blockIdx.x * kQueryBlock >= live) return; // whole workgroup idle (uniform)
 	stage_kd_planes(s_planes, t);
 	if (!(tid < live && tid < n)) return;
 	const uint64_t i = lane_index ? (uint64_t)lane_index[tid < front ? tid : n - 1 - (tid - front)] : tid;
@@ -167,8 +164,6 @@ __global__ __launch_bounds__(kWBlock) void k_guide_bounce_warp(TreeView t, uint6
 	pdf_out[i] = pdf;
 }
 
-static inline dim3 warp_grid(uint64_t n) { return dim3((unsigned)((n + kWBlock - 1) / kWBlock)); }
-
 } // namespace pg
 
 using namespace pg;
@@ -180,9 +175,9 @@ int pg_sample_warp(pg_context *ctx, uint64_t n, const float *p, const float *u, 
 {
 	PG_READY(ctx);
 	if (n && (!p || !u || !dir_out || !pdf_out)) return fail(ctx, PG_ERR_INVALID, "pg_sample_warp: NULL pointer");
-	if (n > 0xffffffffull * kWBlock) return fail(ctx, PG_ERR_INVALID, "pg_sample_warp: too many lanes for one launch");
+	if (n > 0xffffffffull * kQueryBlock) return fail(ctx, PG_ERR_INVALID, "pg_sample_warp: too many lanes for one launch");
 	if (n == 0) return PG_OK;
-	hipLaunchKernelGGL(k_sample_warp, warp_grid(n), dim3(kWBlock), 0, (hipStream_t)stream, ctx->view(), n, p, u, active, dir_out,
+	hipLaunchKernelGGL(k_sample_warp, query_grid(n), dim3(kQueryBlock), 0, (hipStream_t)stream, ctx->view(), n, p, u, active, dir_out,
 	                   pdf_out);
 	PG_LAUNCHED(ctx);
 	return PG_OK;
@@ -193,9 +188,9 @@ int pg_invert_warp(pg_context *ctx, uint64_t n, const float *p, const float *dir
 {
 	PG_READY(ctx);
 	if (n && (!p || !dir || !u_out)) return fail(ctx, PG_ERR_INVALID, "pg_invert_warp: NULL pointer");
-	if (n > 0xffffffffull * kWBlock) return fail(ctx, PG_ERR_INVALID, "pg_invert_warp: too many lanes for one launch");
+	if (n > 0xffffffffull * kQueryBlock) return fail(ctx, PG_ERR_INVALID, "pg_invert_warp: too many lanes for one launch");
 	if (n == 0) return PG_OK;
-	hipLaunchKernelGGL(k_invert_warp, warp_grid(n), dim3(kWBlock), 0, (hipStream_t)stream, ctx->view(), n, p, dir, active, u_out,
+	hipLaunchKernelGGL(k_invert_warp, query_grid(n), dim3(kQueryBlock), 0, (hipStream_t)stream, ctx->view(), n, p, dir, active, u_out,
 	                   pdf_out);
 	PG_LAUNCHED(ctx);
 	return PG_OK;
@@ -212,7 +207,7 @@ int pg_guide_bounce_warp(pg_context *ctx, uint64_t n, const float *p, const floa
 		return fail(ctx, PG_ERR_INVALID, "pg_guide_bounce_warp: lane_index and d_lane_count go together");
 	if (n > 0xffffffffull) return fail(ctx, PG_ERR_INVALID, "pg_guide_bounce_warp: more than 2^32 lanes");
 	if (n == 0) return PG_OK;
-	hipLaunchKernelGGL(k_guide_bounce_warp, warp_grid(n), dim3(kWBlock), 0, (hipStream_t)stream, ctx->view(), n, p, dir_nee,
+	hipLaunchKernelGGL(k_guide_bounce_warp, query_grid(n), dim3(kQueryBlock), 0, (hipStream_t)stream, ctx->view(), n, p, dir_nee,
 	                   nee_active, select, dir_io, u, pdf_nee_out, pdf_out, lane_index, d_lane_count);
 	PG_LAUNCHED(ctx);
 	return PG_OK;

@@ -40,6 +40,24 @@ def _mask(active: Optional[torch.Tensor], n: int):
     return active, active.data_ptr()
 
 
+def _count_ptr(count: Optional[torch.Tensor]):
+    """The pointer of a device-side record count (addDataPropagate's `count`), None without one."""
+    if count is None:
+        return None
+    if count.dtype != torch.int32 or not count.is_cuda:
+        raise ValueError("count must be a CUDA int32 tensor")
+    return count.data_ptr()
+
+
+def _lane_ptrs(lane_index: torch.Tensor, lane_count: torch.Tensor, n: int, message: str):
+    """The pointers of compactLanes' list for n lanes; `message`: what the caller says about a list that is none."""
+    if lane_index.dtype != torch.int32 or lane_count.dtype != torch.int32 or lane_index.numel() < n or lane_count.numel() < 2:
+        raise ValueError(message)
+    return lane_index.data_ptr(), lane_count.data_ptr()
+
+
+_GUIDE_LANES = "lane_index must be int32[n], lane_count int32[2] (from compactLanes)"
+
 # Debug switch (the parity tests of the stand-alone entry points set it): synchronise the device behind every library call, so
 # that a GPU fault is reported under the call that launched the faulting kernel and not under whatever synchronised next
 # (round 2's memory-aperture abort surfaced in exportAccumulators, three launches later: profiles/r03/kd_descend_isa/).
@@ -51,8 +69,8 @@ class PCG32Sampler:
 
     def __init__(self, tree: "SDTree", n: int, seed: int = 0, lane0: int = 0):
         self.n = n
-        self.state = torch.empty(n, dtype=torch.int64, device=tree.device)
-        self.inc = torch.empty(n, dtype=torch.int64, device=tree.device)
+        self.state = tree._new(n, dtype=torch.int64)
+        self.inc = tree._new(n, dtype=torch.int64)
         tree._seed(self, seed, lane0)
 
 
@@ -79,6 +97,10 @@ class SDTree:
                 self._h = None
         except Exception:
             pass
+
+    def _new(self, *shape, dtype=torch.float32) -> torch.Tensor:
+        """A fresh output tensor on this tree's device."""
+        return torch.empty(shape, dtype=dtype, device=self.device)
 
     def _ck(self, rc):
         N.check(self._h, rc)
@@ -127,7 +149,7 @@ class SDTree:
         n = position.shape[1]
         _f32(position, (3, n))
         m, mp = _mask(active, n)
-        out = torch.empty(n, dtype=torch.int32, device=self.device)
+        out = self._new(n, dtype=torch.int32)
         self._ck(self._lib.pg_get_leaf_node_index(self._h, n, position.data_ptr(), mp, out.data_ptr(), _stream_ptr()))
         return out
 
@@ -136,8 +158,8 @@ class SDTree:
         n = position.shape[1]
         _f32(position, (3, n))
         m, mp = _mask(active, n)
-        d = torch.empty((3, n), dtype=torch.float32, device=self.device)
-        pdf = torch.empty(n, dtype=torch.float32, device=self.device)
+        d = self._new(3, n)
+        pdf = self._new(n)
         self._ck(self._lib.pg_sample(self._h, n, position.data_ptr(), sampler.state.data_ptr(), sampler.inc.data_ptr(),
                                      mp, d.data_ptr(), pdf.data_ptr(), _stream_ptr()))
         return d, pdf
@@ -147,7 +169,7 @@ class SDTree:
         _f32(position, (3, n))
         _f32(direction, (3, n))
         m, mp = _mask(active, n)
-        pdf = torch.empty(n, dtype=torch.float32, device=self.device)
+        pdf = self._new(n)
         self._ck(self._lib.pg_pdf(self._h, n, position.data_ptr(), direction.data_ptr(), mp, pdf.data_ptr(), _stream_ptr()))
         return pdf
 
@@ -169,17 +191,12 @@ class SDTree:
         na, nap = _mask(nee_active, n)
         sl, slp = _mask(select, n)
         if pdf_nee_out is None:
-            pdf_nee_out = torch.empty(n, dtype=torch.float32, device=self.device)
+            pdf_nee_out = self._new(n)
         if pdf_out is None:
-            pdf_out = torch.empty(n, dtype=torch.float32, device=self.device)
-        lip = lcp = None
+            pdf_out = self._new(n)
         if (lane_index is None) != (lane_count is None):
             raise ValueError("lane_index and lane_count go together")
-        if lane_index is not None:
-            if (lane_index.dtype != torch.int32 or lane_count.dtype != torch.int32 or lane_index.numel() < n
-                    or lane_count.numel() < 2):
-                raise ValueError("lane_index must be int32[n], lane_count int32[2] (from compactLanes)")
-            lip, lcp = lane_index.data_ptr(), lane_count.data_ptr()
+        lip, lcp = (None, None) if lane_index is None else _lane_ptrs(lane_index, lane_count, n, _GUIDE_LANES)
         keep = (position, dir_nee, na, sl, dir_io, sampler, pdf_nee_out, pdf_out, lane_index, lane_count)
         self._last_bounce_out = (pdf_nee_out, pdf_out)
         fn, h = self._lib.pg_guide_bounce, self._h
@@ -200,8 +217,8 @@ class SDTree:
         _f32(position, (3, n))
         _f32(u, (2, n))
         m, mp = _mask(active, n)
-        d = torch.empty((3, n), dtype=torch.float32, device=self.device)
-        pdf = torch.empty(n, dtype=torch.float32, device=self.device)
+        d = self._new(3, n)
+        pdf = self._new(n)
         self._ck(self._lib.pg_sample_warp(self._h, n, position.data_ptr(), u.data_ptr(), mp, d.data_ptr(), pdf.data_ptr(),
                                           _stream_ptr()))
         return d, pdf
@@ -214,8 +231,8 @@ class SDTree:
         _f32(position, (3, n))
         _f32(direction, (3, n))
         m, mp = _mask(active, n)
-        u = torch.empty((2, n), dtype=torch.float32, device=self.device)
-        pdf = torch.empty(n, dtype=torch.float32, device=self.device)
+        u = self._new(2, n)
+        pdf = self._new(n)
         self._ck(self._lib.pg_invert_warp(self._h, n, position.data_ptr(), direction.data_ptr(), mp, u.data_ptr(), pdf.data_ptr(),
                                           _stream_ptr()))
         return u, pdf
@@ -229,17 +246,12 @@ class SDTree:
         na, nap = _mask(nee_active, n)
         sl, slp = _mask(select, n)
         if pdf_nee_out is None:
-            pdf_nee_out = torch.empty(n, dtype=torch.float32, device=self.device)
+            pdf_nee_out = self._new(n)
         if pdf_out is None:
-            pdf_out = torch.empty(n, dtype=torch.float32, device=self.device)
-        lip = lcp = None
+            pdf_out = self._new(n)
         if (lane_index is None) != (lane_count is None):
             raise ValueError("lane_index and lane_count go together")
-        if lane_index is not None:
-            if (lane_index.dtype != torch.int32 or lane_count.dtype != torch.int32 or lane_index.numel() < n
-                    or lane_count.numel() < 2):
-                raise ValueError("lane_index must be int32[n], lane_count int32[2] (from compactLanes)")
-            lip, lcp = lane_index.data_ptr(), lane_count.data_ptr()
+        lip, lcp = (None, None) if lane_index is None else _lane_ptrs(lane_index, lane_count, n, _GUIDE_LANES)
         self._ck(self._lib.pg_guide_bounce_warp(self._h, n, position.data_ptr(), dir_nee.data_ptr(), nap, slp, dir_io.data_ptr(),
                                                 u.data_ptr(), pdf_nee_out.data_ptr(), pdf_out.data_ptr(), lip, lcp, _stream_ptr()))
         return pdf_nee_out, pdf_out
@@ -268,7 +280,7 @@ class SDTree:
         n = position.shape[1]
         _f32(position, (3, n))
         m, mp = _mask(active, n)
-        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        out = self._new(n)
         self._ck(self._lib.pg_fraction_query(self._h, n, position.data_ptr(), mp, out.data_ptr(), _stream_ptr()))
         return out
 
@@ -281,12 +293,7 @@ class SDTree:
         for k in ("bsdf_pdf", "guide_pdf", "product", "wo_pdf"):
             setattr(r, k, _f32(rec[k], (m,)).data_ptr())
         delta, r.is_delta = _mask(rec.get("is_delta"), m)
-        cp = None
-        if count is not None:
-            if count.dtype != torch.int32 or not count.is_cuda:
-                raise ValueError("count must be a CUDA int32 tensor")
-            cp = count.data_ptr()
-        self._ck(self._lib.pg_fraction_record(self._h, m, C.byref(r), cp, _stream_ptr()))
+        self._ck(self._lib.pg_fraction_record(self._h, m, C.byref(r), _count_ptr(count), _stream_ptr()))
 
     def fractionStep(self):
         """One Adam step for every leaf that received records since the last one (pg_fraction_step)."""
@@ -330,7 +337,7 @@ class SDTree:
         s, sp = _mask(select, n)
         ne, nep = _mask(nee_active, n)
         if idx_out is None:
-            idx_out = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+            idx_out = self._new(max(n, 1), dtype=torch.int32)
         if count_out is None:
             count_out = torch.zeros(2, dtype=torch.int32, device=self.device)
         if count_out.numel() < 2 or count_out.dtype != torch.int32:
@@ -356,12 +363,7 @@ class SDTree:
         if self.store_nee:
             r.direction_nee = _f32(rec["direction_nee"], (2, m)).data_ptr()
             r.radiance_nee_lum = _f32(rec["radiance_nee_lum"], (m,)).data_ptr()
-        cp = None
-        if count is not None:
-            if count.dtype != torch.int32 or not count.is_cuda:
-                raise ValueError("count must be a CUDA int32 tensor")
-            cp = count.data_ptr()
-        self._ck(self._lib.pg_splat(self._h, m, C.byref(r), cp, _stream_ptr()))
+        self._ck(self._lib.pg_splat(self._h, m, C.byref(r), _count_ptr(count), _stream_ptr()))
 
     # ---- the variance-aware guiding target (include/pgsd_target.h; not in the reference) ---------------------------------
     _TARGET = {"second_moment": N.PG_TARGET_SECOND_MOMENT}
@@ -429,11 +431,11 @@ class SDTree:
         n = position.shape[1]
         _f32(position, (3, n))
         m, mp = _mask(active, n)
-        L_mean = torch.empty(n, dtype=torch.float32, device=self.device)
+        L_mean = self._new(n)
         L_dir, dp, lp = None, None, None
         if direction is not None:
             dp = _f32(direction, (3, n)).data_ptr()
-            L_dir = torch.empty(n, dtype=torch.float32, device=self.device)
+            L_dir = self._new(n)
             lp = L_dir.data_ptr()
         self._ck(self._lib.pg_radiance_query(self._h, n, position.data_ptr(), dp, mp, lp, L_mean.data_ptr(), _stream_ptr()))
         return L_dir, L_mean
@@ -445,22 +447,25 @@ class SDTree:
         splitting.  weight: the paths' throughput (a luminance) behind the bounce; reference: the estimate of their pixels'
         values.  A path goes on `count` times (0: it ends) with its throughput multiplied by `scale`; E[count * scale] = 1.
         One draw of `sampler` per active lane.  max_split=1: roulette only."""
+        return self._roulette(self._lib.pg_radiance_rr, position, direction, False, weight, reference, sampler, window, max_split,
+                              active)
+
+    def _roulette(self, fn, position, around, around_optional: bool, weight, reference, sampler, window, max_split, active):
+        """radianceRoulette / irradianceRoulette: `fn` decides on its estimate around the direction or the normal `around`."""
         n = position.shape[1]
         _f32(position, (3, n))
-        _f32(direction, (3, n))
+        ap = None if around is None and around_optional else _f32(around, (3, n)).data_ptr()
         _f32(weight, (n,))
         _f32(reference, (n,))
         if sampler.n != n:
             raise ValueError("the sampler must have one stream per lane")
         m, mp = _mask(active, n)
-        count = torch.empty(n, dtype=torch.int32, device=self.device)
-        scale = torch.empty(n, dtype=torch.float32, device=self.device)
-        L_dir = torch.empty(n, dtype=torch.float32, device=self.device)
+        count, scale, estimate = self._new(n, dtype=torch.int32), self._new(n), self._new(n)
         prm = N.pg_rr_params(float(window), int(max_split))
-        self._ck(self._lib.pg_radiance_rr(self._h, n, position.data_ptr(), direction.data_ptr(), weight.data_ptr(),
-                                          reference.data_ptr(), C.byref(prm), sampler.state.data_ptr(), sampler.inc.data_ptr(),
-                                          mp, count.data_ptr(), scale.data_ptr(), L_dir.data_ptr(), _stream_ptr()))
-        return count, scale, L_dir
+        self._ck(fn(self._h, n, position.data_ptr(), ap, weight.data_ptr(), reference.data_ptr(), C.byref(prm),
+                    sampler.state.data_ptr(), sampler.inc.data_ptr(), mp, count.data_ptr(), scale.data_ptr(), estimate.data_ptr(),
+                    _stream_ptr()))
+        return count, scale, estimate
 
     # ---- irradiance estimates per spatial leaf (include/pgsd_irradiance.h; not in the reference) -----------------------------
     def irradianceBuild(self):
@@ -497,7 +502,7 @@ class SDTree:
         _f32(position, (3, n))
         m, mp = _mask(active, n)
         np_ = _f32(normal, (3, n)).data_ptr() if normal is not None else None
-        E = torch.empty(n, dtype=torch.float32, device=self.device)
+        E = self._new(n)
         self._ck(self._lib.pg_irradiance_query(self._h, n, position.data_ptr(), np_, mp, E.data_ptr(), _stream_ptr()))
         return E
 
@@ -507,22 +512,8 @@ class SDTree:
         """(count int32 (N,), scale float32 (N,), E float32 (N,)) (pg_irradiance_rr): radianceRoulette's decision on the
         irradiance estimate, before a direction is sampled.  weight: the paths' throughput with rho / pi folded in.  One draw
         of `sampler` per active lane."""
-        n = position.shape[1]
-        _f32(position, (3, n))
-        np_ = _f32(normal, (3, n)).data_ptr() if normal is not None else None
-        _f32(weight, (n,))
-        _f32(reference, (n,))
-        if sampler.n != n:
-            raise ValueError("the sampler must have one stream per lane")
-        m, mp = _mask(active, n)
-        count = torch.empty(n, dtype=torch.int32, device=self.device)
-        scale = torch.empty(n, dtype=torch.float32, device=self.device)
-        E = torch.empty(n, dtype=torch.float32, device=self.device)
-        prm = N.pg_rr_params(float(window), int(max_split))
-        self._ck(self._lib.pg_irradiance_rr(self._h, n, position.data_ptr(), np_, weight.data_ptr(), reference.data_ptr(),
-                                            C.byref(prm), sampler.state.data_ptr(), sampler.inc.data_ptr(), mp,
-                                            count.data_ptr(), scale.data_ptr(), E.data_ptr(), _stream_ptr()))
-        return count, scale, E
+        return self._roulette(self._lib.pg_irradiance_rr, position, normal, True, weight, reference, sampler, window, max_split,
+                              active)
 
     # ---- a whole guided bounce behind one KD descent (include/pgsd_bounce.h; not in the reference) -------------------------
     def bounce(self, position, dir_nee, nee_active, dir_io, mode=None, u_select=None, sampler: Optional[PCG32Sampler] = None,
@@ -553,10 +544,8 @@ class SDTree:
             a.rng_state, a.rng_inc = sampler.state.data_ptr(), sampler.inc.data_ptr()
         if lanes is not None:
             lane_index, lane_count = lanes
-            if (lane_index.dtype != torch.int32 or lane_count.dtype != torch.int32 or lane_index.numel() < n
-                    or lane_count.numel() < 2):
-                raise ValueError("lanes must be (int32[n], int32[2]) (from compactLanes)")
-            a.lane_index, a.d_lane_count = lane_index.data_ptr(), lane_count.data_ptr()
+            a.lane_index, a.d_lane_count = _lane_ptrs(lane_index, lane_count, n,
+                                                      "lanes must be (int32[n], int32[2]) (from compactLanes)")
         res = dict(out) if out else {}
         names = ("select", "fraction", "pdf_nee", "pdf") + (("L_dir", "L_mean") if radiance else ())
         for k in names:
@@ -580,25 +569,24 @@ class SDTree:
         accumulators.  Reads the pass's buffers on the current stream: with in_flight = 2 call scene.join() first; valid
         until the next pass of that buffer set."""
         S = int(self._pass_lanes.get(int(slot), 0)) * self._max_depth
-        out = {
-            "position": torch.empty((3, S), dtype=torch.float32, device=self.device),
-            "direction": torch.empty((2, S), dtype=torch.float32, device=self.device),
-            "radiance": torch.empty(S, dtype=torch.float32, device=self.device),
-            "woPdf": torch.empty(S, dtype=torch.float32, device=self.device),
-            "direction_nee": torch.empty((2, S), dtype=torch.float32, device=self.device),
-            "radiance_nee_lum": torch.empty(S, dtype=torch.float32, device=self.device),
-            "slot": torch.empty(S, dtype=torch.int32, device=self.device),
-            "count": torch.zeros(1, dtype=torch.int32, device=self.device),
-        }
-        o = N.pg_records_out()
+        count = torch.zeros(1, dtype=torch.int32, device=self.device)
         # (never NULL, also for S = 0: the library then refuses because no pass recorded geometry, not because of a pointer)
-        ptr = lambda t: t.data_ptr() or out["count"].data_ptr()  # noqa: E731
-        o.position = ptr(out["position"]); o.direction = ptr(out["direction"])
-        o.radiance = ptr(out["radiance"]); o.wo_pdf = ptr(out["woPdf"])
-        o.direction_nee = ptr(out["direction_nee"]); o.radiance_nee_lum = ptr(out["radiance_nee_lum"])
+        out, o = self._records_out(S, count.data_ptr())
+        out["slot"] = self._new(S, dtype=torch.int32)
+        out["count"] = count
         self._ck(self._lib.pg_render_export_records(self._h, int(slot), C.byref(o), out["slot"].data_ptr() or None,
                                                     out["count"].data_ptr(), _stream_ptr()))
         return out
+
+    def _records_out(self, S: int, null=None):
+        """The six columns addDataPropagate takes, fresh and S records long, and the pg_records_out that points at them (`null`:
+        what stands for the pointer of an empty column)."""
+        out = {"position": self._new(3, S), "direction": self._new(2, S), "radiance": self._new(S), "woPdf": self._new(S),
+               "direction_nee": self._new(2, S), "radiance_nee_lum": self._new(S)}
+        o = N.pg_records_out()
+        for (field, _), t in zip(o._fields_, out.values()):  # (the struct's members in the order of the columns)
+            setattr(o, field, t.data_ptr() or null)
+        return out, o
 
     def _dense(self, rec: Dict[str, torch.Tensor], S: int) -> N.pg_dense_records:
         d = N.pg_dense_records()
@@ -622,18 +610,7 @@ class SDTree:
         S = num_rays * max_depth
         _f32(Lfinal, (3, num_rays))
         d = self._dense(rec, S)
-        out = {
-            "position": torch.empty((3, S), dtype=torch.float32, device=self.device),
-            "direction": torch.empty((2, S), dtype=torch.float32, device=self.device),
-            "radiance": torch.empty(S, dtype=torch.float32, device=self.device),
-            "woPdf": torch.empty(S, dtype=torch.float32, device=self.device),
-            "direction_nee": torch.empty((2, S), dtype=torch.float32, device=self.device),
-            "radiance_nee_lum": torch.empty(S, dtype=torch.float32, device=self.device),
-        }
-        o = N.pg_records_out()
-        o.position = out["position"].data_ptr(); o.direction = out["direction"].data_ptr()
-        o.radiance = out["radiance"].data_ptr(); o.wo_pdf = out["woPdf"].data_ptr()
-        o.direction_nee = out["direction_nee"].data_ptr(); o.radiance_nee_lum = out["radiance_nee_lum"].data_ptr()
+        out, o = self._records_out(S)
         count = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._ck(self._lib.pg_process_records(self._h, num_rays, max_depth, Lfinal.data_ptr(), C.byref(d), C.byref(o),
                                               count.data_ptr(), _stream_ptr()))
@@ -744,19 +721,8 @@ class SDTree:
 
     def export(self) -> Dict[str, np.ndarray]:
         s = self.sizes()
-        nk, nq, nr = s.n_kd, s.n_quad, s.n_roots
-        a = {
-            "kdtree_bbox_min": np.empty((nk, 3), np.float32), "kdtree_bbox_max": np.empty((nk, 3), np.float32),
-            "kdtree_depth": np.empty(nk, np.uint32), "kdtree_vertCount": np.empty(nk, np.float32),
-            "kdtree_isLeaf": np.empty(nk, np.uint8), "kdtree_quadTreeRootIndex": np.empty(nk, np.uint32),
-            "kdtree_child_left_index": np.empty(nk, np.uint32), "kdtree_child_right_index": np.empty(nk, np.uint32),
-            "quadtree_rootNodeIndex": np.empty(nr, np.uint32),
-            "quadtree_bbox_min": np.empty((nq, 2), np.float32), "quadtree_bbox_max": np.empty((nq, 2), np.float32),
-            "quadtree_depth": np.empty(nq, np.uint32), "quadtree_irradiance": np.empty(nq, np.float32),
-            "quadtree_isLeaf": np.empty(nq, np.uint8), "quadtree_refinementThreshold": np.empty(nq, np.float32),
-        }
-        for k in (1, 2, 3, 4):
-            a["quadtree_child_%d_index" % k] = np.empty(nq, np.uint32)
+        a = {name: np.empty((getattr(s, size), width) if width > 1 else getattr(s, size), dtype)
+             for name, _, dtype, size, width in _TREE_COLUMNS}
         c = _columns(a)
         self._ck(self._lib.pg_export(self._h, C.byref(s), C.byref(c)))
         a["kdtree_isLeaf"] = a["kdtree_isLeaf"].astype(bool)
@@ -768,25 +734,7 @@ class SDTree:
         return a
 
     def load(self, d: Dict[str, np.ndarray]):
-        a = {
-            "kdtree_bbox_min": np.ascontiguousarray(d["kdtree_bbox_min"], np.float32),
-            "kdtree_bbox_max": np.ascontiguousarray(d["kdtree_bbox_max"], np.float32),
-            "kdtree_depth": np.ascontiguousarray(d["kdtree_depth"], np.uint32),
-            "kdtree_vertCount": np.ascontiguousarray(d["kdtree_vertCount"], np.float32),
-            "kdtree_isLeaf": np.ascontiguousarray(d["kdtree_isLeaf"], np.uint8),
-            "kdtree_quadTreeRootIndex": np.ascontiguousarray(d["kdtree_quadTreeRootIndex"], np.uint32),
-            "kdtree_child_left_index": np.ascontiguousarray(d["kdtree_child_left_index"], np.uint32),
-            "kdtree_child_right_index": np.ascontiguousarray(d["kdtree_child_right_index"], np.uint32),
-            "quadtree_rootNodeIndex": np.ascontiguousarray(d["quadtree_rootNodeIndex"], np.uint32),
-            "quadtree_bbox_min": np.ascontiguousarray(d["quadtree_bbox_min"], np.float32),
-            "quadtree_bbox_max": np.ascontiguousarray(d["quadtree_bbox_max"], np.float32),
-            "quadtree_depth": np.ascontiguousarray(d["quadtree_depth"], np.uint32),
-            "quadtree_irradiance": np.ascontiguousarray(d["quadtree_irradiance"], np.float32),
-            "quadtree_isLeaf": np.ascontiguousarray(d["quadtree_isLeaf"], np.uint8),
-            "quadtree_refinementThreshold": np.ascontiguousarray(d["quadtree_refinementThreshold"], np.float32),
-        }
-        for k in (1, 2, 3, 4):
-            a["quadtree_child_%d_index" % k] = np.ascontiguousarray(d["quadtree_child_%d_index" % k], np.uint32)
+        a = {name: np.ascontiguousarray(d[name], dtype) for name, _, dtype, _, _ in _TREE_COLUMNS}
         c = _columns(a)
         c.kd_max_leaf_size = float(d["kdtree_maxLeafSize"])
         c.kd_max_depth = int(d["kdtree_maxDepth"])
@@ -854,25 +802,30 @@ class SDTree:
         return dc
 
 
+# The columns of a tree in the reference's npz schema: (npz name, member of pg_tree_columns -- or (member, index) of an array of
+# pointers --, dtype, the member of pg_tree_sizes that counts its rows, values per row).  export, load and _columns walk it.
+_TREE_COLUMNS = [
+    ("kdtree_bbox_min", "kd_bbox_min", np.float32, "n_kd", 3), ("kdtree_bbox_max", "kd_bbox_max", np.float32, "n_kd", 3),
+    ("kdtree_depth", "kd_depth", np.uint32, "n_kd", 1), ("kdtree_vertCount", "kd_vert_count", np.float32, "n_kd", 1),
+    ("kdtree_isLeaf", "kd_is_leaf", np.uint8, "n_kd", 1), ("kdtree_quadTreeRootIndex", "kd_quad_root_index", np.uint32, "n_kd", 1),
+    ("kdtree_child_left_index", "kd_child_left", np.uint32, "n_kd", 1),
+    ("kdtree_child_right_index", "kd_child_right", np.uint32, "n_kd", 1),
+    ("quadtree_rootNodeIndex", "quad_root_node_index", np.uint32, "n_roots", 1),
+    ("quadtree_bbox_min", "quad_bbox_min", np.float32, "n_quad", 2),
+    ("quadtree_bbox_max", "quad_bbox_max", np.float32, "n_quad", 2),
+    ("quadtree_depth", "quad_depth", np.uint32, "n_quad", 1), ("quadtree_irradiance", "quad_irradiance", np.float32, "n_quad", 1),
+    ("quadtree_isLeaf", "quad_is_leaf", np.uint8, "n_quad", 1),
+    ("quadtree_refinementThreshold", "quad_threshold", np.float32, "n_quad", 1),
+] + [("quadtree_child_%d_index" % (k + 1), ("quad_child", k), np.uint32, "n_quad", 1) for k in range(4)]
+
+
 def _columns(a: Dict[str, np.ndarray]) -> N.pg_tree_columns:
     c = N.pg_tree_columns()
-    c.kd_bbox_min = a["kdtree_bbox_min"].ctypes.data
-    c.kd_bbox_max = a["kdtree_bbox_max"].ctypes.data
-    c.kd_depth = a["kdtree_depth"].ctypes.data
-    c.kd_vert_count = a["kdtree_vertCount"].ctypes.data
-    c.kd_is_leaf = a["kdtree_isLeaf"].ctypes.data
-    c.kd_quad_root_index = a["kdtree_quadTreeRootIndex"].ctypes.data
-    c.kd_child_left = a["kdtree_child_left_index"].ctypes.data
-    c.kd_child_right = a["kdtree_child_right_index"].ctypes.data
-    c.quad_root_node_index = a["quadtree_rootNodeIndex"].ctypes.data
-    c.quad_bbox_min = a["quadtree_bbox_min"].ctypes.data
-    c.quad_bbox_max = a["quadtree_bbox_max"].ctypes.data
-    c.quad_depth = a["quadtree_depth"].ctypes.data
-    c.quad_irradiance = a["quadtree_irradiance"].ctypes.data
-    c.quad_is_leaf = a["quadtree_isLeaf"].ctypes.data
-    c.quad_threshold = a["quadtree_refinementThreshold"].ctypes.data
-    for k in range(4):
-        c.quad_child[k] = a["quadtree_child_%d_index" % (k + 1)].ctypes.data
+    for name, member, _, _, _ in _TREE_COLUMNS:
+        if isinstance(member, tuple):
+            getattr(c, member[0])[member[1]] = a[name].ctypes.data
+        else:
+            setattr(c, member, a[name].ctypes.data)
     return c
 
 

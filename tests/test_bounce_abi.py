@@ -1,20 +1,14 @@
-"""include/pgsd_bounce.h, the bindings and the built libraries name the same entry point and lay pg_bounce_args out alike.  No GPU."""
+"""include/pgsd_bounce.h and the bindings give pg_bounce the same arguments and lay pg_bounce_args out alike (what every header
+shares: tests/test_abi.py).  No GPU."""
 import ctypes
 import os
 import re
 
 import pytest
 
+from abi_table import native  # noqa: F401  (the fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def native():
-    from practical_path_guiding_lab_amd import _native
-
-    if not os.path.exists(_native.LIB_PATH):
-        _native.build()
-    return _native
 
 
 @pytest.fixture(scope="module")
@@ -25,23 +19,7 @@ def header():
 def test_header_symbol_is_exported(native, header):
     declared = re.findall(r"^(?:int|const char \*)\s*(pg_[a-z_0-9]+)\s*\(", header, flags=re.M)
     assert declared == ["pg_bounce"]
-    assert tuple(declared) == native.EXPORTS_BOUNCE
-    others = native.EXPORTS + native.EXPORTS_WARP + native.EXPORTS_FRACTION + native.EXPORTS_TARGET + native.EXPORTS_RADIANCE
-    assert not set(declared) & set(others)
-    assert hasattr(ctypes.CDLL(native.LIB_PATH), "pg_bounce")
-    # the ABI version stays: an entry point was added, nothing of pgsd.h changed
-    assert native.lib().pg_abi_version() == native.ABI_VERSION == 6
-    fn = native.lib().pg_bounce
-    assert fn.restype is ctypes.c_int
-    assert fn.argtypes == [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(native.pg_bounce_args), ctypes.c_void_p]
-
-
-def test_the_probe_build_exports_it_too(native):
-    probe = os.path.join(os.path.dirname(native.LIB_PATH), "libpgsd_phases.so")
-    if not os.path.exists(probe):
-        import subprocess
-        subprocess.run(["make", "-C", native.CSRC, "-j4", "probe"], check=True, capture_output=True)
-    assert hasattr(ctypes.CDLL(probe), "pg_bounce")
+    assert native.lib().pg_bounce.argtypes == [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(native.pg_bounce_args), ctypes.c_void_p]
 
 
 def test_struct_layout_matches_header(native, header):

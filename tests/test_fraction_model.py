@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import synth
+from abi_table import native  # noqa: F401  (the fixture)
 from fraction_model import (EDGE_DROPPED, LOSS_KL, LOSS_VARIANCE, FractionModel, limbs, logistic, salt_with_edges,
                             synthetic_records)
 from oracle import pg_oracle as po
@@ -32,36 +33,21 @@ def initial():
     return t
 
 
-def test_the_library_exports_the_fraction_entry_points():
-    from practical_path_guiding_lab_amd import _native
-
-    if not os.path.exists(_native.LIB_PATH):
-        _native.build()
+def test_the_library_exports_the_fraction_entry_points(native):
+    # (what every header shares -- the library, the probe build, the counts, the ABI version: tests/test_abi.py)
     hdr = open(os.path.join(ROOT, "include", "pgsd_fraction.h")).read()
     declared = set(re.findall(r"^int\s*(pg_[a-z_0-9]+)\s*\(", hdr, flags=re.M))
-    assert declared == set(_native.EXPORTS_FRACTION) == {
+    assert declared == set(native.EXPORTS_FRACTION) == {
         "pg_fraction_enable", "pg_fraction_query", "pg_fraction_record", "pg_fraction_step", "pg_fraction_accumulators",
         "pg_fraction_export", "pg_fraction_import"}
     assert "#ifndef PGSD_FRACTION_H" in hdr and '#include "pgsd.h"' in hdr
-    assert len(_native.EXPORTS) == 61 and len(_native.EXPORTS_WARP) == 3      # pgsd.h and pgsd_warp.h keep theirs
-    assert not (set(_native.EXPORTS) | set(_native.EXPORTS_WARP)) & declared
-    raw = ctypes.CDLL(_native.LIB_PATH)
-    for name in declared:
-        assert hasattr(raw, name), name
-    L = _native.lib()
-    assert L.pg_abi_version() == _native.ABI_VERSION == 6
-    assert [len(getattr(L, n).argtypes) for n in _native.EXPORTS_FRACTION] == [2, 6, 5, 2, 3, 9, 8]
-    assert ctypes.sizeof(_native.pg_fraction_params) == 28 and ctypes.sizeof(_native.pg_fraction_records) == 48
+    L = native.lib()
+    assert [len(getattr(L, n).argtypes) for n in native.EXPORTS_FRACTION] == [2, 6, 5, 2, 3, 9, 8]
+    assert ctypes.sizeof(native.pg_fraction_params) == 28 and ctypes.sizeof(native.pg_fraction_records) == 48
     # a NULL context is refused before anything touches a device
-    for n in _native.EXPORTS_FRACTION:
+    for n in native.EXPORTS_FRACTION:
         f = getattr(L, n)
         assert f(*([None] + [0 if a is ctypes.c_uint64 else None for a in f.argtypes[1:]])) == -1, n
-    probe = os.path.join(os.path.dirname(_native.LIB_PATH), "libpgsd_phases.so")
-    if not os.path.exists(probe):   # (__graft_entry__.build() makes it; a run that did not: the Makefile's `probe` target)
-        subprocess.run(["make", "-C", CSRC, "-j4", "probe"], check=True, capture_output=True)
-    P = ctypes.CDLL(probe)
-    assert all(hasattr(P, n) for n in declared)
-    assert "pgsd_fraction.h" in open(os.path.join(CSRC, "Makefile")).read()
 
 
 def _subset(rec, idx):

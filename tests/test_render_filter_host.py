@@ -2,37 +2,29 @@
 of the per-pass filter seed, and the Python layer's bookkeeping of the choice."""
 import ctypes
 import os
-import re
 import sys
 
 import pytest
+
+from abi_table import COUNTS, native  # noqa: F401  (native: the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def test_the_library_exports_what_the_header_declares():
-    """(58, not the 57 the plan for this change counted on: the header declared 56 entry points before it -- pg_set_splat_filter had
-    been added without DESIGN.md's "55 exports" being moved -- and this change adds two.  59 since pg_scene_intersect, the
-    ray-casting probe of the tests, joined them; 60 with pg_bsdf_probe, the BSDF probe; 61 with pg_surface_probe, the surface probe.)"""
-    from practical_path_guiding_lab_amd import _native
-
-    if not os.path.exists(_native.LIB_PATH):
-        _native.build()
-    hdr = open(os.path.join(ROOT, "include", "pgsd.h")).read()
-    declared = set(re.findall(r"^(?:int|const char \*)\s*(pg_[a-z_0-9]+)\s*\(", hdr, flags=re.M))
-    assert len(declared) == len(_native.EXPORTS) == 61 and declared == set(_native.EXPORTS)
-    assert {"pg_render_record_geometry", "pg_render_export_records"} <= declared
-    L = _native.lib()
-    assert L.pg_abi_version() == _native.ABI_VERSION == 6      # added entry points: the number stays
+def test_the_library_exports_what_the_header_declares(native):
+    """(The count of pgsd.h's entry points and how it came about: tests/abi_table.py; header against library: tests/test_abi.py.)"""
+    assert {"pg_render_record_geometry", "pg_render_export_records"} <= set(native.EXPORTS)
+    L = native.lib()
     assert L.pg_render_record_geometry.argtypes == [ctypes.c_void_p, ctypes.c_int32]
     assert len(L.pg_render_export_records.argtypes) == 6
     # a NULL context is refused before anything touches a device
     assert L.pg_render_record_geometry(None, 1) == -1
     assert L.pg_render_export_records(None, 0, None, None, None, None) == -1
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
-    assert "61 exports" in design and "60 exports" not in design and "59 exports" not in design and "58 exports" not in design and "55 exports" not in design
+    n = COUNTS["pgsd.h"]
+    assert "%d exports" % n in design and not [k for k in range(55, n) if "%d exports" % k in design]
 
 
 def test_main_parses_the_splat_filter():

@@ -3,7 +3,6 @@ against itself -- the preimages of the leaves tile the unit square, the warp fil
 is the pdf, the inverse undoes the warp -- and the resource lines of the new kernels.
 
 The float64 model (the same code in float64) is the reference of every tolerance that is not derived here."""
-import ctypes
 import glob
 import os
 import re
@@ -13,6 +12,7 @@ import numpy as np
 import pytest
 
 import synth
+from abi_table import native  # noqa: F401  (the fixture)
 from warp_model import WarpModel, with_dead_quadtree
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,31 +32,18 @@ def models(trees):
     return {k: (WarpModel(t), WarpModel(t, np.float64)) for k, t in trees.items()}
 
 
-def test_the_library_exports_the_warp_entry_points():
-    from practical_path_guiding_lab_amd import _native
-
-    if not os.path.exists(_native.LIB_PATH):
-        _native.build()
+def test_the_library_exports_the_warp_entry_points(native):
+    # (what every header shares -- the library, the probe build, the counts, the ABI version: tests/test_abi.py)
     hdr = open(os.path.join(ROOT, "include", "pgsd_warp.h")).read()
     declared = set(re.findall(r"^int\s*(pg_[a-z_0-9]+)\s*\(", hdr, flags=re.M))
-    assert declared == set(_native.EXPORTS_WARP) == {"pg_sample_warp", "pg_invert_warp", "pg_guide_bounce_warp"}
+    assert declared == set(native.EXPORTS_WARP) == {"pg_sample_warp", "pg_invert_warp", "pg_guide_bounce_warp"}
     assert "#ifndef PGSD_WARP_H" in hdr and '#include "pgsd.h"' in hdr
-    assert len(_native.EXPORTS) == 61 and not set(_native.EXPORTS) & declared   # pgsd.h keeps its 61
-    raw = ctypes.CDLL(_native.LIB_PATH)
-    for name in declared:
-        assert hasattr(raw, name), name
-    L = _native.lib()
-    assert L.pg_abi_version() == _native.ABI_VERSION == 6
+    L = native.lib()
     assert len(L.pg_sample_warp.argtypes) == 8 and len(L.pg_invert_warp.argtypes) == 8 and len(L.pg_guide_bounce_warp.argtypes) == 13
     # a NULL context is refused before anything touches a device
     assert L.pg_sample_warp(None, 1, None, None, None, None, None, None) == -1
     assert L.pg_invert_warp(None, 1, None, None, None, None, None, None) == -1
     assert L.pg_guide_bounce_warp(None, 1, None, None, None, None, None, None, None, None, None, None, None) == -1
-    probe = os.path.join(os.path.dirname(_native.LIB_PATH), "libpgsd_phases.so")
-    if not os.path.exists(probe):   # (__graft_entry__.build() makes it; a run that did not: the Makefile's `probe` target)
-        subprocess.run(["make", "-C", CSRC, "-j4", "probe"], check=True, capture_output=True)
-    P = ctypes.CDLL(probe)
-    assert all(hasattr(P, n) for n in declared)
 
 
 def _leaf_rectangles(m, root):
