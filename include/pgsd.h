@@ -696,6 +696,26 @@ int pg_bsdf_probe(pg_context *ctx, uint64_t n, uint64_t n_mat, const float *d_ma
 int pg_surface_probe(pg_context *ctx, uint64_t n, const int32_t *d_prim, const float *d_origin, const float *d_dir,
                      const float *d_t, const float *d_uv, const float *d_ref, float *d_out, int32_t *d_flags, void *stream);
 
+/* The renderer's emitter sampling by itself, for tests: lane i samples the emitters of the scene set on the context from the
+ * point d_p[3 i ..] whose geometric normal is d_n[3 i ..], with the 2-D sample d_e[2 i], d_e[2 i + 1], through the very device
+ * function the render kernels call at every vertex (at the scene's feature level, with the scene's own emitter list --
+ * flagged quads, then flagged spheres, then directional lights -- and bounding sphere), WITHOUT the visibility test: the
+ * shadow ray is returned instead, for pg_scene_intersect(any_hit = 1) to cast.
+ * d_out: PG_EMITTER_PROBE_FLOATS floats per lane --
+ *   0 ds_d (unit direction to the light point), 3 ds_pdf (its solid-angle density times 1 / (number of emitters); a
+ *   directional light: 1 / (number of emitters)), 4 em_weight = radiance / ds_pdf as if unoccluded, 7 sh_o, 10 sh_d, 13 sh_tmax:
+ *   the shadow ray's origin, unit direction and the length within which any hit occludes;
+ * d_flags: two int32 per lane -- ds_delta (1: a directional light was sampled), need_shadow (1: there is a shadow ray to cast).
+ * A lane without a sample (a scene without emitters, a point inside a sphere light, a light that faces away) has ds_pdf = 0,
+ * a zero weight and no shadow ray: sh_o = 0, sh_d = (0, 0, 1), sh_tmax = 0.
+ * The samples are read back and checked before a lane uses one (the first picks the emitter); d_p and d_n may hold any
+ * float (NaN, infinities, zeros).  n = 0 does nothing; n > 2^20, a sample that is NaN or outside [0, 1], a context without a
+ * scene and a NULL pointer are refused.  All pointers are device pointers.  Synchronises the stream (before reading the
+ * samples back, and after the kernel). */
+#define PG_EMITTER_PROBE_FLOATS 14
+int pg_emitter_probe(pg_context *ctx, uint64_t n, const float *d_p, const float *d_n, const float *d_e, float *d_out,
+                     int32_t *d_flags, void *stream);
+
 /* Per-kernel device time of pg_render_pass, measured with HIP events recorded on the launch
  * stream around each kernel (off by default).  pg_read_kernel_timing synchronises. */
 typedef struct pg_kernel_timing {

@@ -630,6 +630,36 @@ def surface_probe(scene_obj, prim, o, d, t, ref, level=None):
     return split_surface(out, flags)
 
 
+EMITTER_FIELDS = (("ds_d", 0, 3), ("ds_pdf", 3, 1), ("em_weight", 4, 3), ("sh_o", 7, 3), ("sh_d", 10, 3), ("sh_tmax", 13, 1))
+EMITTER_FLAGS = ("ds_delta", "need_shadow")
+EMITTER_FLOATS = 14
+
+
+def split_emitter(out, flags):
+    """the emitter probe's two arrays as a dict of named columns (EMITTER_FIELDS, EMITTER_FLAGS)"""
+    r = {k: (out[:, a:a + w].copy() if w > 1 else out[:, a].copy()) for k, a, w in EMITTER_FIELDS}
+    r.update({k: flags[:, i].copy() for i, k in enumerate(EMITTER_FLAGS)})
+    return r
+
+
+def emitter_probe(scene_obj, p, nrm, e, level=None):
+    """pgo_emitter_probe: p, nrm (n,3) and e (n,2) float32 -- the shading point, its geometric normal and the 2-D sample ->
+    dict of the columns EMITTER_FIELDS (float32) and EMITTER_FLAGS (int32): the emitter sample without its visibility test."""
+    lb = lib()
+    lb.pgo_emitter_probe.argtypes = [C.POINTER(_Scene), C.c_size_t, C.c_int] + [_P] * 5
+    lb.pgo_emitter_probe.restype = None
+    sc, keep = _scene_struct(scene_obj, None, None, None, None)
+    p = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
+    n = p.shape[0]
+    nrm = np.ascontiguousarray(nrm, np.float32).reshape(n, 3)
+    e = np.ascontiguousarray(e, np.float32).reshape(n, 2)
+    out, flags = np.zeros((n, EMITTER_FLOATS), np.float32), np.zeros((n, 2), np.int32)
+    lb.pgo_emitter_probe(C.byref(sc), n, feature_level(scene_obj) if level is None else int(level), _ptr(p), _ptr(nrm), _ptr(e),
+                         _ptr(out), _ptr(flags))
+    del keep
+    return split_emitter(out, flags)
+
+
 def render_pass(pair: "OracleSDTreePair", quads, cam, max_depth, rr_depth, iteration, is_final, seed, spp=1,
                 store_nee=True, bsdf_sampling_fraction=0.5, sumL=None, sumL2=None, spheres=None, materials=None,
                 boxes=None):

@@ -470,16 +470,19 @@ void pgo_surface_probe(const pgo_scene *sc, size_t n, int level, const int32_t *
 	}
 }
 
-/* scene.sample_emitter_direction(si, (e1, e2), test_visibility=True): uniform choice of one
- * emitter (e1 is reused after the choice), then a point on it; returns ds.d, ds.pdf and
- * radiance / pdf (zero when occluded, facing away, or from inside a sphere) */
-static void sample_emitter(const pgo_scene *sc, const int *em, int n_em, v3 p, v3 n, float e1, float e2, v3 *ds_d,
-                           float *ds_pdf, v3 *em_weight, int *ds_delta)
+/* scene.sample_emitter_direction(si, (e1, e2)) without its visibility test: uniform choice of one emitter (e1 is reused
+ * after the choice), then a point on it; returns ds.d, ds.pdf, radiance / pdf as if unoccluded (zero when the light faces
+ * away, or from inside a sphere) and the shadow ray -- origin, unit direction, length to test -- that `need_shadow` says
+ * the caller has to cast */
+static void sample_emitter_ray(const pgo_scene *sc, const int *em, int n_em, v3 p, v3 n, float e1, float e2, v3 *ds_d,
+                               float *ds_pdf, v3 *em_weight, int *ds_delta, int *need_shadow, v3 *sh_o, v3 *sh_d, float *sh_tmax)
 {
 	*ds_d = V(0, 0, 0);
 	*ds_pdf = 0.0f;
 	*em_weight = V(0, 0, 0);
 	*ds_delta = 0;
+	*need_shadow = 0;
+	*sh_o = V(0, 0, 0); *sh_d = V(0, 0, 1); *sh_tmax = 0.0f;
 	if (n_em <= 0) return;
 	const float count = (float)n_em, inv_count = 1.0f / count;
 	uint32_t idx = (uint32_t)(e1 * count);
@@ -501,9 +504,9 @@ static void sample_emitter(const pgo_scene *sc, const int *em, int n_em, v3 p, v
 		const v3 so = vadd(p, vscale(n, mag));
 		const v3 sd = vsub(pl, so);
 		const float sdist = sqrtf(dot3(sd, sd));
-		float th;
-		const int occ = intersect(sc, so, vdivs(sd, sdist), sdist * (1.0f - SHADOW_EPS_F), &th) >= 0;
-		if (!occ) *em_weight = vscale(ld3(Dl + 3), count);
+		*need_shadow = 1;
+		*sh_o = so; *sh_d = vdivs(sd, sdist); *sh_tmax = sdist * (1.0f - SHADOW_EPS_F);
+		*em_weight = vscale(ld3(Dl + 3), count);
 		return;
 	}
 	v3 pl, ln, radiance;
@@ -560,11 +563,57 @@ static void sample_emitter(const pgo_scene *sc, const int *em, int n_em, v3 p, v
 	if (pdf > 0.0f) {
 		const v3 sd = vsub(pl, so);
 		const float sdist = sqrtf(dot3(sd, sd));
-		const v3 sdn = vdivs(sd, sdist);
-		float th;
-		const int occ = intersect(sc, so, sdn, sdist * (1.0f - SHADOW_EPS_F), &th) >= 0;
-		if (!occ) *em_weight = vscale(vdivs(radiance, pdf), count);
+		*need_shadow = 1;
+		*sh_o = so; *sh_d = vdivs(sd, sdist); *sh_tmax = sdist * (1.0f - SHADOW_EPS_F);
+		*em_weight = vscale(vdivs(radiance, pdf), count);
 	}
+}
+
+
+/* ... with its visibility test (test_visibility=True): em_weight is zero where the shadow ray meets anything */
+static void sample_emitter(const pgo_scene *sc, const int *em, int n_em, v3 p, v3 n, float e1, float e2, v3 *ds_d,
+                           float *ds_pdf, v3 *em_weight, int *ds_delta)
+{
+	int need_shadow;
+	v3 sh_o, sh_d;
+	float sh_tmax, th;
+	sample_emitter_ray(sc, em, n_em, p, n, e1, e2, ds_d, ds_pdf, em_weight, ds_delta, &need_shadow, &sh_o, &sh_d, &sh_tmax);
+	if (need_shadow && intersect(sc, sh_o, sh_d, sh_tmax, &th) >= 0) *em_weight = V(0, 0, 0);
+}
+
+/* Emitter sampling of the render pass by itself: lane i makes one call of sample_emitter_ray from the point p[3 i ..] with
+ * the geometric normal nrm[3 i ..] and the sample e[2 i ..], against the emitter list the render pass builds (flagged quads,
+ * flagged spheres, directional lights; layout: pg_oracle_render.h) */
+void pgo_emitter_probe(const pgo_scene *sc, size_t n, int level, const float *p, const float *nrm, const float *e, float *out,
+                       int32_t *flags)
+{
+	(void)level; /* (the device folds branches away by it; the results do not depend on it) */
+	int n_em = 0;
+	/* (one entry more than the list can hold, as the render pass allocates it: never malloc(0); sample_emitter_ray clamps its
+	 * index below n_em and never reads it) */
+	int *em = malloc(sizeof(int) * (sc->n_quads + sc->n_spheres + sc->n_dir_lights + 1));
+	for (size_t q = 0; q < sc->n_quads; ++q)
+		if (sc->quads[q * PGO_QUAD_STRIDE + 15] != 0.0f) em[n_em++] = (int)q;
+	for (size_t s = 0; s < sc->n_spheres; ++s)
+		if (sc->spheres[s * PGO_SPHERE_STRIDE + 5] != 0.0f) em[n_em++] = (int)(sc->n_quads + s);
+	for (size_t k = 0; k < sc->n_dir_lights; ++k) em[n_em++] = -1 - (int)k;
+	for (size_t i = 0; i < n; ++i) {
+		v3 ds_d, w, sh_o, sh_d;
+		float ds_pdf, sh_tmax;
+		int delta, need;
+		sample_emitter_ray(sc, em, n_em, ld3(p + 3 * i), ld3(nrm + 3 * i), e[2 * i], e[2 * i + 1], &ds_d, &ds_pdf, &w, &delta,
+		                   &need, &sh_o, &sh_d, &sh_tmax);
+		float *o = out + PGO_EMITTER_PROBE_FLOATS * i;
+		o[0] = ds_d.x; o[1] = ds_d.y; o[2] = ds_d.z;
+		o[3] = ds_pdf;
+		o[4] = w.x; o[5] = w.y; o[6] = w.z;
+		o[7] = sh_o.x; o[8] = sh_o.y; o[9] = sh_o.z;
+		o[10] = sh_d.x; o[11] = sh_d.y; o[12] = sh_d.z;
+		o[13] = sh_tmax;
+		flags[2 * i] = delta;
+		flags[2 * i + 1] = need;
+	}
+	free(em);
 }
 
 /* Mitsuba warp::square_to_uniform_disk_concentric */

@@ -143,6 +143,19 @@ void pgo_intersect(const pgo_scene *scene, size_t n, const float *origin, const 
 void pgo_surface_probe(const pgo_scene *scene, size_t n, int level, const int32_t *prim, const float *origin, const float *dir,
                        const float *t, const float *ref, float *out, int32_t *flags);
 
+/* Emitter sampling of the render pass by itself, without its visibility test: lane i samples the scene's emitters (flagged
+ * quads, then flagged spheres, then directional lights) from the point p[3 i ..] whose geometric normal is nrm[3 i ..], with
+ * the 2-D sample e[2 i], e[2 i + 1].  out: PGO_EMITTER_PROBE_FLOATS floats per lane --
+ *   0 ds_d (direction to the light point), 3 ds_pdf (solid-angle density times 1 / emitters), 4 em_weight = radiance / pdf as
+ *   if unoccluded, 7 sh_o, 10 sh_d, 13 sh_tmax: the shadow ray the render pass casts (any hit with 0 < t < sh_tmax occludes);
+ * flags: two per lane -- ds_delta (a directional light), need_shadow (there is a shadow ray to cast).
+ * A lane without a sample (no emitters, inside a sphere light, a light facing away) has ds_pdf = 0, a zero weight and no
+ * shadow ray (sh_o = 0, sh_d = (0, 0, 1), sh_tmax = 0); its ds_d is zero too, but for a light point that faces away.
+ * `level`: the feature level of the device kernels the scene runs on; the results do not depend on it. */
+#define PGO_EMITTER_PROBE_FLOATS 14
+void pgo_emitter_probe(const pgo_scene *scene, size_t n, int level, const float *p, const float *nrm, const float *e, float *out,
+                       int32_t *flags);
+
 /* Texture `index` of the scene at (u, v): the reflectance a textured material takes there. */
 void pgo_texture_eval(const pgo_scene *scene, int index, float u, float v, float rgb[3]);
 

@@ -169,6 +169,7 @@ SURFACE = {
         "pg_scene_intersect": [V, U64, V, V, V, I32, I32, V, V, V, V],
         "pg_bsdf_probe": [V, U64, U64, V, V, V, V, V, I32, V, V, V, V, V, V, V, V],
         "pg_surface_probe": [V, U64, V, V, V, V, V, V, V, V, V],
+        "pg_emitter_probe": [V, U64, V, V, V, V, V, V],
     },
     "pgsd_warp.h": {  # sample warping: same library, same ABI version
         "pg_sample_warp": [V, U64, V, V, V, V, V, V], "pg_invert_warp": [V, U64, V, V, V, V, V, V],

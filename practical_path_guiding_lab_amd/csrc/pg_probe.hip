@@ -4,8 +4,11 @@
 // kShadeTopNodes nodes, the kSlim walk) and one without staged nodes.  pg_bsdf_probe: the BSDF layer by itself -- one
 // (material row, wi, wo, u) per lane through load_material, bsdf_eval_pdf<> and bsdf_sample<> of the same header.
 // pg_surface_probe: the surface at a hit by itself -- one (shape, ray, t, barycentrics, previous vertex) per lane through
-// surface_at<>, normal_at<>, make_frame, to_local, to_world and emitter_hit_pdf<> as stage_a1 calls them.  Nothing of the
-// product path launches these kernels.
+// surface_at<>, normal_at<>, make_frame, to_local, to_world and emitter_hit_pdf<> as stage_a1 calls them.
+// pg_emitter_probe: emitter sampling by itself -- one (point, geometric normal, 2-D sample) per lane through
+// sample_emitter_ray<> with the scene's own emitter list, directional lights and bounding sphere, as stage_a1 passes them.
+// Nothing of the product path launches these kernels.
+#include <string>
 #include <vector>
 
 #include "pg_render_dev.hpp"
@@ -151,7 +154,85 @@ __global__ __launch_bounds__(kRBlock) void k_probe_surface(SurfaceProbeArgs p)
 }
 static_assert(PG_SURFACE_PROBE_FLOATS == 31, "k_probe_surface writes 31 floats per lane");
 
+struct EmitterProbeArgs {
+	Shapes shapes;
+	DirLights dir_lights;
+	const int32_t *emitters;
+	int n_emitters;
+	uint64_t n;
+	const float *p, *ng, *e; // (n,3), (n,3), (n,2)
+	float *out;              // (n, PG_EMITTER_PROBE_FLOATS)
+	int32_t *flags;          // (n,2)
+};
+
+// No loop and no BVH walk; every address is a function of tid < n but the emitter's row, whose number sample_emitter_ray
+// clamps to [0, n_emitters) whatever e1 is (the host refuses an e outside [0, 1] all the same) and whose entry
+// pg_scene_set_ex made from the scene's own counts: a flagged quad, a flagged sphere or -1 - k of a directional light k.
+template <int kLevel>
+__global__ __launch_bounds__(kRBlock) void k_probe_emitter(EmitterProbeArgs a)
+{
+	const uint64_t tid = (uint64_t)blockIdx.x * kRBlock + threadIdx.x;
+	if (tid >= a.n) return;
+	const v3 p = ld3(a.p + 3 * tid), ng = ld3(a.ng + 3 * tid);
+	v3 ds_d, em_w, sh_o, sh_d;
+	float ds_pdf, sh_tmax;
+	bool ds_delta, need_shadow;
+	sample_emitter_ray<kLevel>(a.shapes, a.dir_lights, a.emitters, a.n_emitters, p, ng, a.e[2 * tid], a.e[2 * tid + 1], ds_d,
+	                           ds_pdf, em_w, ds_delta, need_shadow, sh_o, sh_d, sh_tmax);
+	float *o = a.out + (uint64_t)PG_EMITTER_PROBE_FLOATS * tid;
+	o[0] = ds_d.x; o[1] = ds_d.y; o[2] = ds_d.z;
+	o[3] = ds_pdf;
+	o[4] = em_w.x; o[5] = em_w.y; o[6] = em_w.z;
+	o[7] = sh_o.x; o[8] = sh_o.y; o[9] = sh_o.z;
+	o[10] = sh_d.x; o[11] = sh_d.y; o[12] = sh_d.z;
+	o[13] = sh_tmax;
+	a.flags[2 * tid] = ds_delta ? 1 : 0;
+	a.flags[2 * tid + 1] = need_shadow ? 1 : 0;
+}
+static_assert(PG_EMITTER_PROBE_FLOATS == 14, "k_probe_emitter writes 14 floats per lane");
+
 } // namespace
+
+int pg_emitter_probe(pg_context *ctx, uint64_t n, const float *d_p, const float *d_n, const float *d_e, float *d_out,
+                     int32_t *d_flags, void *stream)
+{
+	if (!ctx) return PG_ERR_INVALID;
+	if (!ctx->render || !scene_state(ctx).have_scene) return fail(ctx, PG_ERR_INVALID, "pg_emitter_probe: call pg_scene_set first");
+	if (n > kProbeMaxRays) return fail(ctx, PG_ERR_INVALID, "pg_emitter_probe: at most 2^20 lanes in one call");
+	if (n == 0) return PG_OK;
+	if (!d_p || !d_n || !d_e || !d_out || !d_flags) return fail(ctx, PG_ERR_INVALID, "pg_emitter_probe: NULL pointer");
+	PG_HIP(ctx, hipSetDevice(ctx->device));
+	const SceneState &sc = scene_state(ctx);
+	const hipStream_t s = (hipStream_t)stream;
+	PG_HIP(ctx, hipStreamSynchronize(s)); // (the caller's writes of the inputs, before the host reads them)
+	// the samples are checked on the host: the emitter's index comes from e1
+	std::vector<float> e(2 * n);
+	PG_HIP(ctx, hipMemcpy(e.data(), d_e, e.size() * sizeof(float), hipMemcpyDeviceToHost));
+	for (uint64_t i = 0; i < 2 * n; ++i)
+		if (!(e[i] >= 0.0f && e[i] <= 1.0f)) return fail(ctx, PG_ERR_INVALID, "pg_emitter_probe: sample outside [0, 1]");
+	// (the emitter list needs no check here: pg_scene_set_ex builds it itself from the flags of the quads and spheres it has
+	// counted and from the number of directional lights, which set feature level 3 -- no caller's index enters it)
+	EmitterProbeArgs a;
+	a.shapes.quads = sc.quads.p; a.shapes.spheres = sc.spheres.p; a.shapes.boxes = sc.boxes.p; a.shapes.tris = sc.tris.p;
+	a.shapes.tri_normals = nullptr; a.shapes.tri_uvs = nullptr;
+	a.shapes.textures = nullptr; a.shapes.texels = nullptr; a.shapes.srgb_lut = nullptr;
+	a.shapes.bvh = sc.bvh.p; a.shapes.n_bvh_nodes = sc.n_bvh_nodes;
+	a.shapes.n_quads = sc.n_quads; a.shapes.n_spheres = sc.n_spheres; a.shapes.n_boxes = sc.n_boxes;
+	a.dir_lights.lights = sc.dir_lights.p;
+	for (int c = 0; c < 4; ++c) a.dir_lights.bsphere[c] = sc.bsphere[c];
+	a.emitters = sc.emitters.p; a.n_emitters = sc.n_emitters;
+	a.n = n; a.p = d_p; a.ng = d_n; a.e = d_e; a.out = d_out; a.flags = d_flags;
+	const dim3 grid((unsigned)((n + kRBlock - 1) / kRBlock));
+	switch (sc.general) {
+	case 0: hipLaunchKernelGGL((k_probe_emitter<0>), grid, dim3(kRBlock), 0, s, a); break;
+	case 1: hipLaunchKernelGGL((k_probe_emitter<1>), grid, dim3(kRBlock), 0, s, a); break;
+	case 2: hipLaunchKernelGGL((k_probe_emitter<2>), grid, dim3(kRBlock), 0, s, a); break;
+	default: hipLaunchKernelGGL((k_probe_emitter<3>), grid, dim3(kRBlock), 0, s, a); break;
+	}
+	PG_HIP(ctx, hipGetLastError());
+	PG_HIP(ctx, hipStreamSynchronize(s));
+	return PG_OK;
+}
 
 int pg_surface_probe(pg_context *ctx, uint64_t n, const int32_t *d_prim, const float *d_origin, const float *d_dir,
                      const float *d_t, const float *d_uv, const float *d_ref, float *d_out, int32_t *d_flags, void *stream)

@@ -233,6 +233,23 @@ class WavefrontScene:
                                                     torch.cuda.current_stream().cuda_stream))
         return out, flags
 
+    EMITTER_PROBE_FLOATS = 14  # PG_EMITTER_PROBE_FLOATS of include/pgsd.h
+
+    def emitter_probe(self, tree, p: torch.Tensor, n: torch.Tensor, e: torch.Tensor):
+        """pg_emitter_probe: the renderer's emitter sampling by itself, without its visibility test, for tests -- p, n (k,3):
+        the shading point and its geometric normal, e (k,2) in [0, 1]: the 2-D sample; float32 cuda tensors.  Returns
+        (out (k, 14) float32, flags (k, 2) int32) in the layout include/pgsd.h documents."""
+        self._upload(tree)
+        pp, nn, ee = (a.to(torch.float32).contiguous() for a in (p, n, e))
+        k = pp.shape[0]
+        if pp.shape != (k, 3) or nn.shape != (k, 3) or ee.shape != (k, 2):
+            raise ValueError("p, n: (k,3); e: (k,2)")
+        out = torch.empty((k, self.EMITTER_PROBE_FLOATS), dtype=torch.float32, device=pp.device)
+        flags = torch.empty((k, 2), dtype=torch.int32, device=pp.device)
+        N.check(tree._h, tree._lib.pg_emitter_probe(tree._h, k, pp.data_ptr(), nn.data_ptr(), ee.data_ptr(), out.data_ptr(),
+                                                    flags.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        return out, flags
+
     def join(self) -> None:
         """in_flight = 2: the current stream waits for every pass issued so far (no host synchronisation)."""
         if self._streams is not None:

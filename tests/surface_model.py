@@ -272,6 +272,21 @@ def duff(n, sign=None):
     return s, np.stack([b, sign + n[:, 1] ** 2 * a, -n[:, 1]], axis=1)
 
 
+@np.errstate(invalid="ignore", over="ignore", divide="ignore")
+def cone_density(ref, c, r, inv):
+    """the density 1 / (2 pi (1 - cos alpha)) times inv of the cone a sphere (c, r) subtends from ref, sin alpha = r / |c - ref|
+    -> (sin alpha, its bracket, the density, its bracket, cos alpha, d_ca: the absolute error float32 leaves in cos alpha)"""
+    sinf = lambda r_, c_, rad_: rad_ / np.sqrt(_dot(c_ - r_, c_ - r_))
+    sin, sin_b = bracket(sinf, [ref, c, r], 8)
+    mm = 1 - sin ** 2
+    ca = np.sqrt(np.maximum(mm, 0.0))
+    cone = lambda r_, c_, rad_: inv / (2 * np.pi * (1 - np.sqrt(np.maximum(1 - sinf(r_, c_, rad_) ** 2, 0.0))))
+    cq, cb = bracket(cone, [ref, c, r], OPS["pdf_cone"])
+    # the two intermediate results whose last place is not small against them (module docstring)
+    d_ca = ulp(ca) + (ulp(mm) + 3 * EPS * sin ** 2) / (2 * np.maximum(ca, 1e-300))
+    return sin, sin_b, cq, cb + cq / (1 - ca) * d_ca, ca, d_ca
+
+
 def emitter_pdf(T, m, ref, p, n, C=None):
     """the density for hits m.prim at the implementation's own p and n (float32 values), seen from ref -> Quantity (n,)"""
     C = C or BAND_C
@@ -298,15 +313,7 @@ def emitter_pdf(T, m, ref, p, n, C=None):
         use_area = np.ones(n_l, bool)
         if k.any():   # the cone
             c, r = m.centre, np.where(k, m.radius, 1.0)
-            sinf = lambda r_, c_, rad_: rad_ / np.sqrt(_dot(c_ - r_, c_ - r_))
-            sin, sin_b = bracket(sinf, [ref, c, r], 8)
-            mm = 1 - sin ** 2
-            ca = np.sqrt(np.maximum(mm, 0.0))
-            cone = lambda r_, c_, rad_: inv / (2 * np.pi * (1 - np.sqrt(np.maximum(1 - sinf(r_, c_, rad_) ** 2, 0.0))))
-            cq, cb = bracket(cone, [ref, c, r], OPS["pdf_cone"])
-            # the two intermediate results whose last place is not small against them (module docstring)
-            d_ca = ulp(ca) + (ulp(mm) + 3 * EPS * sin ** 2) / (2 * np.maximum(ca, 1e-300))
-            cb = cb + cq / (1 - ca) * d_ca
+            sin, sin_b, cq, cb, _, _ = cone_density(ref, c, r, inv)
             in_cone = k & (sin < CAP_LIMIT)
             lim = k & (np.abs(sin - CAP_LIMIT) <= C["pdf"] * sin_b) & faces
             use_area = ~in_cone

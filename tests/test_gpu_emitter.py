@@ -1,0 +1,199 @@
+"""The device's emitter sampling by itself (pg_emitter_probe: sample_emitter_ray<> of csrc/pg_render_dev.hpp with the scene's
+emitter list, directional lights and bounding sphere as stage_a1 passes them, at the scene's feature level) against the CPU
+oracle's (pgo_emitter_probe) bit for bit -- on the broad sets of five scenes, on the known-answer inputs of
+tests/test_emitter_model.py and on non-finite points and normals -- and against the float64 model of tests/emitter_model.py
+directly, so that a change moving oracle and device together still fails a test.
+
+"Bit for bit" lets one thing differ: WHICH NaN a lane holds; where one side has a NaN the other must have one."""
+import functools
+
+import numpy as np
+import pytest
+
+import emitter_model as EM
+import test_emitter_model as TE
+import test_surface_model as TS
+
+pytestmark = pytest.mark.gpu
+
+SIZES = (1, 63, 64, 65, 257, 4099)
+
+
+@functools.lru_cache(maxsize=None)
+def tree():
+    from practical_path_guiding_lab_amd.sdtree import SDTree
+    return SDTree(0)
+
+
+@functools.lru_cache(maxsize=None)
+def device(name):
+    from practical_path_guiding_lab_amd.render import WavefrontScene
+    return WavefrontScene(TE.scene(name))
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def probe(ws, L):
+    from oracle import pg_oracle as po
+    ws._uploaded_to = None      # (one context serves every scene of this module: the scene is set again)
+    out, flags = ws.emitter_probe(tree(), _dev(L["p"]), _dev(L["n"]), _dev(L["e"]))
+    return po.split_emitter(out.cpu().numpy(), flags.cpu().numpy())
+
+
+def probe_scene(sc, L):
+    from practical_path_guiding_lab_amd.render import WavefrontScene
+    return probe(WavefrontScene(sc), L)
+
+
+def _same(dev, ora, what):
+    from oracle import pg_oracle as po
+    assert set(dev) == set(ora)
+    for k in po.EMITTER_FLAGS:
+        np.testing.assert_array_equal(dev[k], ora[k], err_msg="%s: %s" % (what, k))
+    for k, _, _ in po.EMITTER_FIELDS:
+        a, b = dev[k], ora[k]
+        same = (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
+        assert same.all(), "%s: %s differs on lanes %s, e.g. device %r oracle %r" % (
+            what, k, np.unique(np.nonzero(~same)[0])[:8], a[~same][:3], b[~same][:3])
+
+
+def _first(L, n):
+    return {k: a[:n] for k, a in L.items()}
+
+
+@pytest.mark.parametrize("name", TE.SCENES)
+def test_device_equals_oracle(name):
+    L = {k: a for k, a in TE.broad(name).items() if k != "prim"}
+    assert L["p"].shape[0] == SIZES[-1]
+    ora = TE.probe_oracle(TE.scene(name), L)
+    for n in SIZES:
+        _same(probe(device(name), _first(L, n)), _first(ora, n), "%s n %d" % (name, n))
+
+
+def test_device_equals_oracle_on_the_known_answers():
+    count = 0
+    for label, sc, L in TE.known_cases():
+        _same(probe_scene(sc, L), TE.probe_oracle(sc, L), label)
+        count += 1
+    assert count == 10
+
+
+@pytest.mark.parametrize("name", ["mixed", "torus", "cornell-box"])
+def test_non_finite_points_and_normals(name):
+    """NaN, inf and 0 in p and n: the oracle returns for them (tests/test_emitter_model.py); the device has no loop to run away
+    in and takes no address from a float but the clamped emitter index, which comes from the checked e alone"""
+    L = TE.non_finite_lanes(name)
+    _same(probe(device(name), L), TE.probe_oracle(TE.scene(name), L), name + " non-finite")
+
+
+@pytest.mark.parametrize("name", ["veach-ajar", "mixed", "torus", "cornell-box"])
+def test_device_against_the_model(name):
+    """levels 2 (veach-ajar), 3 (mixed, torus) and 0 (cornell-box, where the sphere branch is folded away)"""
+    from oracle import pg_oracle as po
+    assert po.feature_level(TE.scene(name)) == {"veach-ajar": 2, "mixed": 3, "torus": 3, "cornell-box": 0}[name]
+    L = _first(TE.broad(name), 2048)
+    TE.check(TE.tables(name), L, probe(device(name), L), name + " device")
+
+
+def test_sampling_density():
+    """one pair at 256 x 256 in one call: the oracle's (worst, mass) exactly, and within the tolerances"""
+    pair = "two spheres and a quad"
+    dev = TE.density_differences(pair, probe_scene)
+    ora = TE.density_differences(pair, TE.probe_oracle)
+    print("%s: device %r oracle %r" % (pair, dev, ora))
+    assert dev == ora and dev[0] <= TE.BIN_TOLERANCE[pair] and dev[1] <= TE.MASS_TOLERANCE[pair]
+
+
+def test_mis_consistency_through_the_surface_probe():
+    """ds_pdf of a sample against the device's own emitter_hit_pdf<> for the ray p -> light point (pg_surface_probe), within
+    the sum of the two brackets"""
+    import torch
+    from oracle import pg_oracle as po
+    name = "mixed"
+    L, T = _first(TE.broad(name), 2048), TE.tables(name)
+    ws = device(name)
+    out = probe(ws, L)
+    y = (out["need_shadow"] != 0) & (out["ds_delta"] == 0)
+    prim = T.emitters[EM.choice(T, L["e"][:, 0])[0]]
+    y &= prim >= 0
+    p = L["p"].astype(np.float64)
+    light = out["sh_o"].astype(np.float64) + out["sh_d"] * (out["sh_tmax"].astype(np.float64) / EM.ONE_MINUS_SHADOW)[:, None]
+    d = light - p
+    t = np.linalg.norm(d, axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        d = np.nan_to_num(d / t[:, None])
+    n = p.shape[0]
+    q = np.where(y, prim, 0).astype(np.int32)
+    s_out, s_flags = ws.surface_probe(tree(), _dev(q), _dev(L["p"]), _dev(d.astype(np.float32)), _dev(t.astype(np.float32)),
+                                      torch.zeros((n, 2), dtype=torch.float32, device="cuda"), _dev(L["p"]))
+    hit = po.split_surface(s_out.cpu().numpy(), s_flags.cpu().numpy())
+    fails, judged, between = EM.consistency(T, L["p"], L["e"], out, hit)
+    fails = fails[y[fails]]
+    print("%s: %d lanes judged through pg_surface_probe, %d between the inside cut and the cap limit" % (name, (judged & y).sum(), between.sum()))
+    assert fails.size == 0, (fails[:8], out["ds_pdf"][fails[:8]], hit["emitter_pdf"][fails[:8]])
+    assert (judged & y).sum() >= 1024 and (hit["is_em"][y] == 1).all()
+
+
+def test_composition_with_the_shadow_rays():
+    """em_weight where pg_scene_intersect(any_hit = 1) finds the probe's shadow ray free, zero where it is occluded: what the
+    oracle composes from its own probe and pgo_intersect -- the emitter sample of the render pass"""
+    from oracle import pg_oracle as po
+    name = "veach-ajar"
+    L = {k: a for k, a in TE.broad(name).items() if k != "prim"}
+    ws, sc = device(name), TE.scene(name)
+    dev, ora = probe(ws, L), TE.probe_oracle(sc, L)
+    _, prim, _ = ws.intersect(tree(), _dev(dev["sh_o"]), _dev(dev["sh_d"]), _dev(dev["sh_tmax"]), any_hit=True)
+    occluded = (prim.cpu().numpy() >= 0) & (dev["need_shadow"] != 0)
+    occluded_o = (po.intersect(sc, ora["sh_o"], ora["sh_d"], ora["sh_tmax"])[1] >= 0) & (ora["need_shadow"] != 0)
+    np.testing.assert_array_equal(occluded, occluded_o)
+    got, want = dev["em_weight"] * ~occluded[:, None], ora["em_weight"] * ~occluded_o[:, None]
+    assert (got.view(np.uint32) == want.view(np.uint32)).all()
+    assert occluded.sum() >= 256 and (~occluded & (dev["need_shadow"] != 0)).sum() >= 256
+
+
+def test_misuse_is_refused_with_a_message():
+    import torch
+    from practical_path_guiding_lab_amd import _native as N
+    from practical_path_guiding_lab_amd.sdtree import SDTree
+    L = N.lib()
+    f = lambda n: torch.zeros(n, dtype=torch.float32, device="cuda")
+    p, nrm, e = f(48) + 1, f(48) + 1, f(32) + 0.5
+    out, flags = f(16 * 14), torch.zeros(32, dtype=torch.int32, device="cuda")
+
+    def refused(h, n, args, word):
+        rc = L.pg_emitter_probe(h, n, *args)
+        assert rc < 0 and word in L.pg_last_error(h).decode() and "pg_emitter_probe" in L.pg_last_error(h).decode(), (rc, L.pg_last_error(h))
+
+    good = [p.data_ptr(), nrm.data_ptr(), e.data_ptr(), out.data_ptr(), flags.data_ptr(), None]
+    bare = SDTree(0)
+    refused(bare._h, 16, good, "pg_scene_set")          # no scene
+    tr, ws = SDTree(0), device("cornell-box")
+    ws._uploaded_to = None
+    ws._upload(tr)
+    assert L.pg_emitter_probe(tr._h, 16, *good) == 0
+    for k in range(5):
+        refused(tr._h, 16, good[:k] + [None] + good[k + 1:], "NULL")
+    refused(tr._h, (1 << 20) + 1, good, "2^20")
+    for wrong in (-0.1, 1.5, float("nan")):
+        for at in (6, 7):                                 # (e1 and e2 of lane 3)
+            e[at] = wrong
+            refused(tr._h, 16, good, "[0, 1]")
+            e[at] = 0.5
+    e[6], e[7] = 0.0, 1.0
+    assert L.pg_emitter_probe(tr._h, 16, *good) == 0      # the context stays usable, and the ends of [0, 1] are samples
+    assert L.pg_emitter_probe(tr._h, 0, None, None, None, None, None, None) == 0
+    torch.cuda.synchronize()
+    assert (flags.view(16, 2)[:, 0] == 0).all() and (out.view(16, 14)[:, 3] >= 0).all()
+
+
+def test_a_scene_without_emitters_gives_zero_lanes():
+    from practical_path_guiding_lab_amd import scene as S
+    sc = TS._finish(TE._floor(S), None, TE.MATS(S), None, None, None)
+    L = TE.lanes([(0.3, 0.2, 0.0), (1.0, 2.0, 3.0)], (0.0, 0.0, 1.0), [(0.0, 0.0), (1.0, 1.0)])
+    dev = probe_scene(sc, L)
+    _same(dev, TE.probe_oracle(sc, L), "no emitters")
+    assert not EM.judge(EM.Tables(sc), L["p"], L["n"], L["e"], dev)[0]
+    assert (dev["sh_d"] == (0, 0, 1)).all() and (dev["ds_pdf"] == 0).all() and (dev["need_shadow"] == 0).all()
