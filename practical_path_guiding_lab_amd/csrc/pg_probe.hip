@@ -9,6 +9,7 @@
 // sample_emitter_ray<> with the scene's own emitter list, directional lights and bounding sphere, as stage_a1 passes them.
 // Nothing of the product path launches these kernels.
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "pg_render_dev.hpp"
@@ -59,18 +60,11 @@ __global__ __launch_bounds__(kRBlock) void k_probe_intersect(ProbeArgs p)
 }
 
 template <int kLevel, bool kAny>
-void launch_form(int form, dim3 grid, hipStream_t s, const ProbeArgs &p)
+auto intersect_form(int form) -> void (*)(ProbeArgs)
 {
-	if (form == 0) hipLaunchKernelGGL((k_probe_intersect<kLevel, kAny, 0>), grid, dim3(kRBlock), 0, s, p);
-	else if (form == 1) hipLaunchKernelGGL((k_probe_intersect<kLevel, kAny, 1>), grid, dim3(kRBlock), 0, s, p);
-	else hipLaunchKernelGGL((k_probe_intersect<kLevel, kAny, 2>), grid, dim3(kRBlock), 0, s, p);
-}
-
-template <int kLevel>
-void launch_any(bool any, int form, dim3 grid, hipStream_t s, const ProbeArgs &p)
-{
-	if (any) launch_form<kLevel, true>(form, grid, s, p);
-	else launch_form<kLevel, false>(form, grid, s, p);
+	if (form == 0) return k_probe_intersect<kLevel, kAny, 0>;
+	if (form == 1) return k_probe_intersect<kLevel, kAny, 1>;
+	return k_probe_intersect<kLevel, kAny, 2>;
 }
 
 struct BsdfProbeArgs {
@@ -191,20 +185,48 @@ __global__ __launch_bounds__(kRBlock) void k_probe_emitter(EmitterProbeArgs a)
 }
 static_assert(PG_EMITTER_PROBE_FLOATS == 14, "k_probe_emitter writes 14 floats per lane");
 
+// What every probe does before it reads an argument, in the order in which a caller sees the refusals: the context, the
+// scene (where the probe reads one), the probe's first check of its own (own_first, own_last: the message, or nullptr where
+// the check passes), the lane count, n == 0 (PG_OK: nothing is read), the pointers, its last check, the device.
+// Returns kProbeGo where the probe is to go on, or what the probe returns.
+constexpr int kProbeGo = 1;
+int probe_ready(pg_context *ctx, const std::string &who, bool reads_scene, const char *own_first, uint64_t n, const char *lanes,
+                bool null_pointer, const char *own_last = nullptr)
+{
+	if (!ctx) return PG_ERR_INVALID;
+	if (reads_scene && (!ctx->render || !scene_state(ctx).have_scene)) return fail(ctx, PG_ERR_INVALID, who + ": call pg_scene_set first");
+	if (own_first) return fail(ctx, PG_ERR_INVALID, who + ": " + own_first);
+	if (n > kProbeMaxRays) return fail(ctx, PG_ERR_INVALID, who + ": at most 2^20 " + lanes + " in one call");
+	if (n == 0) return PG_OK;
+	if (null_pointer) return fail(ctx, PG_ERR_INVALID, who + ": NULL pointer");
+	if (own_last) return fail(ctx, PG_ERR_INVALID, who + ": " + own_last);
+	PG_HIP(ctx, hipSetDevice(ctx->device));
+	return kProbeGo;
+}
+
+// One lane per item on `stream`, and the wait for it, of the kernel that kernel_of(std::integral_constant<int, level>()) names
+// (level 0..3; anything else is 3's)
+template <int kLevel> using Level = std::integral_constant<int, kLevel>;
+template <class Args, class KernelOf>
+int run_at_level(pg_context *ctx, int level, uint64_t n, void *stream, const Args &args, KernelOf kernel_of)
+{
+	void (*const kernel)(Args) = level == 0 ? kernel_of(Level<0>()) : level == 1 ? kernel_of(Level<1>())
+	                             : level == 2 ? kernel_of(Level<2>()) : kernel_of(Level<3>());
+	hipLaunchKernelGGL(kernel, dim3((unsigned)((n + kRBlock - 1) / kRBlock)), dim3(kRBlock), 0, (hipStream_t)stream, args);
+	PG_HIP(ctx, hipGetLastError());
+	PG_HIP(ctx, hipStreamSynchronize((hipStream_t)stream));
+	return PG_OK;
+}
+
 } // namespace
 
 int pg_emitter_probe(pg_context *ctx, uint64_t n, const float *d_p, const float *d_n, const float *d_e, float *d_out,
                      int32_t *d_flags, void *stream)
 {
-	if (!ctx) return PG_ERR_INVALID;
-	if (!ctx->render || !scene_state(ctx).have_scene) return fail(ctx, PG_ERR_INVALID, "pg_emitter_probe: call pg_scene_set first");
-	if (n > kProbeMaxRays) return fail(ctx, PG_ERR_INVALID, "pg_emitter_probe: at most 2^20 lanes in one call");
-	if (n == 0) return PG_OK;
-	if (!d_p || !d_n || !d_e || !d_out || !d_flags) return fail(ctx, PG_ERR_INVALID, "pg_emitter_probe: NULL pointer");
-	PG_HIP(ctx, hipSetDevice(ctx->device));
+	const int rc = probe_ready(ctx, "pg_emitter_probe", true, nullptr, n, "lanes", !d_p || !d_n || !d_e || !d_out || !d_flags);
+	if (rc != kProbeGo) return rc;
 	const SceneState &sc = scene_state(ctx);
-	const hipStream_t s = (hipStream_t)stream;
-	PG_HIP(ctx, hipStreamSynchronize(s)); // (the caller's writes of the inputs, before the host reads them)
+	PG_HIP(ctx, hipStreamSynchronize((hipStream_t)stream)); // (the caller's writes of the inputs, before the host reads them)
 	// the samples are checked on the host: the emitter's index comes from e1
 	std::vector<float> e(2 * n);
 	PG_HIP(ctx, hipMemcpy(e.data(), d_e, e.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -213,40 +235,22 @@ int pg_emitter_probe(pg_context *ctx, uint64_t n, const float *d_p, const float 
 	// (the emitter list needs no check here: pg_scene_set_ex builds it itself from the flags of the quads and spheres it has
 	// counted and from the number of directional lights, which set feature level 3 -- no caller's index enters it)
 	EmitterProbeArgs a;
-	a.shapes.quads = sc.quads.p; a.shapes.spheres = sc.spheres.p; a.shapes.boxes = sc.boxes.p; a.shapes.tris = sc.tris.p;
-	a.shapes.tri_normals = nullptr; a.shapes.tri_uvs = nullptr;
-	a.shapes.textures = nullptr; a.shapes.texels = nullptr; a.shapes.srgb_lut = nullptr;
-	a.shapes.bvh = sc.bvh.p; a.shapes.n_bvh_nodes = sc.n_bvh_nodes;
-	a.shapes.n_quads = sc.n_quads; a.shapes.n_spheres = sc.n_spheres; a.shapes.n_boxes = sc.n_boxes;
+	a.shapes = scene_shapes(sc, false);
 	a.dir_lights.lights = sc.dir_lights.p;
 	for (int c = 0; c < 4; ++c) a.dir_lights.bsphere[c] = sc.bsphere[c];
 	a.emitters = sc.emitters.p; a.n_emitters = sc.n_emitters;
 	a.n = n; a.p = d_p; a.ng = d_n; a.e = d_e; a.out = d_out; a.flags = d_flags;
-	const dim3 grid((unsigned)((n + kRBlock - 1) / kRBlock));
-	switch (sc.general) {
-	case 0: hipLaunchKernelGGL((k_probe_emitter<0>), grid, dim3(kRBlock), 0, s, a); break;
-	case 1: hipLaunchKernelGGL((k_probe_emitter<1>), grid, dim3(kRBlock), 0, s, a); break;
-	case 2: hipLaunchKernelGGL((k_probe_emitter<2>), grid, dim3(kRBlock), 0, s, a); break;
-	default: hipLaunchKernelGGL((k_probe_emitter<3>), grid, dim3(kRBlock), 0, s, a); break;
-	}
-	PG_HIP(ctx, hipGetLastError());
-	PG_HIP(ctx, hipStreamSynchronize(s));
-	return PG_OK;
+	return run_at_level(ctx, sc.general, n, stream, a, [](auto L) { return k_probe_emitter<decltype(L)::value>; });
 }
 
 int pg_surface_probe(pg_context *ctx, uint64_t n, const int32_t *d_prim, const float *d_origin, const float *d_dir,
                      const float *d_t, const float *d_uv, const float *d_ref, float *d_out, int32_t *d_flags, void *stream)
 {
-	if (!ctx) return PG_ERR_INVALID;
-	if (!ctx->render || !scene_state(ctx).have_scene) return fail(ctx, PG_ERR_INVALID, "pg_surface_probe: call pg_scene_set first");
-	if (n > kProbeMaxRays) return fail(ctx, PG_ERR_INVALID, "pg_surface_probe: at most 2^20 lanes in one call");
-	if (n == 0) return PG_OK;
-	if (!d_prim || !d_origin || !d_dir || !d_t || !d_uv || !d_ref || !d_out || !d_flags)
-		return fail(ctx, PG_ERR_INVALID, "pg_surface_probe: NULL pointer");
-	PG_HIP(ctx, hipSetDevice(ctx->device));
+	const int rc = probe_ready(ctx, "pg_surface_probe", true, nullptr, n, "lanes",
+	                              !d_prim || !d_origin || !d_dir || !d_t || !d_uv || !d_ref || !d_out || !d_flags);
+	if (rc != kProbeGo) return rc;
 	const SceneState &sc = scene_state(ctx);
-	const hipStream_t s = (hipStream_t)stream;
-	PG_HIP(ctx, hipStreamSynchronize(s)); // (the caller's writes of the inputs, before the host reads them)
+	PG_HIP(ctx, hipStreamSynchronize((hipStream_t)stream)); // (the caller's writes of the inputs, before the host reads them)
 	// the shape numbers are checked on the host before a lane follows them
 	const int64_t n_shapes = (int64_t)sc.n_quads + sc.n_spheres + 6 * (int64_t)sc.n_boxes + (int64_t)sc.n_tris;
 	std::vector<int32_t> prim(n);
@@ -254,42 +258,23 @@ int pg_surface_probe(pg_context *ctx, uint64_t n, const int32_t *d_prim, const f
 	for (uint64_t i = 0; i < n; ++i)
 		if (prim[i] < 0 || (int64_t)prim[i] >= n_shapes) return fail(ctx, PG_ERR_INVALID, "pg_surface_probe: shape number outside the scene");
 	SurfaceProbeArgs p;
-	p.shapes.quads = sc.quads.p; p.shapes.spheres = sc.spheres.p; p.shapes.boxes = sc.boxes.p; p.shapes.tris = sc.tris.p;
-	p.shapes.tri_normals = sc.have_tri_normals ? sc.tri_normals.p : nullptr;
-	p.shapes.tri_uvs = sc.have_tri_uvs ? sc.tri_uvs.p : nullptr;
-	p.shapes.textures = sc.textures.p; p.shapes.texels = sc.texels.p; p.shapes.srgb_lut = sc.srgb_lut.p;
-	p.shapes.bvh = sc.bvh.p; p.shapes.n_bvh_nodes = sc.n_bvh_nodes;
-	p.shapes.n_quads = sc.n_quads; p.shapes.n_spheres = sc.n_spheres; p.shapes.n_boxes = sc.n_boxes;
+	p.shapes = scene_shapes(sc, true);
 	p.mats = sc.mats.p;
 	p.n = n; p.n_emitters = sc.n_emitters; // (an emitter shape is in the scene's emitter list: n_emitters >= 1 wherever a lane divides by it)
 	p.prim = d_prim; p.o = d_origin; p.d = d_dir; p.t = d_t; p.uv = d_uv; p.ref = d_ref; p.out = d_out; p.flags = d_flags;
-	const dim3 grid((unsigned)((n + kRBlock - 1) / kRBlock));
-	switch (sc.general) {
-	case 0: hipLaunchKernelGGL((k_probe_surface<0>), grid, dim3(kRBlock), 0, s, p); break;
-	case 1: hipLaunchKernelGGL((k_probe_surface<1>), grid, dim3(kRBlock), 0, s, p); break;
-	case 2: hipLaunchKernelGGL((k_probe_surface<2>), grid, dim3(kRBlock), 0, s, p); break;
-	default: hipLaunchKernelGGL((k_probe_surface<3>), grid, dim3(kRBlock), 0, s, p); break;
-	}
-	PG_HIP(ctx, hipGetLastError());
-	PG_HIP(ctx, hipStreamSynchronize(s));
-	return PG_OK;
+	return run_at_level(ctx, sc.general, n, stream, p, [](auto L) { return k_probe_surface<decltype(L)::value>; });
 }
 
 int pg_bsdf_probe(pg_context *ctx, uint64_t n, uint64_t n_mat, const float *d_materials, const int32_t *d_material_index,
                   const float *d_wi, const float *d_wo, const float *d_u, int32_t level, float *d_value, float *d_pdf,
                   float *d_sampled_wo, float *d_sampled_pdf, float *d_weight, float *d_eta, int32_t *d_delta, void *stream)
 {
-	if (!ctx) return PG_ERR_INVALID;
-	if (level < 0 || level > 3) return fail(ctx, PG_ERR_INVALID, "pg_bsdf_probe: level must be 0, 1, 2 or 3");
-	if (n > kProbeMaxRays) return fail(ctx, PG_ERR_INVALID, "pg_bsdf_probe: at most 2^20 lanes in one call");
-	if (n == 0) return PG_OK;
-	if (!d_materials || !d_material_index || !d_wi || !d_wo || !d_u || !d_value || !d_pdf || !d_sampled_wo || !d_sampled_pdf ||
-	    !d_weight || !d_eta || !d_delta)
-		return fail(ctx, PG_ERR_INVALID, "pg_bsdf_probe: NULL pointer");
-	if (n_mat == 0 || n_mat > 65536) return fail(ctx, PG_ERR_INVALID, "pg_bsdf_probe: need 1..65536 material rows");
-	PG_HIP(ctx, hipSetDevice(ctx->device));
-	const hipStream_t s = (hipStream_t)stream;
-	PG_HIP(ctx, hipStreamSynchronize(s)); // (the caller's writes of the inputs, before the host reads them)
+	const int rc = probe_ready(ctx, "pg_bsdf_probe", false, level < 0 || level > 3 ? "level must be 0, 1, 2 or 3" : nullptr, n, "lanes",
+	                              !d_materials || !d_material_index || !d_wi || !d_wo || !d_u || !d_value || !d_pdf || !d_sampled_wo ||
+	                                  !d_sampled_pdf || !d_weight || !d_eta || !d_delta,
+	                              n_mat == 0 || n_mat > 65536 ? "need 1..65536 material rows" : nullptr);
+	if (rc != kProbeGo) return rc;
+	PG_HIP(ctx, hipStreamSynchronize((hipStream_t)stream)); // (the caller's writes of the inputs, before the host reads them)
 	// the rows and the row numbers are checked on the host before a lane follows them
 	std::vector<float> rows(n_mat * kMaterialStride);
 	PG_HIP(ctx, hipMemcpy(rows.data(), d_materials, rows.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -303,49 +288,24 @@ int pg_bsdf_probe(pg_context *ctx, uint64_t n, uint64_t n_mat, const float *d_ma
 	p.n = n; p.mats = d_materials; p.mat = d_material_index; p.wi = d_wi; p.wo = d_wo; p.u = d_u;
 	p.value = d_value; p.pdf = d_pdf; p.s_wo = d_sampled_wo; p.s_pdf = d_sampled_pdf; p.s_weight = d_weight; p.s_eta = d_eta;
 	p.s_delta = d_delta;
-	const dim3 grid((unsigned)((n + kRBlock - 1) / kRBlock));
-	switch (level) {
-	case 0: hipLaunchKernelGGL((k_probe_bsdf<0>), grid, dim3(kRBlock), 0, s, p); break;
-	case 1: hipLaunchKernelGGL((k_probe_bsdf<1>), grid, dim3(kRBlock), 0, s, p); break;
-	case 2: hipLaunchKernelGGL((k_probe_bsdf<2>), grid, dim3(kRBlock), 0, s, p); break;
-	default: hipLaunchKernelGGL((k_probe_bsdf<3>), grid, dim3(kRBlock), 0, s, p); break;
-	}
-	PG_HIP(ctx, hipGetLastError());
-	PG_HIP(ctx, hipStreamSynchronize(s));
-	return PG_OK;
+	return run_at_level(ctx, level, n, stream, p, [](auto L) { return k_probe_bsdf<decltype(L)::value>; });
 }
 
 int pg_scene_intersect(pg_context *ctx, uint64_t n, const float *d_origin, const float *d_dir, const float *d_tmax,
                        int32_t any_hit, int32_t walk_form, float *d_t, int32_t *d_prim, float *d_uv, void *stream)
 {
-	if (!ctx) return PG_ERR_INVALID;
-	if (!ctx->render || !scene_state(ctx).have_scene) return fail(ctx, PG_ERR_INVALID, "pg_scene_intersect: call pg_scene_set first");
-	if (walk_form < 0 || walk_form > 2) return fail(ctx, PG_ERR_INVALID, "pg_scene_intersect: walk_form must be 0, 1 or 2");
-	if (n > kProbeMaxRays) return fail(ctx, PG_ERR_INVALID, "pg_scene_intersect: at most 2^20 rays in one call");
-	if (n == 0) return PG_OK;
-	if (!d_origin || !d_dir || !d_tmax || !d_t || !d_prim || !d_uv) return fail(ctx, PG_ERR_INVALID, "pg_scene_intersect: NULL pointer");
-	PG_HIP(ctx, hipSetDevice(ctx->device));
+	const int rc = probe_ready(ctx, "pg_scene_intersect", true, walk_form < 0 || walk_form > 2 ? "walk_form must be 0, 1 or 2" : nullptr,
+	                              n, "rays", !d_origin || !d_dir || !d_tmax || !d_t || !d_prim || !d_uv);
+	if (rc != kProbeGo) return rc;
 	const SceneState &sc = scene_state(ctx);
 	ProbeArgs p;
-	p.shapes.quads = sc.quads.p; p.shapes.spheres = sc.spheres.p; p.shapes.boxes = sc.boxes.p; p.shapes.tris = sc.tris.p;
-	p.shapes.tri_normals = nullptr; p.shapes.tri_uvs = nullptr;
-	p.shapes.textures = nullptr; p.shapes.texels = nullptr; p.shapes.srgb_lut = nullptr;
-	p.shapes.bvh = sc.bvh.p; p.shapes.n_bvh_nodes = sc.n_bvh_nodes;
-	p.shapes.n_quads = sc.n_quads; p.shapes.n_spheres = sc.n_spheres; p.shapes.n_boxes = sc.n_boxes;
+	p.shapes = scene_shapes(sc, false);
 	p.n = n; p.o = d_origin; p.d = d_dir; p.tmax = d_tmax; p.t = d_t; p.uv = d_uv; p.prim = d_prim;
-	// the probe's own overflow strips, for this call only
+	// the probe's own overflow strips, for this call only (freed on return, behind the wait for the kernel)
 	DevBuf<uint2> ovf;
 	PG_HIP(ctx, ovf.ensure((size_t)n * kOvfStack));
 	p.ovf = ovf.p;
-	const dim3 grid((unsigned)((n + kRBlock - 1) / kRBlock));
-	const hipStream_t s = (hipStream_t)stream;
-	switch (sc.general) {
-	case 0: launch_any<0>(any_hit != 0, walk_form, grid, s, p); break;
-	case 1: launch_any<1>(any_hit != 0, walk_form, grid, s, p); break;
-	case 2: launch_any<2>(any_hit != 0, walk_form, grid, s, p); break;
-	default: launch_any<3>(any_hit != 0, walk_form, grid, s, p); break;
-	}
-	PG_HIP(ctx, hipGetLastError());
-	PG_HIP(ctx, hipStreamSynchronize(s)); // (the strips are freed on return)
-	return PG_OK;
+	return run_at_level(ctx, sc.general, n, stream, p, [&](auto L) {
+		return any_hit ? intersect_form<decltype(L)::value, true>(walk_form) : intersect_form<decltype(L)::value, false>(walk_form);
+	});
 }

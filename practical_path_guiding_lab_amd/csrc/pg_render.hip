@@ -561,6 +561,20 @@ SceneState &pg::scene_state(pg_context *ctx) { return rstate(ctx)->scene; }
 bool pg::split_pipeline_always(pg_context *ctx) { return rstate(ctx)->split_always; }
 bool pg::record_geometry_wanted(pg_context *ctx) { return rstate(ctx)->record_geometry; }
 
+Shapes pg::scene_shapes(const SceneState &sc, bool shading_tables)
+{
+	Shapes shapes;
+	shapes.quads = sc.quads.p; shapes.spheres = sc.spheres.p; shapes.boxes = sc.boxes.p; shapes.tris = sc.tris.p;
+	shapes.tri_normals = shading_tables && sc.have_tri_normals ? sc.tri_normals.p : nullptr;
+	shapes.tri_uvs = shading_tables && sc.have_tri_uvs ? sc.tri_uvs.p : nullptr;
+	shapes.textures = shading_tables ? sc.textures.p : nullptr;
+	shapes.texels = shading_tables ? sc.texels.p : nullptr;
+	shapes.srgb_lut = shading_tables ? sc.srgb_lut.p : nullptr;
+	shapes.bvh = sc.bvh.p; shapes.n_bvh_nodes = sc.n_bvh_nodes;
+	shapes.n_quads = sc.n_quads; shapes.n_spheres = sc.n_spheres; shapes.n_boxes = sc.n_boxes;
+	return shapes;
+}
+
 void pg::destroy_render_state(pg_context *ctx)
 {
 	delete ctx->render;
@@ -662,12 +676,7 @@ static RenderArgs pass_args(pg_context *ctx, const pg_pass_params *prm, PassBuf 
 	a.tree = ctx->view();
 	// the scene
 	const SceneState &sc = r->scene;
-	a.shapes.quads = sc.quads.p; a.shapes.spheres = sc.spheres.p; a.shapes.boxes = sc.boxes.p; a.shapes.tris = sc.tris.p;
-	a.shapes.tri_normals = sc.have_tri_normals ? sc.tri_normals.p : nullptr;
-	a.shapes.tri_uvs = sc.have_tri_uvs ? sc.tri_uvs.p : nullptr;
-	a.shapes.textures = sc.textures.p; a.shapes.texels = sc.texels.p; a.shapes.srgb_lut = sc.srgb_lut.p;
-	a.shapes.bvh = sc.bvh.p; a.shapes.n_bvh_nodes = sc.n_bvh_nodes;
-	a.shapes.n_quads = sc.n_quads; a.shapes.n_spheres = sc.n_spheres; a.shapes.n_boxes = sc.n_boxes;
+	a.shapes = scene_shapes(sc, true);
 	a.mats = sc.mats.p; a.emitters = sc.emitters.p; a.n_emitters = sc.n_emitters; a.ior = r->ior.p;
 	a.dir_lights.lights = sc.dir_lights.p;
 	for (int c = 0; c < 4; ++c) a.dir_lights.bsphere[c] = sc.bsphere[c];

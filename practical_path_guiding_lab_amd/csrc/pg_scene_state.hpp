@@ -29,6 +29,10 @@ struct SceneState {
 SceneState &scene_state(pg_context *ctx);
 bool split_pipeline_always(pg_context *ctx);
 bool record_geometry_wanted(pg_context *ctx);
+// ... and the one place that fills the kernels' view of its shapes (Shapes: pg_render_dev.hpp).  shading_tables false: what
+// a kernel that only casts rays or samples emitters reads -- vertex normals, uvs, textures, texels and the sRGB table are null
+struct Shapes;
+Shapes scene_shapes(const SceneState &sc, bool shading_tables);
 
 // pg_scene.hip: the checks pg_scene_set_ex applies to the rows of a material table (host memory, n_mats rows of
 // kMaterialStride floats; n_tex: the textures a row may name) -- the bare reason of the first one a row fails

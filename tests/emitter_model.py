@@ -58,17 +58,18 @@ Decisions within float32's own reach are AMBIGUOUS; the lane must then equal the
   switch        sin^2 alpha_max within its band of 0.00068523                -> `map` is not judged
 C per quantity (BAND_C) is four times the worst ratio measured on the CPU oracle over the suite's own input sets
 (profiles/emitter/band.txt, written by tools/emitter_mutants.py --band)."""
+import functools
+
 import numpy as np
 
 import surface_model as SM
-from surface_model import EPS, _dot, _unit, ulp
+from surface_model import AMBIGUOUS_CAP, EPS, _dot, _unit, ulp  # noqa: F401 (the cap: defined once, read as EM.AMBIGUOUS_CAP)
 
 K_RAY = float(np.float32(1e-4))
 K_SHADOW = float(np.float32(1e-3))
 ONE_MINUS_SHADOW = float(np.float32(1.0) - np.float32(1e-3))   # (1.0f - kShadowEps is itself rounded)
 K_SPHERE = 1500 * 2.0 ** -24
 SWITCH = float(np.float32(0.00068523))
-AMBIGUOUS_CAP = 0.02
 # four times the worst |difference| / bracket measured on the oracle (profiles/emitter/band.txt); 64 would mean a missing term
 BAND_C = {"light": 1.66, "ds_d": 0.75, "sh_o": 0.91, "sh_d": 0.78, "tmax": 0.85, "pdf": 3.00, "weight": 2.62, "radius": 1.38,
           "cone": 0.01, "map": 2.49, "azimuth": 1.16, "near": 0.21}
@@ -89,21 +90,8 @@ class Tables(SM.Tables):
         self.count = self.emitters.shape[0]
 
 
-def bracket(f, xs, ops, scale=None, steps=None):
-    """surface_model.bracket with steps[j], where given, in the place of ulp(x_j)"""
-    q = f(*xs)
-    b = EPS * ops * (np.abs(q) if scale is None else scale)
-    for j, x in enumerate(xs):
-        h = ulp(x) if steps is None or steps[j] is None else np.broadcast_to(steps[j], x.shape)
-        cols = [()] if x.ndim == 1 else [(slice(None), k) for k in range(x.shape[1])]
-        for c in cols:
-            worst = 0.0
-            for sgn in (1.0, -1.0):
-                y = x.copy()
-                y[c] = y[c] + sgn * h[c]
-                worst = np.maximum(worst, np.abs(f(*xs[:j], y, *xs[j + 1:]) - q))
-            b = b + worst
-    return q, np.nan_to_num(b, nan=np.inf)
+# surface_model's bracket, with a bracket that is not a number widened to inf: a band that wide judges nothing
+_bracket = functools.partial(SM.bracket, nan_is_inf=True)
 
 
 def _tangential(r, sin_alpha):
@@ -158,14 +146,14 @@ def _assignment(T, p, n, e2, idx, e1r, e1h, out, C):
         Q = T.quads[np.where(kq, prim, 0)]
         lf = lambda o_, a_, b_, u_, w_: o_ + u_[:, None] * a_ + w_[:, None] * b_
         size = np.abs(Q[:, 0:3]) + np.abs(e1r[:, None] * Q[:, 3:6]) + np.abs(e2[:, None] * Q[:, 6:9])
-        lq, lb = bracket(lf, [Q[:, 0:3], Q[:, 3:6], Q[:, 6:9], e1r, e2], OPS["light_quad"], size, [None, None, None, e1h, None])
+        lq, lb = _bracket(lf, [Q[:, 0:3], Q[:, 3:6], Q[:, 6:9], e1r, e2], OPS["light_quad"], size, [None, None, None, e1h, None])
         L[kq], uL[kq], nl[kq], area[kq], rad[kq] = lq[kq], lb[kq], Q[kq, 9:12], Q[kq, 14], Q[kq, 19:22]
     if kd.any():
         D = T.dir[np.where(kd, -1 - prim, 0)]
         bs = np.tile(T.bsphere, (N, 1))
         lf = lambda p_, d_, s_: p_ - d_ * (2 * np.maximum(s_[:, 3], np.sqrt(_dot(p_ - s_[:, 0:3], p_ - s_[:, 0:3]))))[:, None]
         size = np.abs(p) + np.abs(lf(p, D[:, 0:3], bs) - p)
-        lq, lb = bracket(lf, [p, D[:, 0:3], bs], OPS["light_dir"], size)
+        lq, lb = _bracket(lf, [p, D[:, 0:3], bs], OPS["light_dir"], size)
         L[kd], uL[kd], rad[kd] = lq[kd], lb[kd], D[kd, 3:6]
         v.dir_d = D[:, 0:3]
     centre, radius = np.zeros((N, 3)), one.copy()
@@ -181,14 +169,14 @@ def _assignment(T, p, n, e2, idx, e1r, e1h, out, C):
     graze = np.zeros(N, bool)
     cosf = lambda p_, l_, n_: _dot(_unit(l_ - p_), n_)
     if kq.any():
-        cos, cos_b = bracket(cosf, [p, L, nl], 13, one, [None, uL, None])
+        cos, cos_b = _bracket(cosf, [p, L, nl], 13, one, [None, uL, None])
         expect[kq] = (cos < 0)[kq]
         graze = kq & (np.abs(cos) <= C_DECISION * cos_b) & (dist > 0)
         doubt |= graze
         v.why["graze"] = graze
     inside = np.zeros(N, bool)
     if ks.any():
-        D_, D_b = bracket(lambda p_, c_: np.sqrt(_dot(c_ - p_, c_ - p_)), [p, centre], 8)
+        D_, D_b = _bracket(lambda p_, c_: np.sqrt(_dot(c_ - p_, c_ - p_)), [p, centre], 8)
         adj = radius * (1 - K_SPHERE)
         inside = ks & (D_ <= adj)
         cut = ks & (np.abs(D_ - adj) <= C_DECISION * (D_b + 3 * EPS * radius))
@@ -222,7 +210,7 @@ def _assignment(T, p, n, e2, idx, e1r, e1h, out, C):
     v.ok["need_shadow is ds_pdf > 0"] = sampled == (g["ds_pdf"] > 0)
     v.ok["delta"] = no | (delta == kd)
     # a light that faces away still has its direction (NaN where p is the light point itself); inside a sphere there is none
-    dq, db = bracket(lambda l_, p_: _unit(l_ - p_), [L, p], OPS["unit"], 1.0, [uL, None])
+    dq, db = _bracket(lambda l_, p_: _unit(l_ - p_), [L, p], OPS["unit"], 1.0, [uL, None])
     away = no & kq
     v.ok["ds_d (no sample)"] = ~no | np.where(away, SM._within(g["ds_d"], dq, db, C["ds_d"]) | np.isnan(g["ds_d"]).any(axis=1) | (dist == 0),
                                              zero3(g["ds_d"]) | (ks & ~inside & doubt))
@@ -236,9 +224,9 @@ def _assignment(T, p, n, e2, idx, e1r, e1h, out, C):
         banded("ds_d is -direction", "ds_d", g["ds_d"], -v.dir_d, np.zeros((N, 3)), y & kd)
     # the offset's side
     sidef = lambda n_, l_, p_: _dot(n_, l_ - p_)
-    sd, sd_b = bracket(sidef, [n, L, p], OPS["side"], np.abs(n * (L - p)).sum(axis=1), [None, uL, None])
+    sd, sd_b = _bracket(sidef, [n, L, p], OPS["side"], np.abs(n * (L - p)).sum(axis=1), [None, uL, None])
     if kd.any():   # (a directional light's side is decided by n . ds_d itself)
-        sd2, sd2_b = bracket(lambda n_, d_: -_dot(n_, d_), [n, v.dir_d], OPS["side"], np.abs(n * v.dir_d).sum(axis=1))
+        sd2, sd2_b = _bracket(lambda n_, d_: -_dot(n_, d_), [n, v.dir_d], OPS["side"], np.abs(n * v.dir_d).sum(axis=1))
         sd, sd_b = np.where(kd, sd2, sd), np.where(kd, sd2_b, sd_b)
     side_doubt = y & (np.abs(sd) <= C_DECISION * sd_b)
     v.amb |= side_doubt
@@ -248,22 +236,22 @@ def _assignment(T, p, n, e2, idx, e1r, e1h, out, C):
     so_ok = np.zeros(N, bool)
     for flip in (1.0, -1.0):
         mag = np.abs(n) * ((1 + np.abs(p).max(axis=1)) * K_RAY)[:, None]
-        oq, ob = bracket(lambda p_, n_: sof(p_, n_, sgn * flip), [p, n], OPS["sh_o"], np.abs(p) + mag)
+        oq, ob = _bracket(lambda p_, n_: sof(p_, n_, sgn * flip), [p, n], OPS["sh_o"], np.abs(p) + mag)
         ok = SM._within(g["sh_o"], oq, ob, C["sh_o"])
         so_ok |= ok & ((flip > 0) | side_doubt)
         if flip > 0:
             v.ratio["sh_o"] = np.where(y & ~side_doubt, SM._ratio(g["sh_o"], oq, ob), 0.0)
     v.ok["sh_o"] = ~y | so_ok
     so = g["sh_o"]
-    hq, hb = bracket(lambda l_, o_: _unit(l_ - o_), [L, so], OPS["unit"], 1.0, [uL, None])
+    hq, hb = _bracket(lambda l_, o_: _unit(l_ - o_), [L, so], OPS["unit"], 1.0, [uL, None])
     banded("sh_d", "sh_d", g["sh_d"], hq, hb, y)
-    tq, tb = bracket(lambda l_, o_: np.sqrt(_dot(l_ - o_, l_ - o_)) * ONE_MINUS_SHADOW, [L, so], OPS["tmax"], None, [uL, None])
+    tq, tb = _bracket(lambda l_, o_: np.sqrt(_dot(l_ - o_, l_ - o_)) * ONE_MINUS_SHADOW, [L, so], OPS["tmax"], None, [uL, None])
     banded("sh_tmax", "tmax", tmax, tq, tb, y)
     # the density
     pq, pb = np.full(N, inv), np.full(N, EPS * inv)
     if kq.any():
         form = lambda p_, l_, n_, a_: _dot(l_ - p_, l_ - p_) / np.abs(cosf(p_, l_, n_)) / a_ * inv
-        fq, fb = bracket(form, [p, L, nl, area], OPS["pdf_quad"], None, [None, uL, None, None])
+        fq, fb = _bracket(form, [p, L, nl, area], OPS["pdf_quad"], None, [None, uL, None, None])
         pq, pb = np.where(kq, fq, pq), np.where(kq, fb, pb)
         edge = dist ** 2 / (np.abs(cos) + C_DECISION * cos_b) / area * inv * (1 - C["pdf"] * OPS["pdf_quad"] * EPS)
     if ks.any():

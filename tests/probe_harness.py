@@ -1,0 +1,79 @@
+"""What the GPU tests of the stage probes share (test_gpu_raycast, test_gpu_bsdf, test_gpu_surface, test_gpu_emitter): the
+contexts, the scenes on the device, the copy to the device, and the bit-for-bit comparison of a probe's columns with the CPU
+oracle's.  A test module keeps its own probe() call and its tests.  (A plain module: nothing of it runs at import, and the
+package is imported where a test first needs the device.)"""
+import functools
+
+import numpy as np
+
+SIZES = (1, 63, 64, 65, 257, 4099)   # one lane, around one wavefront, more than one workgroup, and no multiple of anything
+
+
+@functools.lru_cache(maxsize=None)
+def _tree(which):
+    from practical_path_guiding_lab_amd.sdtree import SDTree
+    return SDTree(0)
+
+
+def context():
+    """the one context that serves every scene (set_scene)"""
+    return _tree("scenes")
+
+
+def bare_context():
+    """a context that is never given a scene: pg_bsdf_probe needs none"""
+    return _tree("never a scene")
+
+
+@functools.lru_cache(maxsize=None)
+def scene(factory, name):
+    """WavefrontScene(factory(name)): made once per scene factory (the TM.scene, TS.scene, TE.scene of the model tests) and name"""
+    return wavefront(factory(name))
+
+
+def wavefront(sc):
+    from practical_path_guiding_lab_amd.render import WavefrontScene
+    return WavefrontScene(sc)
+
+
+_holds = {}   # context -> the WavefrontScene whose scene it holds
+
+
+def set_scene(ws, tree=None):
+    """-> the context (context(), or the caller's own) holding ws's scene: set again wherever the context was given another
+    scene since, which ws cannot know -- it only remembers the context it was last set in"""
+    tree = context() if tree is None else tree
+    if _holds.get(tree) is not ws:
+        ws._uploaded_to = None
+        ws._upload(tree)
+        _holds[tree] = ws
+    return tree
+
+
+def dev(a):
+    """a host array on the device (from a copy: contiguous, and writable whatever the caller's set is)"""
+    import torch
+    return torch.from_numpy(np.array(a)).cuda()
+
+
+def first(d, n):
+    """the first n lanes of every column of a dict, or of a sequence of columns"""
+    return {k: a[:n] for k, a in d.items()} if isinstance(d, dict) else [a[:n] for a in d]
+
+
+def same_bits(dev, ora, flags, fields, what, any_nan=True, missing=False):
+    """dev and ora, dicts of columns: the same columns, `flags` equal and `fields` the same bits.  any_nan: WHICH NaN a lane
+    holds may differ (0 / 0 is a negative quiet NaN on the host and a positive one on the device); where one side has a NaN
+    the other must have one.  missing: both sides may lack the same columns of flags and fields."""
+    assert set(dev) == set(ora)
+    assert missing or set(dev) == set(flags) | set(fields)
+    for k in [k for k in flags if k in dev]:
+        np.testing.assert_array_equal(dev[k], ora[k], err_msg="%s: %s" % (what, k))
+    for k in [k for k in fields if k in dev]:
+        a, b = dev[k], ora[k]
+        assert a.shape == b.shape and a.dtype == b.dtype, (what, k)
+        same = a.view(np.uint32) == b.view(np.uint32)
+        if any_nan:
+            same |= np.isnan(a) & np.isnan(b)
+        assert same.all(), "%s: %s differs on lanes %s, e.g. device %r oracle %r" % (
+            what, k, np.unique(np.nonzero(~same)[0])[:8], a[~same][:3], b[~same][:3])

@@ -71,12 +71,13 @@ def ulp(x):
         return np.spacing(np.abs(np.asarray(x, np.float64)).astype(np.float32)).astype(np.float64)
 
 
-def bracket(f, xs, ops, scale=None):
-    """q = f(*xs) and 2^-24 ops |q| + sum_j max |f(.. x_j +- ulp ..) - q|; xs: float64 arrays (n,) or (n, k) of float32 values"""
+def bracket(f, xs, ops, scale=None, steps=None, nan_is_inf=False):
+    """q = f(*xs) and 2^-24 ops |q| + sum_j max |f(.. x_j +- ulp ..) - q|; xs: float64 arrays (n,) or (n, k) of float32 values.
+    steps[j], where given, stands in the place of ulp(x_j); nan_is_inf: a bracket that is not a number comes back as inf"""
     q = f(*xs)
     b = EPS * ops * (np.abs(q) if scale is None else scale)
     for j, x in enumerate(xs):
-        h = ulp(x)
+        h = ulp(x) if steps is None or steps[j] is None else np.broadcast_to(steps[j], x.shape)
         cols = [()] if x.ndim == 1 else [(slice(None), k) for k in range(x.shape[1])]
         for c in cols:
             worst = 0.0
@@ -85,7 +86,7 @@ def bracket(f, xs, ops, scale=None):
                 y[c] = y[c] + sgn * h[c]
                 worst = np.maximum(worst, np.abs(f(*xs[:j], y, *xs[j + 1:]) - q))
             b = b + worst
-    return q, b
+    return q, np.nan_to_num(b, nan=np.inf) if nan_is_inf else b
 
 
 def _dot(a, b):

@@ -10,21 +10,14 @@ import pytest
 
 import bsdf_model as BM
 import bsdf_sets as BS
+import probe_harness as H
 import test_bsdf_model as TB
 
 pytestmark = pytest.mark.gpu
 
 
-@functools.lru_cache(maxsize=None)
-def context():
-    from practical_path_guiding_lab_amd.sdtree import SDTree
-    return SDTree(0)
-
-
 def probe(rows, idx, wi, wo, u, level=3):
-    import torch
-    dev = lambda a: torch.from_numpy(np.array(a)).cuda()   # (a copy: the sets are read-only)
-    out = context().bsdfProbe(dev(rows), dev(idx), dev(wi), dev(wo), dev(u), level)
+    out = H.bare_context().bsdfProbe(H.dev(rows), H.dev(idx), H.dev(wi), H.dev(wo), H.dev(u), level)
     return tuple(o.cpu().numpy() for o in out)
 
 
@@ -35,9 +28,8 @@ def device(name, level=3):
 
 
 def _same(dev, ora, what):
-    for k, a, b in zip(TB.NAMES, dev, ora):
-        assert a.shape == b.shape and a.dtype == b.dtype, (what, k)
-        np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32), err_msg="%s: %s" % (what, k))
+    """the seven outputs of the device and of the oracle: every bit, a NaN's included"""
+    H.same_bits(dict(zip(TB.NAMES, dev)), dict(zip(TB.NAMES, ora)), (), TB.NAMES, what, any_nan=False)
 
 
 @pytest.mark.parametrize("level", [0, 1, 2, 3])
@@ -51,7 +43,7 @@ def test_sizes_that_are_no_multiple_of_the_workgroup():
     idx, wi, wo, u = BS.get("uniform")
     ora = TB.oracle("uniform")
     for n in (1, 63, 64, 65, 255, 257, 4097):
-        _same(probe(rows, idx[:n], wi[:n], wo[:n], u[:n]), [a[:n] for a in ora], "uniform, %d lanes" % n)
+        _same(probe(rows, idx[:n], wi[:n], wo[:n], u[:n]), H.first(ora, n), "uniform, %d lanes" % n)
     one = rows[idx[:777]]   # a table of one row per lane, and a table of one row
     _same(probe(one, np.arange(777, dtype=np.int32), wi[:777], wo[:777], u[:777]), [a[:777] for a in ora], "a row per lane")
     k = int(idx[0])
@@ -88,7 +80,7 @@ def test_misuse_is_refused_with_a_message():
     import torch
     from practical_path_guiding_lab_amd import _native as N
     L = N.lib()
-    h = context()._h
+    h = H.bare_context()._h
     rows = torch.from_numpy(BS.table()[0]).cuda()
     n_mat = rows.shape[0]
     f3 = lambda: torch.full((16, 3), 0.5, dtype=torch.float32, device="cuda")

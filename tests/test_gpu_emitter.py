@@ -5,63 +5,35 @@ tests/test_emitter_model.py and on non-finite points and normals -- and against 
 directly, so that a change moving oracle and device together still fails a test.
 
 "Bit for bit" lets one thing differ: WHICH NaN a lane holds; where one side has a NaN the other must have one."""
-import functools
-
 import numpy as np
 import pytest
 
 import emitter_model as EM
+import probe_harness as H
 import test_emitter_model as TE
 import test_surface_model as TS
+from probe_harness import SIZES
 
 pytestmark = pytest.mark.gpu
 
-SIZES = (1, 63, 64, 65, 257, 4099)
 
-
-@functools.lru_cache(maxsize=None)
-def tree():
-    from practical_path_guiding_lab_amd.sdtree import SDTree
-    return SDTree(0)
-
-
-@functools.lru_cache(maxsize=None)
 def device(name):
-    from practical_path_guiding_lab_amd.render import WavefrontScene
-    return WavefrontScene(TE.scene(name))
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    return H.scene(TE.scene, name)
 
 
 def probe(ws, L):
     from oracle import pg_oracle as po
-    ws._uploaded_to = None      # (one context serves every scene of this module: the scene is set again)
-    out, flags = ws.emitter_probe(tree(), _dev(L["p"]), _dev(L["n"]), _dev(L["e"]))
+    out, flags = ws.emitter_probe(H.set_scene(ws), H.dev(L["p"]), H.dev(L["n"]), H.dev(L["e"]))
     return po.split_emitter(out.cpu().numpy(), flags.cpu().numpy())
 
 
 def probe_scene(sc, L):
-    from practical_path_guiding_lab_amd.render import WavefrontScene
-    return probe(WavefrontScene(sc), L)
+    return probe(H.wavefront(sc), L)
 
 
 def _same(dev, ora, what):
     from oracle import pg_oracle as po
-    assert set(dev) == set(ora)
-    for k in po.EMITTER_FLAGS:
-        np.testing.assert_array_equal(dev[k], ora[k], err_msg="%s: %s" % (what, k))
-    for k, _, _ in po.EMITTER_FIELDS:
-        a, b = dev[k], ora[k]
-        same = (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
-        assert same.all(), "%s: %s differs on lanes %s, e.g. device %r oracle %r" % (
-            what, k, np.unique(np.nonzero(~same)[0])[:8], a[~same][:3], b[~same][:3])
-
-
-def _first(L, n):
-    return {k: a[:n] for k, a in L.items()}
+    H.same_bits(dev, ora, po.EMITTER_FLAGS, [k for k, _, _ in po.EMITTER_FIELDS], what)
 
 
 @pytest.mark.parametrize("name", TE.SCENES)
@@ -70,7 +42,7 @@ def test_device_equals_oracle(name):
     assert L["p"].shape[0] == SIZES[-1]
     ora = TE.probe_oracle(TE.scene(name), L)
     for n in SIZES:
-        _same(probe(device(name), _first(L, n)), _first(ora, n), "%s n %d" % (name, n))
+        _same(probe(device(name), H.first(L, n)), H.first(ora, n), "%s n %d" % (name, n))
 
 
 def test_device_equals_oracle_on_the_known_answers():
@@ -94,7 +66,7 @@ def test_device_against_the_model(name):
     """levels 2 (veach-ajar), 3 (mixed, torus) and 0 (cornell-box, where the sphere branch is folded away)"""
     from oracle import pg_oracle as po
     assert po.feature_level(TE.scene(name)) == {"veach-ajar": 2, "mixed": 3, "torus": 3, "cornell-box": 0}[name]
-    L = _first(TE.broad(name), 2048)
+    L = H.first(TE.broad(name), 2048)
     TE.check(TE.tables(name), L, probe(device(name), L), name + " device")
 
 
@@ -113,7 +85,7 @@ def test_mis_consistency_through_the_surface_probe():
     import torch
     from oracle import pg_oracle as po
     name = "mixed"
-    L, T = _first(TE.broad(name), 2048), TE.tables(name)
+    L, T = H.first(TE.broad(name), 2048), TE.tables(name)
     ws = device(name)
     out = probe(ws, L)
     y = (out["need_shadow"] != 0) & (out["ds_delta"] == 0)
@@ -127,8 +99,8 @@ def test_mis_consistency_through_the_surface_probe():
         d = np.nan_to_num(d / t[:, None])
     n = p.shape[0]
     q = np.where(y, prim, 0).astype(np.int32)
-    s_out, s_flags = ws.surface_probe(tree(), _dev(q), _dev(L["p"]), _dev(d.astype(np.float32)), _dev(t.astype(np.float32)),
-                                      torch.zeros((n, 2), dtype=torch.float32, device="cuda"), _dev(L["p"]))
+    s_out, s_flags = ws.surface_probe(H.set_scene(ws), H.dev(q), H.dev(L["p"]), H.dev(d.astype(np.float32)), H.dev(t.astype(np.float32)),
+                                      torch.zeros((n, 2), dtype=torch.float32, device="cuda"), H.dev(L["p"]))
     hit = po.split_surface(s_out.cpu().numpy(), s_flags.cpu().numpy())
     fails, judged, between = EM.consistency(T, L["p"], L["e"], out, hit)
     fails = fails[y[fails]]
@@ -145,7 +117,7 @@ def test_composition_with_the_shadow_rays():
     L = {k: a for k, a in TE.broad(name).items() if k != "prim"}
     ws, sc = device(name), TE.scene(name)
     dev, ora = probe(ws, L), TE.probe_oracle(sc, L)
-    _, prim, _ = ws.intersect(tree(), _dev(dev["sh_o"]), _dev(dev["sh_d"]), _dev(dev["sh_tmax"]), any_hit=True)
+    _, prim, _ = ws.intersect(H.set_scene(ws), H.dev(dev["sh_o"]), H.dev(dev["sh_d"]), H.dev(dev["sh_tmax"]), any_hit=True)
     occluded = (prim.cpu().numpy() >= 0) & (dev["need_shadow"] != 0)
     occluded_o = (po.intersect(sc, ora["sh_o"], ora["sh_d"], ora["sh_tmax"])[1] >= 0) & (ora["need_shadow"] != 0)
     np.testing.assert_array_equal(occluded, occluded_o)
@@ -170,9 +142,7 @@ def test_misuse_is_refused_with_a_message():
     good = [p.data_ptr(), nrm.data_ptr(), e.data_ptr(), out.data_ptr(), flags.data_ptr(), None]
     bare = SDTree(0)
     refused(bare._h, 16, good, "pg_scene_set")          # no scene
-    tr, ws = SDTree(0), device("cornell-box")
-    ws._uploaded_to = None
-    ws._upload(tr)
+    tr = H.set_scene(device("cornell-box"), SDTree(0))     # (a context of its own, to refuse and to stay usable)
     assert L.pg_emitter_probe(tr._h, 16, *good) == 0
     for k in range(5):
         refused(tr._h, 16, good[:k] + [None] + good[k + 1:], "NULL")

@@ -5,17 +5,9 @@ profiles/bsdf/mutations.txt records: which check catches the error and by how mu
 
     python tools/bsdf_mutants.py > profiles/bsdf/mutations.txt      (a few numbers behind it: those mutants only)
 """
-import ctypes
-import os
-import shutil
-import subprocess
-import sys
-import tempfile
+import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
-
-import numpy as np  # noqa: E402
+import oracle_mutants as OM   # (puts the tree and tests/ on sys.path)
 
 import bsdf_model as BM  # noqa: E402
 import bsdf_sets as BS  # noqa: E402
@@ -41,27 +33,6 @@ MUTANTS = [
     ("Beckmann visible normals: the Newton steps left out", [("for (int i = 0; i < 3; ++i) {\n\t\tconst float slope = pgo_erfinv(x);", "for (int i = 0; i < 0; ++i) {\n\t\tconst float slope = pgo_erfinv(x);")]),
     ("the sampled slope not stretched back by alpha in x", [("const float rx = (cos_phi * sx - sin_phi * sy) * alpha;", "const float rx = (cos_phi * sx - sin_phi * sy);")]),
 ]
-ONLY = [int(a) for a in sys.argv[1:]]
-
-
-def build(tmp, number, edits):
-    d = os.path.join(tmp, "oracle%d" % number)   # (a directory of its own: the loader knows a library by its path)
-    os.makedirs(d)
-    for f in os.listdir(os.path.join(ROOT, "oracle")):
-        if f.endswith((".c", ".h")) or f == "Makefile":
-            shutil.copy(os.path.join(ROOT, "oracle", f), d)
-    p = os.path.join(d, "pg_oracle_render.c")
-    s = open(p).read()
-    for old, new in edits:
-        assert s.count(old) == 1, old
-        s = s.replace(old, new)
-    open(p, "w").write(s)
-    subprocess.run(["make", "-C", d, "-s"], check=True, stdout=subprocess.DEVNULL)
-    lib = ctypes.CDLL(os.path.join(d, "libpg_oracle.so"))
-    po._declare(lib)
-    return lib
-
-
 RESULTS = []   # (name, set checks failed, least and greatest worst ratio of them, greatest multiple of a density tolerance)
 
 
@@ -106,27 +77,17 @@ def main():
 # tests/test_bsdf_model.py: every input set at level 3 against the model (eval and sample outputs), and every density pair.
 # Tolerances of the density test: bin %.2e, mass %.2e.  The last three errors sit in a sampler alone: they move sampled
 # directions and leave pdf and weight consistent at the direction returned.  The summary at the end is computed from the run.""" % (TB.BIN_TOLERANCE, TB.MASS_TOLERANCE))
-    with tempfile.TemporaryDirectory() as tmp:
-        po.lib()
-        own = po._lib
-        if not ONLY:
-            report("the oracle as it is")
-        for number, (name, edits) in enumerate(MUTANTS):
-            if ONLY and number not in ONLY:
-                continue
-            po._lib = build(tmp, number, edits)
-            report(name)
-        po._lib = own
-    print("== summary")
+    for name in OM.each_oracle(MUTANTS):
+        report(name)
+    lines = []
     for name, checks, least, greatest, factor in RESULTS:
         what = []
         if checks:
             what.append("band checks fail in %d of %d, worst lane %.3g to %.3g brackets" % (checks, 2 * len(BS.SETS), least, greatest))
         if factor:
             what.append("density test fails, by up to %.1f times a tolerance" % factor)
-        print("   %-80s %s" % (name, "; ".join(what) if what else "NOTHING FAILS" + ("" if name == "the oracle as it is" else ": ESCAPES")))
-    escaped = [r[0] for r in RESULTS if not r[1] and not r[4] and r[0] != "the oracle as it is"]
-    print("   escaped: %s" % (", ".join(escaped) if escaped else "none"))
+        lines.append((name, "; ".join(what)))
+    OM.summary(lines, width=80)
 
 
 if __name__ == "__main__":

@@ -9,23 +9,12 @@ the error.
                                                                            quantity and set, C = 4 x worst, ambiguous shares,
                                                                            the density differences behind the tolerances)
 """
-import ctypes
-import io
-import os
-import shutil
-import subprocess
-import sys
-import tempfile
-from contextlib import redirect_stdout
+import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
-
-import numpy as np  # noqa: E402
+import oracle_mutants as OM   # (puts the tree and tests/ on sys.path)
 
 import emitter_model as EM  # noqa: E402
 import test_emitter_model as TE  # noqa: E402
-from oracle import pg_oracle as po  # noqa: E402
 
 SHADOW = "*sh_o = so; *sh_d = vdivs(sd, sdist); *sh_tmax = sdist * (1.0f - SHADOW_EPS_F);"
 # name, [(text of oracle/pg_oracle_render.c, its replacement[, how often the text occurs: 1])]
@@ -51,9 +40,6 @@ MUTANTS = [
     ("the small-angle switch inverted", [("if (sin_max2 > 0.00068523f) {", "if (!(sin_max2 > 0.00068523f)) {")]),
     ("the facing test dropped: a light seen from behind is sampled", [("if (dp < 0.0f) pdf = is_sphere", "if (dp != 0.0f) pdf = is_sphere")]),
 ]
-ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
-ONLY = [int(a) for a in ARGS]
-
 TESTS = [(name, getattr(TE, name), args) for name, args in (
     ("test_oracle_against_the_model", TE.SCENES), ("test_mis_consistency", TE.SCENES), ("test_shadow_rays", TE.SCENES),
     ("test_choice_of_emitter", (1, 2, 3, 7)), ("test_quad_light_at_grazing_incidence", None),
@@ -61,71 +47,10 @@ TESTS = [(name, getattr(TE, name), args) for name, args in (
     ("test_directional_light", None), ("test_a_scene_without_emitters_gives_zero_lanes", None),
     ("test_oracle_returns_for_non_finite_points_and_normals", ("mixed", "torus", "cornell-box")),
     ("test_sampling_density", TE.PAIRS))]
-
-
-def build(tmp, number, edits):
-    d = os.path.join(tmp, "oracle%d" % number)   # (a directory of its own: the loader knows a library by its path)
-    os.makedirs(d)
-    for f in os.listdir(os.path.join(ROOT, "oracle")):
-        if f.endswith((".c", ".h")) or f == "Makefile":
-            shutil.copy(os.path.join(ROOT, "oracle", f), d)
-    p = os.path.join(d, "pg_oracle_render.c")
-    s = open(p).read()
-    for old, new, *times in edits:
-        assert s.count(old) == (times[0] if times else 1), old
-        s = s.replace(old, new)
-    open(p, "w").write(s)
-    subprocess.run(["make", "-C", d, "-s"], check=True, stdout=subprocess.DEVNULL)
-    lib = ctypes.CDLL(os.path.join(d, "libpg_oracle.so"))
-    po._declare(lib)
-    return lib
-
-
-RESULTS = []
-
-
-def report(name):
-    failed, ran = [], 0
-    for test, fn, args in TESTS:
-        for a in args or (None,):
-            ran += 1
-            try:
-                with redirect_stdout(io.StringIO()):
-                    fn(*(() if a is None else (a,)))
-            except Exception as e:   # (an AssertionError, or whatever a copy's nonsense raises further down)
-                first = (str(e) or type(e).__name__).split("\n")[0]
-                failed.append(("%s[%s]" % (test, a) if a is not None else test, first[:150]))
-    print("== %s" % name)
-    for t, why in failed:
-        print("   FAILS %-75s %s" % (t, why))
-    if not failed:
-        print("   all %d tests pass" % ran)
-    RESULTS.append((name, [t for t, _ in failed], ran))
-
-
-def mutations():
-    print("""# profiles/emitter/mutations.txt -- can the emitter-sampling tests fail?  Written by: python tools/emitter_mutants.py
+HEADER = """# profiles/emitter/mutations.txt -- can the emitter-sampling tests fail?  Written by: python tools/emitter_mutants.py
 # One deliberate error at a time in a scratch copy of oracle/pg_oracle_render.c (never committed, never built for the device),
 # then every test of tests/test_emitter_model.py against that copy: the failing tests and the first line of each failure.
-# The summary at the end is computed from the run.""")
-    with tempfile.TemporaryDirectory() as tmp:
-        po.lib()
-        own = po._lib
-        if not ONLY:
-            report("the oracle as it is")
-        for number, (name, edits) in enumerate(MUTANTS):
-            if ONLY and number not in ONLY:
-                continue
-            po._lib = build(tmp, number, edits)
-            report(name)
-        po._lib = own
-    print("== summary")
-    for name, failed, ran in RESULTS:
-        print("   %-60s %s" % (name, ("caught by %d of %d tests: %s" % (len(failed), ran, ", ".join(failed[:3]) + (" ..." if len(failed) > 3 else "")))
-                               if failed else "NOTHING FAILS" + ("" if name == "the oracle as it is" else ": ESCAPES")))
-    escaped = [r[0] for r in RESULTS if not r[1] and r[0] != "the oracle as it is"]
-    print("   escaped: %s" % (", ".join(escaped) if escaped else "none"))
-
+# The summary at the end is computed from the run."""
 
 def band():
     print("""# profiles/emitter/band.txt -- the band of tests/emitter_model.py measured on the CPU oracle.  Written by:
@@ -147,9 +72,7 @@ def band():
             label, amb.shape[0], 100 * amb.mean(), own.sum(), 100 * amb[~own].mean(), "  ".join("%s %.3f" % (k, r.max()) for k, r in sorted(ratio.items()))))
         for k, r in ratio.items():
             worst[k] = max(worst.get(k, 0.0), float(r.max()))
-    print("worst ratio, C = 4 x it, and the committed BAND_C:")
-    for k in sorted(worst):
-        print("   %-8s %.3f   %.2f   %.2f" % (k, worst[k], 4 * worst[k], EM.BAND_C[k]))
+    OM.worst_ratios(worst, EM.BAND_C)
     print("the sampling density at the committed grid (%d x %d samples, %d x %d bins -- %s --, %d^2 midpoints per bin): worst bin difference, "
           "|valid fraction - the model's mass|" % (TE.GRID, TE.GRID, TE.BINS_C, TE.BINS_P, ", ".join("%s: %d x %d over the exact extent" % (k, v[0], v[1]) for k, v in TE.PAIR_BINS.items()), TE.SUB))
     for pair in TE.PAIRS:
@@ -157,5 +80,6 @@ def band():
         print("   %-26s %.3e   %.3e   twice that: %.2e  %.2e   committed tolerances: %.2e  %.2e" % (
             pair, a, b, 2 * a, 2 * b, TE.BIN_TOLERANCE[pair], TE.MASS_TOLERANCE[pair]))
 
+
 if __name__ == "__main__":
-    band() if "--band" in sys.argv else mutations()
+    OM.main(HEADER, MUTANTS, TESTS, band)

@@ -8,25 +8,15 @@ the error.
     python tools/surface_mutants.py --band > profiles/surface/band.txt    (the oracle as it is: worst |difference| / bracket per
                                                                            quantity and set, C = 4 x worst, ambiguous shares)
 """
-import ctypes
-import io
-import os
-import shutil
-import subprocess
-import sys
-import tempfile
-from contextlib import redirect_stdout
+import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
-
-import numpy as np  # noqa: E402
+import oracle_mutants as OM   # (puts the tree and tests/ on sys.path)
 
 import surface_model as SM  # noqa: E402
 import test_surface_model as TS  # noqa: E402
 from oracle import pg_oracle as po  # noqa: E402
 
-# name, [(text of oracle/pg_oracle_render.c, its replacement)]: every text occurs exactly once
+# name, [(text of oracle/pg_oracle_render.c, its replacement[, how often the text occurs: 1])]
 MUTANTS = [
     ("bu and bv swapped in the normal blend", [("vscale(ld3(Nn + 3), u)), vscale(ld3(Nn + 6), v));", "vscale(ld3(Nn + 3), v)), vscale(ld3(Nn + 6), u));")]),
     # (blending the vertices' uv and the affine to_uv commute: taking one before the other is the same function.  The order
@@ -47,9 +37,6 @@ MUTANTS = [
     ("the quad's pdf by area: 1 / A in place of d^2 / (cos A)", [("pdf = d2 / (fabsf(dp) * Q[14]);", "pdf = 1.0f / Q[14];")]),
     ("a left-handed frame (t negated)", [("*t = V(b, sign + (n.y * n.y) * a, -n.y);", "*t = V(-b, -(sign + (n.y * n.y) * a), n.y);")]),
 ]
-ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
-ONLY = [int(a) for a in ARGS]
-
 TESTS = [(name, getattr(TS, name), args) for name, args in (
     ("test_oracle_against_the_model", TS.SCENES), ("test_the_next_bounce_finds_the_same_normal", TS.SCENES),
     ("test_bitmap_known_answers", None), ("test_texture_coordinates_on_the_wrap_negative_huge_and_not_finite", None),
@@ -58,71 +45,10 @@ TESTS = [(name, getattr(TS, name), args) for name, args in (
     ("test_sphere_head_on_and_grazing", None), ("test_quad_emitter_at_grazing_incidence", None),
     ("test_sphere_emitter_around_the_cap_limit", None),
     ("test_oracle_returns_for_non_finite_and_degenerate_hits", ("veach-ajar", "mixed", "veach-mis")))]
-
-
-def build(tmp, number, edits):
-    d = os.path.join(tmp, "oracle%d" % number)   # (a directory of its own: the loader knows a library by its path)
-    os.makedirs(d)
-    for f in os.listdir(os.path.join(ROOT, "oracle")):
-        if f.endswith((".c", ".h")) or f == "Makefile":
-            shutil.copy(os.path.join(ROOT, "oracle", f), d)
-    p = os.path.join(d, "pg_oracle_render.c")
-    s = open(p).read()
-    for old, new in edits:
-        assert s.count(old) == 1, old
-        s = s.replace(old, new)
-    open(p, "w").write(s)
-    subprocess.run(["make", "-C", d, "-s"], check=True, stdout=subprocess.DEVNULL)
-    lib = ctypes.CDLL(os.path.join(d, "libpg_oracle.so"))
-    po._declare(lib)
-    return lib
-
-
-RESULTS = []
-
-
-def report(name):
-    failed, ran = [], 0
-    for test, fn, args in TESTS:
-        for a in args or (None,):
-            ran += 1
-            try:
-                with redirect_stdout(io.StringIO()):
-                    fn(*(() if a is None else (a,)))
-            except AssertionError as e:
-                first = str(e).split("\n")[0]
-                failed.append(("%s[%s]" % (test, a) if a else test, first[:150]))
-    print("== %s" % name)
-    for t, why in failed:
-        print("   FAILS %-75s %s" % (t, why))
-    if not failed:
-        print("   all %d tests pass" % ran)
-    RESULTS.append((name, [t for t, _ in failed], ran))
-
-
-def mutations():
-    print("""# profiles/surface/mutations.txt -- can the surface tests fail?  Written by: python tools/surface_mutants.py
+HEADER = """# profiles/surface/mutations.txt -- can the surface tests fail?  Written by: python tools/surface_mutants.py
 # One deliberate error at a time in a scratch copy of oracle/pg_oracle_render.c (never committed, never built for the device),
 # then every test of tests/test_surface_model.py against that copy: the failing tests and the first line of each failure.
-# The summary at the end is computed from the run.""")
-    with tempfile.TemporaryDirectory() as tmp:
-        po.lib()
-        own = po._lib
-        if not ONLY:
-            report("the oracle as it is")
-        for number, (name, edits) in enumerate(MUTANTS):
-            if ONLY and number not in ONLY:
-                continue
-            po._lib = build(tmp, number, edits)
-            report(name)
-        po._lib = own
-    print("== summary")
-    for name, failed, ran in RESULTS:
-        print("   %-60s %s" % (name, ("caught by %d of %d tests: %s" % (len(failed), ran, ", ".join(failed[:3]) + (" ..." if len(failed) > 3 else "")))
-                               if failed else "NOTHING FAILS" + ("" if name == "the oracle as it is" else ": ESCAPES")))
-    escaped = [r[0] for r in RESULTS if not r[1] and r[0] != "the oracle as it is"]
-    print("   escaped: %s" % (", ".join(escaped) if escaped else "none"))
-
+# The summary at the end is computed from the run."""
 
 def band():
     print("""# profiles/surface/band.txt -- the band of tests/surface_model.py measured on the CPU oracle.  Written by:
@@ -146,10 +72,8 @@ def band():
                                                            "  ".join("%s %.3f" % (k, v.max()) for k, v in sorted(ratio.items()))))
         for k, v in ratio.items():
             worst[k] = max(worst.get(k, 0.0), float(v.max()))
-    print("worst ratio, C = 4 x it, and the committed BAND_C:")
-    for k in sorted(worst):
-        print("   %-8s %.3f   %.2f   %.2f" % (k, worst[k], 4 * worst[k], SM.BAND_C[k]))
+    OM.worst_ratios(worst, SM.BAND_C)
 
 
 if __name__ == "__main__":
-    band() if "--band" in sys.argv else mutations()
+    OM.main(HEADER, MUTANTS, TESTS, band)
