@@ -63,6 +63,16 @@ class pg_bounce_args(C.Structure):  # include/pgsd_bounce.h
         "dir_io", "select_out", "fraction_out", "pdf_nee_out", "pdf_out", "L_dir_out", "L_mean_out")]
 
 
+class pg_resample_params(C.Structure):  # include/pg_resample.h
+    _fields_ = [("candidates", C.c_uint32), ("alpha", C.c_float), ("delta", C.c_float), ("reserved", C.c_uint32)]
+
+
+class pg_resample_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in (
+        "p", "normal", "active", "rng_state", "rng_inc", "dir_out", "weight_out", "target_out", "source_out", "index_out",
+        "cand_dir_out", "cand_target_out", "cand_source_out")]
+
+
 class pg_tree_sizes(C.Structure):
     _fields_ = [("n_kd", C.c_uint64), ("n_quad", C.c_uint64), ("n_roots", C.c_uint64)]
 
@@ -130,6 +140,7 @@ ABI_VERSION = 6  # PGSD_ABI_VERSION of include/pgsd.h these bindings match
 PG_FRACTION_LOSS_KL, PG_FRACTION_LOSS_VARIANCE = 0, 1
 PG_TARGET_SECOND_MOMENT = 1
 PG_BOUNCE_NONE, PG_BOUNCE_PDF, PG_BOUNCE_SAMPLE, PG_BOUNCE_CHOOSE = 0, 1, 2, 3
+PG_RESAMPLE_MAX_CANDIDATES, PG_RESAMPLE_NONE = 64, 0xFFFFFFFF
 
 V, U64, I32, U32, F32, P = C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_float, C.POINTER
 _RR = [V, U64, V, V, V, V, P(pg_rr_params), V, V, V, V, V, V, V]  # pg_radiance_rr and pg_irradiance_rr
@@ -199,16 +210,26 @@ SURFACE = {
 RESTYPES = {"pg_last_error": C.c_char_p}  # (pg_abi_version returns the c_int of all the others: it only has no context to fail on)
 EXPORTS, EXPORTS_WARP, EXPORTS_FRACTION, EXPORTS_TARGET, EXPORTS_RADIANCE, EXPORTS_BOUNCE, EXPORTS_IRRADIANCE = (
     tuple(entry_points) for entry_points in SURFACE.values())
+# Entry points of the same library whose headers are not include/pgsd*.h: beside SURFACE, not in it, because the ABI tests pin
+# SURFACE to that pattern and to its count.  lib() binds them after SURFACE, source_hash() hashes their headers
+# after SURFACE's; their own test files hold them to the header and the two builds.
+SURFACE_EXTRA = {
+    "pg_resample.h": {  # product guiding for diffuse surfaces: resampled importance sampling of cosine and tree candidates
+        "pg_resample_cosine": [V, U64, P(pg_resample_params), P(pg_resample_args), V],
+    },
+}
+(EXPORTS_RESAMPLE,) = (tuple(entry_points) for entry_points in SURFACE_EXTRA.values())
 
 
 def source_hash() -> str:
-    """sha256 (16 hex digits) over the library's sources (csrc/*.hip, csrc/*.hpp, then the headers of SURFACE in its order):
+    """sha256 (16 hex digits) over the library's sources (csrc/*.hip, csrc/*.hpp, then the headers of SURFACE in its order, then
+    those of SURFACE_EXTRA):
     names the code a profile was taken of (profiles/pmc_traffic.json) so that bench.py never pairs old counters with new kernels."""
     import glob
     import hashlib
     h = hashlib.sha256()
     files = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
-    files += [os.path.join(os.path.dirname(_PKG), "include", header) for header in SURFACE]
+    files += [os.path.join(os.path.dirname(_PKG), "include", header) for header in list(SURFACE) + list(SURFACE_EXTRA)]
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
@@ -247,7 +268,7 @@ def lib() -> C.CDLL:
     if L.pg_abi_version() != ABI_VERSION:  # (a library left over from an older build: its structs have other layouts)
         raise ImportError(f"{LIB_PATH} has ABI version {L.pg_abi_version()}, these bindings are written for {ABI_VERSION}: "
                           "rebuild it with `python -c 'import __graft_entry__ as g; g.build()'`")
-    for entry_points in SURFACE.values():
+    for entry_points in list(SURFACE.values()) + list(SURFACE_EXTRA.values()):
         for name, argtypes in entry_points.items():
             fn = getattr(L, name)  # (a missing symbol is an AttributeError here)
             fn.argtypes = list(argtypes)
