@@ -716,6 +716,61 @@ int pg_surface_probe(pg_context *ctx, uint64_t n, const int32_t *d_prim, const f
 int pg_emitter_probe(pg_context *ctx, uint64_t n, const float *d_p, const float *d_n, const float *d_e, float *d_out,
                      int32_t *d_flags, void *stream);
 
+/* The renderer's bookkeeping of one path vertex by itself, for tests: lane i goes through the very device function the render
+ * kernels call once a vertex's surface, emitter sample, BSDF sample and SD-tree answers are known (stage_b of
+ * csrc/pg_render_stages.hpp) -- the emitter sample's MIS weight against the mixture pdf frac * bsdf + (1 - frac) * tree, the
+ * radiance add, the BSDF re-evaluated at a direction the SD-tree proposed, woPdf and the BSDF weight it overwrites, the record
+ * entry, ior, the throughput, Russian roulette and the spawned ray -- as a kernel of feature level `level` (0..3) runs it.
+ * Needs no scene: what the earlier stages and the SD-tree give a vertex comes in as columns (pg_vertex_lanes; a 3-vector
+ * column holds lane i at [3 i ..]), the material table as in pg_bsdf_probe (read only where PG_VERTEX_SMP_TREE is set, and
+ * not at level 0, which takes the lane's reflectance as a two-sided diffuse material).
+ * flags: the lane's class as the stages before set it -- */
+#define PG_VERTEX_VALID 1u        /* the ray hit something; only such a lane is recorded */
+#define PG_VERTEX_ACTIVE_NEXT 2u  /* the path may go on (depth + 1 < max_depth and valid) */
+#define PG_VERTEX_DS_DELTA 16u    /* the emitter sample came from a delta light: MIS weight 1 at level 3 where it is live */
+#define PG_VERTEX_DELTA 32u       /* the BSDF sample is a delta lobe (handed on in delta) */
+#define PG_VERTEX_DO_MIS 64u      /* woPdf is the mixture, and the BSDF weight value / woPdf */
+#define PG_VERTEX_SMP_TREE 128u   /* wo came from the SD-tree: the BSDF is evaluated at it */
+#define PG_VERTEX_NEE_LIVE 512u   /* the emitter sample can contribute: em_w, bv_em, bp_em, ds_pdf are read */
+#define PG_VERTEX_HAS_LE 1024u    /* emitted radiance reached the path here: Le is read */
+/* (other bits are ignored.)  Call parameters: frac (the BSDF sampling fraction), guided (the mixture is in use), record and
+ * store_nee (the record entry is written; it holds the emitter sample's luminance), rr_depth (roulette from that depth on). */
+typedef struct pg_vertex_lanes {  /* device pointers, n lanes each */
+	const float *thr, *L, *ior;            /* the path's state: float[3 n], float[3 n], float[n] */
+	const uint32_t *depth, *flags;         /* uint32[n] each */
+	const float *Le;                       /* float[3 n] */
+	const float *p, *n, *ng, *wi, *refl;   /* float[3 n] each: the vertex, shading and geometric normal, -ray direction in the
+	                                          shading frame, the reflectance the surface left (a texture's colour) */
+	const int32_t *mat;                    /* int32[n]: row of the material table (checked on the host) */
+	const float *em_w, *bv_em, *bp_em, *ds_pdf; /* float[3 n], float[3 n], float[n], float[n]: the emitter sample's radiance /
+	                                          pdf as if unoccluded, the BSDF value and pdf towards it, its solid-angle density */
+	const float *bsdf_w, *bsdf_pdf, *eta;  /* float[3 n], float[n], float[n]: the BSDF sample */
+	const float *wo, *pdf_nee, *pdf_tree;  /* float[3 n], float[n], float[n]: the continuation direction (world), the SD-tree's
+	                                          pdf of the emitter direction and of wo */
+	const int32_t *occluded;               /* int32[n]: the shadow ray found an occluder */
+	const uint64_t *rng_state, *rng_inc;   /* uint64[n] each: the lane's sampler, as pg_sample takes it */
+} pg_vertex_lanes;
+typedef struct pg_vertex_out {    /* device pointers */
+	int32_t *go;                           /* int32[n]: 1 where the path continues */
+	float *thr, *L, *ior, *ray_o, *ray_d, *prev_pdf; /* float[3 n], float[3 n], float[n], float[3 n], float[3 n], float[n]: the
+	                                          state the next bounce reads (prev_pdf = woPdf) and the spawned ray */
+	int32_t *delta;                        /* int32[n] */
+	uint64_t *rng_state;                   /* uint64[n]: the sampler after the roulette's one draw */
+	/* the record entry, planes of stride n (a channel c of lane i at [c n + i]): ray_of[i] = i, or 0xffffffff for a lane that
+	 * is not valid, written when `record`; the others are written for a recorded lane only (record and PG_VERTEX_VALID) and
+	 * keep what they held otherwise -- the BSDF weight, the throughput before it is multiplied, L after the add, the luminance
+	 * of the emitter sample's share over the throughput (0 unless store_nee), woPdf */
+	uint32_t *ray_of;
+	float *r_bsdf, *r_tb, *r_tr, *r_nee, *r_wp; /* float[3 n], float[3 n], float[3 n], float[n], float[n] */
+} pg_vertex_out;
+/* Any float is safe in any column.  n = 0 does nothing; n > 2^20, a level outside 0..3, n_mat outside 1..65536, a table that
+ * fails the material-row checks of pg_scene_set_ex, a row number outside the table and a NULL pointer (the structs', or any
+ * of their members) are refused.  Synchronises the stream (before reading the table and the row numbers back, and after the
+ * kernel). */
+int pg_vertex_probe(pg_context *ctx, uint64_t n, uint64_t n_mat, const float *d_materials, int32_t level,
+                    const pg_vertex_lanes *lanes, float frac, int32_t guided, int32_t record, int32_t store_nee, int32_t rr_depth,
+                    const pg_vertex_out *out, void *stream);
+
 /* Per-kernel device time of pg_render_pass, measured with HIP events recorded on the launch
  * stream around each kernel (off by default).  pg_read_kernel_timing synchronises. */
 typedef struct pg_kernel_timing {

@@ -660,6 +660,66 @@ def emitter_probe(scene_obj, p, nrm, e, level=None):
     return split_emitter(out, flags)
 
 
+# pgo_vertex_lanes and pgo_vertex_out of pg_oracle_render.h, in the structs' order: (column, dtype, components per lane)
+VERTEX_LANES = (("thr", np.float32, 3), ("L", np.float32, 3), ("ior", np.float32, 1), ("depth", np.uint32, 1), ("flags", np.uint32, 1),
+                ("Le", np.float32, 3), ("p", np.float32, 3), ("n", np.float32, 3), ("ng", np.float32, 3), ("wi", np.float32, 3),
+                ("refl", np.float32, 3), ("mat", np.int32, 1), ("em_w", np.float32, 3), ("bv_em", np.float32, 3),
+                ("bp_em", np.float32, 1), ("ds_pdf", np.float32, 1), ("bsdf_w", np.float32, 3), ("bsdf_pdf", np.float32, 1),
+                ("eta", np.float32, 1), ("wo", np.float32, 3), ("pdf_nee", np.float32, 1), ("pdf_tree", np.float32, 1),
+                ("occluded", np.int32, 1), ("rng_state", np.uint64, 1), ("rng_inc", np.uint64, 1))
+# (..., planar: the record planes hold channel c of lane i at [c, i])
+VERTEX_OUT = (("go", np.int32, 1, False), ("thr", np.float32, 3, False), ("L", np.float32, 3, False), ("ior", np.float32, 1, False),
+              ("ray_o", np.float32, 3, False), ("ray_d", np.float32, 3, False), ("prev_pdf", np.float32, 1, False),
+              ("delta", np.int32, 1, False), ("rng_state", np.uint64, 1, False), ("ray_of", np.uint32, 1, True),
+              ("r_bsdf", np.float32, 3, True), ("r_tb", np.float32, 3, True), ("r_tr", np.float32, 3, True),
+              ("r_nee", np.float32, 1, True), ("r_wp", np.float32, 1, True))
+VERTEX_RECORD_FILL = {"ray_of": 0xFFFFFFFE, "r_bsdf": -7.0, "r_tb": -7.0, "r_tr": -7.0, "r_nee": -7.0, "r_wp": -7.0}   # what an unwritten record entry holds
+F_VALID, F_ACTIVE_NEXT, F_DS_DELTA, F_DELTA, F_DO_MIS, F_SMP_TREE, F_NEE_LIVE, F_HAS_LE = 1, 2, 16, 32, 64, 128, 512, 1024
+
+
+def vertex_lanes(lanes):
+    """the columns of VERTEX_LANES out of a dict, contiguous and of their types -> (n, [arrays in the struct's order])"""
+    n = np.asarray(lanes["flags"]).reshape(-1).shape[0]
+    cols = [np.ascontiguousarray(lanes[k], t).reshape((n, w) if w > 1 else (n,)) for k, t, w in VERTEX_LANES]
+    return n, cols
+
+
+def vertex_outputs(n):
+    """fresh output columns of VERTEX_OUT; the record planes filled with VERTEX_RECORD_FILL, so that what was not written shows"""
+    out = {}
+    for k, t, w, plane in VERTEX_OUT:
+        shape = ((w, n) if plane else (n, w)) if w > 1 else (n,)
+        out[("rng_out" if k == "rng_state" else k)] = np.full(shape, VERTEX_RECORD_FILL.get(k, 0), t)
+    return out
+
+
+def vertex_probe(materials, lanes, level, frac, guided, record, store_nee, rr_depth):
+    """pgo_vertex_probe: the bookkeeping of one path vertex (vertex_bookkeeping of pg_oracle_render.c, which the render pass
+    calls) over arrays.  materials (n_mat,16); lanes: dict of the columns VERTEX_LANES -> dict of the columns VERTEX_OUT (the
+    advanced sampler state as "rng_out")."""
+    lb = lib()
+
+    class Lanes(C.Structure):
+        _fields_ = [(k, _P) for k, _, _ in VERTEX_LANES]
+
+    class Out(C.Structure):
+        _fields_ = [(k, _P) for k, _, _, _ in VERTEX_OUT]
+
+    lb.pgo_vertex_probe.argtypes = [C.c_size_t, C.c_size_t, _P, C.c_int, C.POINTER(Lanes), C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.POINTER(Out)]
+    lb.pgo_vertex_probe.restype = None
+    m = np.ascontiguousarray(materials, np.float32).reshape(-1, 16)
+    n, cols = vertex_lanes(lanes)
+    idx = cols[[k for k, _, _ in VERTEX_LANES].index("mat")]
+    assert 0 <= int(level) <= 3 and (n == 0 or (idx.min() >= 0 and idx.max() < m.shape[0]))
+    out = vertex_outputs(n)
+    li = Lanes(*[_ptr(c) for c in cols])
+    oo = Out(*[_ptr(out["rng_out" if k == "rng_state" else k]) for k, _, _, _ in VERTEX_OUT])
+    lb.pgo_vertex_probe(n, m.shape[0], _ptr(m), int(level), C.byref(li), float(frac), int(bool(guided)), int(bool(record)),
+                        int(bool(store_nee)), int(rr_depth), C.byref(oo))
+    return out
+
+
 def render_pass(pair: "OracleSDTreePair", quads, cam, max_depth, rr_depth, iteration, is_final, seed, spp=1,
                 store_nee=True, bsdf_sampling_fraction=0.5, sumL=None, sumL2=None, spheres=None, materials=None,
                 boxes=None):

@@ -1025,6 +1025,159 @@ void pgo_bsdf_probe(size_t n, const float *materials, const int32_t *material_in
 	}
 }
 
+/* ---- the bookkeeping of one path vertex (:247-261, 302-311, 318-346, 352-378): everything a bounce does with what ray
+ * casting, the surface, emitter sampling, the BSDF and the SD-tree have given it.  The device's stage_b<>
+ * (csrc/pg_render_stages.hpp), operation by operation; the lane loop of pgo_render_pass_scene and pgo_vertex_probe call it. ---- */
+typedef struct {
+	v3 p, n, ng, wi;       /* the vertex, its shading and geometric normal, -ray direction in the shading frame */
+	v3 Le;                 /* emitted radiance that reached the path here, with its MIS weight and the throughput (:189-200) */
+	v3 em_w, bv_em;        /* the emitter sample: radiance / ds_pdf as if unoccluded, the BSDF towards it */
+	v3 bsdf_w, wo;         /* the BSDF sample's weight; the continuation direction (the tree's on a PGO_F_SMP_TREE lane) */
+	float ds_pdf, bp_em, bsdf_pdf, eta;
+	float pdf_nee, pdf_tree; /* the SD-tree's pdf of the emitter direction and of wo (1 where nobody asked) */
+	uint32_t flags;        /* PGO_F_* */
+	int occluded;          /* the shadow ray found an occluder */
+} vertex_in;
+
+typedef struct {
+	int recorded;
+	v3 bsdf_weight, thr, L, nee; /* :329, 331, 333, 336 */
+	float nee_lum, woPdf;        /* luminance of the NaN-scrubbed nee (:467, 471); :340 */
+} vertex_rec;
+
+/* the emitter sample can contribute: its BSDF value is not zero, or its weight is not finite (the device's F_NEE_LIVE) */
+static int vertex_nee_live(int active_em, v3 bv_em, v3 em_w)
+{
+	return active_em && !(bv_em.x == 0.0f && bv_em.y == 0.0f && bv_em.z == 0.0f && isfinite(em_w.x) && isfinite(em_w.y) && isfinite(em_w.z));
+}
+
+/* returns whether the path continues; its state for the next bounce in thr, L, ior, ray_o, ray_d, prev_pdf, delta_out.
+ * mt: the vertex's material as a kernel of feature level `level` reads it (read on PGO_F_SMP_TREE lanes only) */
+static int vertex_bookkeeping(const vertex_in *A, const material *mt, int level, float f, int guided, int record, int store_nee,
+                              int rr_depth, uint32_t depth, pgo_pcg32 *rng, v3 *thr_io, v3 *L_io, float *ior_io, vertex_rec *rec,
+                              v3 *ray_o, v3 *ray_d, float *prev_pdf, int *delta_out)
+{
+	v3 thr = *thr_io, L = *L_io;
+	float ior = *ior_io;
+	const int valid = (A->flags & PGO_F_VALID) != 0u;
+	int active_next = (A->flags & PGO_F_ACTIVE_NEXT) != 0u;
+	const int ds_delta = (A->flags & PGO_F_DS_DELTA) != 0u, delta = (A->flags & PGO_F_DELTA) != 0u;
+	const int do_mis = (A->flags & PGO_F_DO_MIS) != 0u, smp_tree = (A->flags & PGO_F_SMP_TREE) != 0u;
+	const int nee_live = (A->flags & PGO_F_NEE_LIVE) != 0u;
+	const v3 em_weight = (A->occluded || !nee_live) ? V(0, 0, 0) : A->em_w;
+	/* ---- :223-256 NEE MIS against the mixture pdf ---- */
+	const float pdf_diffuse = 1.0f; /* :222-241, SURVEY A12 */
+	const float sdtree_pdf_em = A->pdf_nee;
+	/* a lane without a live emitter sample: every factor is zero or multiplies zero */
+	const float bp_em = nee_live ? A->bp_em : 0.0f, ds_pdf = nee_live ? A->ds_pdf : 0.0f;
+	const v3 bv_em = nee_live ? A->bv_em : V(0, 0, 0);
+	float surface_pdf_em = f * bp_em + ((1.0f - f) * sdtree_pdf_em) * pdf_diffuse;
+	if (!guided) surface_pdf_em = bp_em;
+	const float mis_em = (level >= 3 && ds_delta && nee_live) ? 1.0f : mis_weight(ds_pdf, surface_pdf_em); /* :253 */
+	const v3 Lr_dir = vmul(vmul(vscale(thr, mis_em), bv_em), em_weight);
+	const v3 Le = (A->flags & PGO_F_HAS_LE) ? A->Le : V(0, 0, 0);
+	L = vadd(L, vadd(Le, Lr_dir)); /* :261 */
+	/* ---- :302-311 ---- */
+	v3 bsdf_weight = A->bsdf_w;
+	float bsdf_pdf = A->bsdf_pdf;
+	v3 bsdf_value = vscale(bsdf_weight, bsdf_pdf);
+	float woPdf = bsdf_pdf;
+	const v3 wo_world = A->wo;
+	if (smp_tree) { /* :302-304 */
+		frame fr;
+		fr.n = A->n;
+		frame_from_normal(A->n, &fr.s, &fr.t);
+		const v3 wo_local = to_local(&fr, wo_world);
+		bsdf_eval_pdf(mt, A->wi, wo_local, 1, &bsdf_value, &bsdf_pdf);
+	}
+	if (do_mis) { /* :310-311 */
+		woPdf = f * bsdf_pdf + (1.0f - f) * A->pdf_tree;
+		bsdf_weight = vdivs(bsdf_value, woPdf);
+		/* DELIBERATE DEVIATION: a direction sampled from a zero-energy quadtree
+		 * (pdf 0, quadtree.py:1086-1092) below the surface has bsdf_pdf = 0 too, and the
+		 * reference then divides 0/0 -- its throughput turns NaN and poisons the pixel
+		 * (about 1e-7 of the paths on cornell-box).  Such a path carries no energy: stop it. */
+		if (!(woPdf > 0.0f)) bsdf_weight = V(0, 0, 0);
+	}
+	/* ---- :318-346 record ---- */
+	rec->recorded = record && valid;
+	rec->bsdf_weight = bsdf_weight; rec->thr = thr; rec->L = L; rec->woPdf = woPdf;
+	rec->nee = V(0, 0, 0); rec->nee_lum = 0.0f;
+	if (rec->recorded && store_nee) { /* :336, and the NaN scrub + luminance of :467, 471 */
+		v3 rn = vdiv(Lr_dir, thr);
+		rec->nee = rn;
+		if (rn.x != rn.x) rn.x = 0.0f;
+		if (rn.y != rn.y) rn.y = 0.0f;
+		if (rn.z != rn.z) rn.z = 0.0f;
+		rec->nee_lum = pgo_luminance(rn.x, rn.y, rn.z);
+	}
+	/* ---- :352-381 advance ---- */
+	if (level >= 3) ior = ior * A->eta; /* :353 (the BSDF sample's eta also when the direction came from the tree) */
+	thr = vmul(thr, bsdf_weight);
+	const float tmax = max3(thr);
+	active_next = active_next && (tmax != 0.0f);
+	float rr_prob = tmax * (ior * ior);
+	if (!(rr_prob < 0.95f)) rr_prob = 0.95f; /* dr.minimum(x, 0.95): NaN -> 0.95 */
+	const int rr_active = depth >= (uint32_t)rr_depth;
+	const float rr = pgo_pcg32_next_f32(rng); /* :377, unmasked */
+	const int rr_continue = rr < rr_prob;
+	active_next = active_next && (!rr_active || rr_continue);
+	/* :352 spawn_ray: the vertex pushed off the surface along the geometric normal, towards wo */
+	float mag = (1.0f + max3(V(fabsf(A->p.x), fabsf(A->p.y), fabsf(A->p.z)))) * RAY_EPS_F;
+	if (dot3(A->ng, wo_world) < 0.0f) mag = -mag;
+	*ray_o = vadd(A->p, vscale(A->ng, mag));
+	*ray_d = wo_world;
+	*prev_pdf = woPdf;
+	*delta_out = delta;
+	*thr_io = thr; *L_io = L; *ior_io = ior;
+	return active_next;
+}
+
+void pgo_vertex_probe(size_t n, size_t n_mat, const float *materials, int level, const pgo_vertex_lanes *in, float frac, int guided,
+                      int record, int store_nee, int rr_depth, const pgo_vertex_out *out)
+{
+	(void)n_mat; /* (the caller has checked the rows: oracle/pg_oracle.py) */
+	for (size_t i = 0; i < n; ++i) {
+		vertex_in A;
+		A.p = ld3(in->p + 3 * i); A.n = ld3(in->n + 3 * i); A.ng = ld3(in->ng + 3 * i); A.wi = ld3(in->wi + 3 * i);
+		A.Le = ld3(in->Le + 3 * i); A.em_w = ld3(in->em_w + 3 * i); A.bv_em = ld3(in->bv_em + 3 * i);
+		A.bsdf_w = ld3(in->bsdf_w + 3 * i); A.wo = ld3(in->wo + 3 * i);
+		A.ds_pdf = in->ds_pdf[i]; A.bp_em = in->bp_em[i]; A.bsdf_pdf = in->bsdf_pdf[i]; A.eta = in->eta[i];
+		A.pdf_nee = in->pdf_nee[i]; A.pdf_tree = in->pdf_tree[i];
+		A.flags = in->flags[i]; A.occluded = in->occluded[i] != 0;
+		/* the material as the device's material_of makes it: the row as the level reads it (level 0: none), the lane's reflectance */
+		material mt;
+		memset(&mt, 0, sizeof mt);
+		if (level > 0) mt = load_material_at_level(materials + (size_t)in->mat[i] * PGO_MATERIAL_STRIDE, level);
+		mt.refl = ld3(in->refl + 3 * i);
+		v3 thr = ld3(in->thr + 3 * i), L = ld3(in->L + 3 * i), ray_o, ray_d;
+		float ior = in->ior[i], prev_pdf;
+		int delta_out;
+		pgo_pcg32 rng = { in->rng_state[i], in->rng_inc[i] };
+		vertex_rec rec;
+		const int go = vertex_bookkeeping(&A, &mt, level, frac, guided, record, store_nee, rr_depth, in->depth[i], &rng, &thr, &L, &ior,
+		                                  &rec, &ray_o, &ray_d, &prev_pdf, &delta_out);
+		out->go[i] = go;
+		out->thr[3 * i] = thr.x; out->thr[3 * i + 1] = thr.y; out->thr[3 * i + 2] = thr.z;
+		out->L[3 * i] = L.x; out->L[3 * i + 1] = L.y; out->L[3 * i + 2] = L.z;
+		out->ior[i] = ior;
+		out->ray_o[3 * i] = ray_o.x; out->ray_o[3 * i + 1] = ray_o.y; out->ray_o[3 * i + 2] = ray_o.z;
+		out->ray_d[3 * i] = ray_d.x; out->ray_d[3 * i + 1] = ray_d.y; out->ray_d[3 * i + 2] = ray_d.z;
+		out->prev_pdf[i] = prev_pdf;
+		out->delta[i] = delta_out;
+		out->rng_state[i] = rng.state;
+		/* the record entry, planes of stride n as the device's list has them; nothing is written where nothing is recorded */
+		if (record) out->ray_of[i] = (A.flags & PGO_F_VALID) ? (uint32_t)i : 0xffffffffu;
+		if (rec.recorded) {
+			out->r_bsdf[i] = rec.bsdf_weight.x; out->r_bsdf[n + i] = rec.bsdf_weight.y; out->r_bsdf[2 * n + i] = rec.bsdf_weight.z;
+			out->r_tb[i] = rec.thr.x; out->r_tb[n + i] = rec.thr.y; out->r_tb[2 * n + i] = rec.thr.z;
+			out->r_tr[i] = rec.L.x; out->r_tr[n + i] = rec.L.y; out->r_tr[2 * n + i] = rec.L.z;
+			out->r_nee[i] = rec.nee_lum;
+			out->r_wp[i] = rec.woPdf;
+		}
+	}
+}
+
 void pgo_render_pass(const pgo_tree *prev, pgo_tree *current, size_t nq, const float *quads,
                      const pgo_camera *cam, const pgo_render_params *prm, float *L_out, uint8_t *valid_out,
                      float *sumL, float *sumL2)
@@ -1124,9 +1277,8 @@ void pgo_render_pass_scene(const pgo_tree *prev, pgo_tree *current, const pgo_sc
 			v3 bsdf_value_em;
 			float bsdf_pdf_em;
 			bsdf_eval_pdf(mt, wi, wo_em, active_em, &bsdf_value_em, &bsdf_pdf_em);
-			/* ---- :223-256 NEE MIS against the mixture pdf ---- */
+			/* ---- :244 the SD-tree's pdf of the emitter direction ---- */
 			int active_sd_em = active_em && guided;
-			float pdf_diffuse = 1.0f; /* :222-241, SURVEY A12 */
 			float pp[3] = { p.x, p.y, p.z };
 			uint32_t tree = 0;
 			int tree_known = 0;
@@ -1137,20 +1289,13 @@ void pgo_render_pass_scene(const pgo_tree *prev, pgo_tree *current, const pgo_sc
 				float dv[3] = { ds_d.x, ds_d.y, ds_d.z };
 				sdtree_pdf_em = pgo_i_pdf(prev, tree, dv, 1);
 			}
-			float surface_pdf_em = f * bsdf_pdf_em + ((1.0f - f) * sdtree_pdf_em) * pdf_diffuse;
-			if (!guided) surface_pdf_em = bsdf_pdf_em;
-			float mis_em = ds_delta ? 1.0f : mis_weight(ds_pdf, surface_pdf_em); /* :253 */
-			v3 Lr_dir = vmul(vmul(vscale(thr, mis_em), bsdf_value_em), em_weight);
-			L = vadd(L, vadd(Le, Lr_dir)); /* :261 */
-			/* ---- :272-311 next direction ---- */
+			/* ---- :272-297 next direction ---- */
 			float s1 = 0.0f, s2x = 0.0f, s2y = 0.0f;
 			if (active_next) { s1 = pgo_pcg32_next_f32(&rng); s2x = pgo_pcg32_next_f32(&rng); s2y = pgo_pcg32_next_f32(&rng); }
 			v3 wo_local, bsdf_weight;
 			float bsdf_pdf, eta;
 			int delta;
 			bsdf_sample(mt, wi, s1, s2x, s2y, active_next, &wo_local, &bsdf_pdf, &bsdf_weight, &eta, &delta);
-			v3 bsdf_value = vscale(bsdf_weight, bsdf_pdf);
-			float woPdf = bsdf_pdf;
 			v3 wo_world = to_world(&fr, wo_local);
 			int do_mis = active_next && !delta && guided;
 			int pick_tree = 0;
@@ -1158,68 +1303,49 @@ void pgo_render_pass_scene(const pgo_tree *prev, pgo_tree *current, const pgo_sc
 			int smp_tree = pick_tree && do_mis;
 			int bsdf_mis = do_mis && !smp_tree;
 			float sdtree_pdf = 1.0f;
-			if (smp_tree) { /* :301-304 */
+			if (smp_tree) { /* :301 (the BSDF at that direction, :302-304: vertex_bookkeeping) */
 				if (!tree_known) { tree = pgo_i_quadtree_of(prev, pp, 1); tree_known = 1; }
 				float dv[3];
 				pgo_i_sample(prev, tree, &rng.state, rng.inc, 1, dv);
 				sdtree_pdf = pgo_i_pdf(prev, tree, dv, 1);
 				wo_world = V(dv[0], dv[1], dv[2]);
-				wo_local = to_local(&fr, wo_world);
-				bsdf_eval_pdf(mt, wi, wo_local, 1, &bsdf_value, &bsdf_pdf);
 			}
 			if (bsdf_mis) { /* :307 */
 				if (!tree_known) { tree = pgo_i_quadtree_of(prev, pp, 1); tree_known = 1; }
 				float dv[3] = { wo_world.x, wo_world.y, wo_world.z };
 				sdtree_pdf = pgo_i_pdf(prev, tree, dv, 1);
 			}
-			if (do_mis) { /* :310-311 */
-				woPdf = f * bsdf_pdf + (1.0f - f) * sdtree_pdf;
-				bsdf_weight = vdivs(bsdf_value, woPdf);
-				/* DELIBERATE DEVIATION: a direction sampled from a zero-energy quadtree
-				 * (pdf 0, quadtree.py:1086-1092) below the surface has bsdf_pdf = 0 too, and the
-				 * reference then divides 0/0 -- its throughput turns NaN and poisons the pixel
-				 * (about 1e-7 of the paths on cornell-box).  Such a path carries no energy: stop it. */
-				if (!(woPdf > 0.0f)) bsdf_weight = V(0, 0, 0);
-			}
-			/* ---- :318-346 record ---- */
-			if (record && active && valid) {
+			/* ---- :247-261, 302-311, 318-346, 352-378: the vertex's bookkeeping ---- */
+			vertex_in A;
+			A.p = p; A.n = n; A.ng = ng; A.wi = wi; A.Le = Le; A.em_w = em_weight; A.bv_em = bsdf_value_em; A.bsdf_w = bsdf_weight;
+			A.wo = wo_world; A.ds_pdf = ds_pdf; A.bp_em = bsdf_pdf_em; A.bsdf_pdf = bsdf_pdf; A.eta = eta;
+			A.pdf_nee = sdtree_pdf_em; A.pdf_tree = sdtree_pdf;
+			A.occluded = 0; /* (sample_emitter has cast the shadow ray: em_weight is zero behind an occluder) */
+			A.flags = (valid ? PGO_F_VALID : 0u) | (active_next ? PGO_F_ACTIVE_NEXT : 0u) | (ds_delta ? PGO_F_DS_DELTA : 0u) |
+			          (delta ? PGO_F_DELTA : 0u) | (do_mis ? PGO_F_DO_MIS : 0u) | (smp_tree ? PGO_F_SMP_TREE : 0u) |
+			          (vertex_nee_live(active_em, bsdf_value_em, em_weight) ? PGO_F_NEE_LIVE : 0u) |
+			          ((pgo_f2u(Le.x) | pgo_f2u(Le.y) | pgo_f2u(Le.z)) != 0u ? PGO_F_HAS_LE : 0u);
+			vertex_rec rec;
+			active_next = vertex_bookkeeping(&A, mt, 3, f, guided, record, prm->store_nee, prm->rr_depth, depth, &rng, &thr, &L, &ior,
+			                                 &rec, &ray_o, &ray_d, &prev_bsdf_pdf, &prev_delta);
+			if (rec.recorded) { /* the record as the reference keeps it: position and directions beside what the bookkeeping gives */
 				size_t g = lane * (size_t)D + depth;
 				float c[2];
 				r_act[g] = 1;
 				r_pos[g] = p.x; r_pos[S + g] = p.y; r_pos[2 * S + g] = p.z;
 				pgo_dir_to_canonical(wo_world.x, wo_world.y, wo_world.z, c);
 				r_dir[g] = c[0]; r_dir[S + g] = c[1];
-				r_bsdf[g] = bsdf_weight.x; r_bsdf[S + g] = bsdf_weight.y; r_bsdf[2 * S + g] = bsdf_weight.z;
-				r_tb[g] = thr.x; r_tb[S + g] = thr.y; r_tb[2 * S + g] = thr.z;
-				r_tr[g] = L.x; r_tr[S + g] = L.y; r_tr[2 * S + g] = L.z;
+				r_bsdf[g] = rec.bsdf_weight.x; r_bsdf[S + g] = rec.bsdf_weight.y; r_bsdf[2 * S + g] = rec.bsdf_weight.z;
+				r_tb[g] = rec.thr.x; r_tb[S + g] = rec.thr.y; r_tb[2 * S + g] = rec.thr.z;
+				r_tr[g] = rec.L.x; r_tr[S + g] = rec.L.y; r_tr[2 * S + g] = rec.L.z;
 				if (prm->store_nee) {
-					v3 rn = vdiv(Lr_dir, thr);
-					r_nee[g] = rn.x; r_nee[S + g] = rn.y; r_nee[2 * S + g] = rn.z;
+					r_nee[g] = rec.nee.x; r_nee[S + g] = rec.nee.y; r_nee[2 * S + g] = rec.nee.z;
 					pgo_dir_to_canonical(ds_d.x, ds_d.y, ds_d.z, c);
 					r_dnee[g] = c[0]; r_dnee[S + g] = c[1];
 				}
-				r_wp[g] = woPdf;
+				r_wp[g] = rec.woPdf;
 			}
-			/* ---- :352-381 advance ---- */
-			{
-				float mag = (1.0f + max3(V(fabsf(p.x), fabsf(p.y), fabsf(p.z)))) * RAY_EPS_F;
-				if (dot3(ng, wo_world) < 0.0f) mag = -mag;
-				ray_o = vadd(p, vscale(ng, mag));
-				ray_d = wo_world;
-			}
-			ior = ior * eta;
-			thr = vmul(thr, bsdf_weight);
 			prev_p = p;
-			prev_bsdf_pdf = woPdf;
-			prev_delta = delta;
-			float tmax = max3(thr);
-			active_next = active_next && (tmax != 0.0f);
-			float rr_prob = tmax * (ior * ior);
-			if (!(rr_prob < 0.95f)) rr_prob = 0.95f; /* dr.minimum(x, 0.95): NaN -> 0.95 */
-			int rr_active = depth >= (uint32_t)prm->rr_depth;
-			float rr = pgo_pcg32_next_f32(&rng); /* :377, unmasked */
-			int rr_continue = rr < rr_prob;
-			active_next = active_next && (!rr_active || rr_continue);
 			active = active_next;
 			if (valid) depth += 1;
 		}

@@ -179,6 +179,46 @@ void pgo_bsdf_probe(size_t n, const float *materials, const int32_t *material_in
                     const float *u, int level, float *value, float *pdf, float *sampled_wo, float *sampled_pdf, float *weight,
                     float *eta, int32_t *delta);
 
+/* The bookkeeping of one path vertex by itself (path_guiding_integrator.py:247-261, 302-311, 318-346, 352-378): the emitter
+ * sample's MIS against the mixture pdf, the radiance add, the BSDF at a direction the SD-tree proposed, woPdf and the
+ * overwritten BSDF weight, the record, ior, throughput, Russian roulette, the spawned ray -- the function the lane loop of
+ * pgo_render_pass_scene calls, over arrays.  What ray casting, the surface, emitter sampling, the BSDF sample and the SD-tree
+ * give a vertex comes in as columns (n lanes; 3-vectors interleaved, lane i at [3 i ..]); the flags are the device's F_*. */
+#define PGO_F_VALID 1u        /* the ray hit something (:185) */
+#define PGO_F_ACTIVE_NEXT 2u  /* depth + 1 < max_depth and valid (:207) */
+#define PGO_F_DS_DELTA 16u    /* the emitter sample came from a delta light */
+#define PGO_F_DELTA 32u       /* the BSDF sample is a delta lobe (:282) */
+#define PGO_F_DO_MIS 64u      /* bsdf-mis or sdtree-mis lane (:283) */
+#define PGO_F_SMP_TREE 128u   /* sdtree-mis: the direction comes from the SD-tree (:295) */
+#define PGO_F_NEE_LIVE 512u   /* the emitter sample can contribute */
+#define PGO_F_HAS_LE 1024u    /* emitted radiance reached the path here */
+typedef struct pgo_vertex_lanes {
+	const float *thr, *L, *ior;       /* the path's state: (n,3), (n,3), (n) */
+	const uint32_t *depth, *flags;    /* (n) each */
+	const float *Le;                  /* (n,3): read where PGO_F_HAS_LE is set */
+	const float *p, *n, *ng, *wi, *refl; /* (n,3) each */
+	const int32_t *mat;               /* (n): row of the material table (not read at level 0) */
+	const float *em_w, *bv_em, *bp_em, *ds_pdf; /* (n,3), (n,3), (n), (n): read where PGO_F_NEE_LIVE is set */
+	const float *bsdf_w, *bsdf_pdf, *eta;       /* (n,3), (n), (n) */
+	const float *wo, *pdf_nee, *pdf_tree;       /* (n,3), (n), (n) */
+	const int32_t *occluded;                    /* (n) */
+	const uint64_t *rng_state, *rng_inc;        /* (n) each: the lane's sampler */
+} pgo_vertex_lanes;
+typedef struct pgo_vertex_out {
+	int32_t *go;                      /* (n): the path continues */
+	float *thr, *L, *ior, *ray_o, *ray_d, *prev_pdf; /* (n,3), (n,3), (n), (n,3), (n,3), (n) */
+	int32_t *delta;                   /* (n) */
+	uint64_t *rng_state;              /* (n): advanced by the roulette's draw */
+	/* the record entry, planes of stride n; ray_of is written when `record` (i, or 0xffffffff for an invalid lane), the others
+	 * only for a recorded lane (record and PGO_F_VALID) */
+	uint32_t *ray_of;
+	float *r_bsdf, *r_tb, *r_tr, *r_nee, *r_wp; /* (3,n), (3,n), (3,n), (n), (n) */
+} pgo_vertex_out;
+/* level: the feature level of the device kernel whose reading is wanted (it decides how a PGO_F_SMP_TREE lane reads its
+ * material row, whether a delta light's sample has MIS weight 1 and whether ior follows eta: level 3 only, both). */
+void pgo_vertex_probe(size_t n, size_t n_mat, const float *materials, int level, const pgo_vertex_lanes *in, float frac, int guided,
+                      int record, int store_nee, int rr_depth, const pgo_vertex_out *out);
+
 /* Film reconstruction of one full-frame pass with Mitsuba's `tent` reconstruction filter, radius one
  * pixel (the <rfilter type="tent"/> of scenes/cornell-box/scene.xml:27): what mi.render returns at
  * main.py:218.  Sample s of pixel (px,py) sits at (px + jx, py + jy), its first two sampler draws;

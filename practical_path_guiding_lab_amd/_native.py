@@ -73,6 +73,18 @@ class pg_resample_args(C.Structure):
         "cand_dir_out", "cand_target_out", "cand_source_out")]
 
 
+class pg_vertex_lanes(C.Structure):  # include/pgsd.h: the columns of pg_vertex_probe, device pointers
+    _fields_ = [(n, C.c_void_p) for n in (
+        "thr", "L", "ior", "depth", "flags", "Le", "p", "n", "ng", "wi", "refl", "mat", "em_w", "bv_em", "bp_em", "ds_pdf",
+        "bsdf_w", "bsdf_pdf", "eta", "wo", "pdf_nee", "pdf_tree", "occluded", "rng_state", "rng_inc")]
+
+
+class pg_vertex_out(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in (
+        "go", "thr", "L", "ior", "ray_o", "ray_d", "prev_pdf", "delta", "rng_state", "ray_of", "r_bsdf", "r_tb", "r_tr", "r_nee",
+        "r_wp")]
+
+
 class pg_tree_sizes(C.Structure):
     _fields_ = [("n_kd", C.c_uint64), ("n_quad", C.c_uint64), ("n_roots", C.c_uint64)]
 
@@ -181,6 +193,7 @@ SURFACE = {
         "pg_bsdf_probe": [V, U64, U64, V, V, V, V, V, I32, V, V, V, V, V, V, V, V],
         "pg_surface_probe": [V, U64, V, V, V, V, V, V, V, V, V],
         "pg_emitter_probe": [V, U64, V, V, V, V, V, V],
+        "pg_vertex_probe": [V, U64, U64, V, I32, P(pg_vertex_lanes), F32, I32, I32, I32, I32, P(pg_vertex_out), V],
     },
     "pgsd_warp.h": {  # sample warping: same library, same ABI version
         "pg_sample_warp": [V, U64, V, V, V, V, V, V], "pg_invert_warp": [V, U64, V, V, V, V, V, V],

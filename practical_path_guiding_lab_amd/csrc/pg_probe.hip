@@ -7,12 +7,15 @@
 // surface_at<>, normal_at<>, make_frame, to_local, to_world and emitter_hit_pdf<> as stage_a1 calls them.
 // pg_emitter_probe: emitter sampling by itself -- one (point, geometric normal, 2-D sample) per lane through
 // sample_emitter_ray<> with the scene's own emitter list, directional lights and bounding sphere, as stage_a1 passes them.
+// pg_vertex_probe: a vertex's bookkeeping by itself -- one lane per item through stage_b<> of pg_render_stages.hpp, fed with
+// columns that hold what StageA, GuideOut and the path state hold, its record planes the caller's output planes.
 // Nothing of the product path launches these kernels.
 #include <string>
 #include <type_traits>
 #include <vector>
 
 #include "pg_render_dev.hpp"
+#include "pg_render_stages.hpp"
 #include "pg_scene_state.hpp"
 
 using namespace pg;
@@ -185,6 +188,58 @@ __global__ __launch_bounds__(kRBlock) void k_probe_emitter(EmitterProbeArgs a)
 }
 static_assert(PG_EMITTER_PROBE_FLOATS == 14, "k_probe_emitter writes 14 floats per lane");
 
+struct VertexProbeArgs {
+	RenderArgs a; // what stage_b reads of it: mats, n_lanes, max_depth (the record planes' stride only), frac, guided, record,
+	              // store_nee, rr_depth and the record planes -- the caller's output planes, stride n
+	pg_vertex_lanes in;
+	pg_vertex_out out;
+};
+static_assert(sizeof(VertexProbeArgs) <= 4096, "kernel arguments are at most 4 KB");
+static_assert(PG_VERTEX_VALID == F_VALID && PG_VERTEX_ACTIVE_NEXT == F_ACTIVE_NEXT && PG_VERTEX_DS_DELTA == F_DS_DELTA &&
+                  PG_VERTEX_DELTA == F_DELTA && PG_VERTEX_DO_MIS == F_DO_MIS && PG_VERTEX_SMP_TREE == F_SMP_TREE &&
+                  PG_VERTEX_NEE_LIVE == F_NEE_LIVE && PG_VERTEX_HAS_LE == F_HAS_LE,
+              "include/pgsd.h names the lane classes of pg_render_stages.hpp");
+
+// No loop (stage_b evaluates the BSDF, it does not sample: rc_sample_visible_11's Newton steps are not reached); every address is a
+// function of tid < n -- the record entry's too: rec_slot = tid in planes of stride n_lanes * max_depth = n -- and of a checked
+// row number, which material_of follows on PG_VERTEX_SMP_TREE lanes of levels 1..3 only.
+template <int kLevel>
+__global__ __launch_bounds__(kRBlock) void k_probe_vertex(VertexProbeArgs v)
+{
+	const uint64_t tid = (uint64_t)blockIdx.x * kRBlock + threadIdx.x;
+	if (tid >= v.a.n_lanes) return;
+	const pg_vertex_lanes &in = v.in;
+	StageA A;
+	A.p = ld3(in.p + 3 * tid); A.n = ld3(in.n + 3 * tid); A.ng = ld3(in.ng + 3 * tid); A.wi = ld3(in.wi + 3 * tid);
+	A.refl = ld3(in.refl + 3 * tid); A.Le = ld3(in.Le + 3 * tid);
+	A.ds_d = V(0, 0, 0); A.sh_o = V(0, 0, 0); A.sh_d = V(0, 0, 1); A.sh_tmax = 0.0f; // (stage_b reads none of the four)
+	A.em_w = ld3(in.em_w + 3 * tid); A.bv_em = ld3(in.bv_em + 3 * tid);
+	A.wo = ld3(in.wo + 3 * tid); A.bsdf_w = ld3(in.bsdf_w + 3 * tid);
+	A.ds_pdf = in.ds_pdf[tid]; A.bp_em = in.bp_em[tid]; A.bsdf_pdf = in.bsdf_pdf[tid]; A.eta = in.eta[tid];
+	A.mat = in.mat[tid];
+	A.flags = in.flags[tid];
+	GuideOut g = guide_none(A.wo);
+	g.pdf_nee = in.pdf_nee[tid];
+	g.pdf_tree = in.pdf_tree[tid];
+	Pcg32 rng;
+	rng.state = in.rng_state[tid]; rng.inc = in.rng_inc[tid];
+	v3 thr = ld3(in.thr + 3 * tid), L = ld3(in.L + 3 * tid), ray_o, ray_d;
+	float ior = in.ior[tid], prev_pdf;
+	bool delta_out;
+	const bool go = stage_b<kLevel>(v.a, rng, thr, L, ior, A, g, in.occluded[tid] != 0, tid, tid, in.depth[tid], ray_o, ray_d, prev_pdf,
+	                                delta_out);
+	const pg_vertex_out &o = v.out;
+	o.go[tid] = go ? 1 : 0;
+	o.thr[3 * tid] = thr.x; o.thr[3 * tid + 1] = thr.y; o.thr[3 * tid + 2] = thr.z;
+	o.L[3 * tid] = L.x; o.L[3 * tid + 1] = L.y; o.L[3 * tid + 2] = L.z;
+	o.ior[tid] = ior;
+	o.ray_o[3 * tid] = ray_o.x; o.ray_o[3 * tid + 1] = ray_o.y; o.ray_o[3 * tid + 2] = ray_o.z;
+	o.ray_d[3 * tid] = ray_d.x; o.ray_d[3 * tid + 1] = ray_d.y; o.ray_d[3 * tid + 2] = ray_d.z;
+	o.prev_pdf[tid] = prev_pdf;
+	o.delta[tid] = delta_out ? 1 : 0;
+	o.rng_state[tid] = rng.state;
+}
+
 // What every probe does before it reads an argument, in the order in which a caller sees the refusals: the context, the
 // scene (where the probe reads one), the probe's first check of its own (own_first, own_last: the message, or nullptr where
 // the check passes), the lane count, n == 0 (PG_OK: nothing is read), the pointers, its last check, the device.
@@ -219,6 +274,48 @@ int run_at_level(pg_context *ctx, int level, uint64_t n, void *stream, const Arg
 }
 
 } // namespace
+
+int pg_vertex_probe(pg_context *ctx, uint64_t n, uint64_t n_mat, const float *d_materials, int32_t level,
+                    const pg_vertex_lanes *lanes, float frac, int32_t guided, int32_t record, int32_t store_nee, int32_t rr_depth,
+                    const pg_vertex_out *out, void *stream)
+{
+	bool null_pointer = !d_materials || !lanes || !out;
+	if (lanes && out) {
+		const pg_vertex_lanes &l = *lanes;
+		const pg_vertex_out &o = *out;
+		for (const void *q : {(const void *)l.thr, (const void *)l.L, (const void *)l.ior, (const void *)l.depth, (const void *)l.flags,
+		                      (const void *)l.Le, (const void *)l.p, (const void *)l.n, (const void *)l.ng, (const void *)l.wi,
+		                      (const void *)l.refl, (const void *)l.mat, (const void *)l.em_w, (const void *)l.bv_em,
+		                      (const void *)l.bp_em, (const void *)l.ds_pdf, (const void *)l.bsdf_w, (const void *)l.bsdf_pdf,
+		                      (const void *)l.eta, (const void *)l.wo, (const void *)l.pdf_nee, (const void *)l.pdf_tree,
+		                      (const void *)l.occluded, (const void *)l.rng_state, (const void *)l.rng_inc, (const void *)o.go,
+		                      (const void *)o.thr, (const void *)o.L, (const void *)o.ior, (const void *)o.ray_o, (const void *)o.ray_d,
+		                      (const void *)o.prev_pdf, (const void *)o.delta, (const void *)o.rng_state, (const void *)o.ray_of,
+		                      (const void *)o.r_bsdf, (const void *)o.r_tb, (const void *)o.r_tr, (const void *)o.r_nee,
+		                      (const void *)o.r_wp})
+			null_pointer = null_pointer || !q;
+	}
+	const int rc = probe_ready(ctx, "pg_vertex_probe", false, level < 0 || level > 3 ? "level must be 0, 1, 2 or 3" : nullptr, n, "lanes",
+	                              null_pointer, n_mat == 0 || n_mat > 65536 ? "need 1..65536 material rows" : nullptr);
+	if (rc != kProbeGo) return rc;
+	PG_HIP(ctx, hipStreamSynchronize((hipStream_t)stream)); // (the caller's writes of the inputs, before the host reads them)
+	// the rows and the row numbers are checked on the host before a lane follows them
+	std::vector<float> rows(n_mat * kMaterialStride);
+	PG_HIP(ctx, hipMemcpy(rows.data(), d_materials, rows.size() * sizeof(float), hipMemcpyDeviceToHost));
+	if (const char *err = check_material_rows(rows.data(), n_mat, 65536)) return fail(ctx, PG_ERR_INVALID, std::string("pg_vertex_probe: ") + err);
+	std::vector<int32_t> index(n);
+	PG_HIP(ctx, hipMemcpy(index.data(), lanes->mat, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+	for (uint64_t i = 0; i < n; ++i)
+		if (index[i] < 0 || (uint64_t)index[i] >= n_mat) return fail(ctx, PG_ERR_INVALID, "pg_vertex_probe: material index outside the table");
+	VertexProbeArgs v = {};
+	v.in = *lanes;
+	v.out = *out;
+	v.a.mats = d_materials;
+	v.a.n_lanes = n; v.a.max_depth = 1; // (planes of stride n_lanes * max_depth = n, and rec_slot = the lane)
+	v.a.frac = frac; v.a.guided = guided ? 1 : 0; v.a.record = record ? 1 : 0; v.a.store_nee = store_nee ? 1 : 0; v.a.rr_depth = rr_depth;
+	v.a.ray_of = out->ray_of; v.a.r_bsdf = out->r_bsdf; v.a.r_tb = out->r_tb; v.a.r_tr = out->r_tr; v.a.r_nee = out->r_nee; v.a.r_wp = out->r_wp;
+	return run_at_level(ctx, level, n, stream, v, [](auto L) { return k_probe_vertex<decltype(L)::value>; });
+}
 
 int pg_emitter_probe(pg_context *ctx, uint64_t n, const float *d_p, const float *d_n, const float *d_e, float *d_out,
                      int32_t *d_flags, void *stream)

@@ -707,6 +707,25 @@ class SDTree:
                                          weight.data_ptr(), eta.data_ptr(), delta.data_ptr(), _stream_ptr()))
         return value, pdf, swo, spdf, weight, eta, delta
 
+    def vertexProbe(self, materials: torch.Tensor, lanes: Dict[str, torch.Tensor], out: Dict[str, torch.Tensor], level: int,
+                    frac: float, guided: bool, record: bool, store_nee: bool, rr_depth: int) -> None:
+        """pg_vertex_probe: the renderer's bookkeeping of one path vertex by itself, for tests -- materials (n_mat, 16) float32;
+        lanes: the columns of pg_vertex_lanes by name, out: those of pg_vertex_out by name (include/pgsd.h), contiguous tensors
+        on this device of the header's types (uint32 as int32 bits, uint64 as int64 bits); the outputs are written in place."""
+        m = materials.to(torch.float32).contiguous()
+        if m.dim() != 2 or m.shape[1] != 16:
+            raise ValueError("materials must be (n_mat,16)")
+        n = int(lanes["flags"].numel())
+        li, oo = N.pg_vertex_lanes(), N.pg_vertex_out()
+        for struct, cols in ((li, lanes), (oo, out)):
+            for name, _ in struct._fields_:
+                t = cols[name]
+                if not t.is_contiguous() or t.device != m.device:
+                    raise ValueError(name + ": a contiguous tensor on the tree's device")
+                setattr(struct, name, t.data_ptr())
+        self._ck(self._lib.pg_vertex_probe(self._h, n, m.shape[0], m.data_ptr(), int(level), C.byref(li), float(frac), int(bool(guided)),
+                                           int(bool(record)), int(bool(store_nee)), int(rr_depth), C.byref(oo), _stream_ptr()))
+
     def packAccumulators(self) -> torch.Tensor:
         """sdTree_current's accumulators in the 24-byte exchange format (pg_exchange_pack, on the current stream): the int64
         tensor a host-side collective sums instead of accumulators() -- a quarter fewer bytes; unpackAccumulators() writes
