@@ -73,6 +73,14 @@ class pg_resample_args(C.Structure):
         "cand_dir_out", "cand_target_out", "cand_source_out")]
 
 
+class pg_lights_params(C.Structure):  # include/ext/pg_lights.h
+    _fields_ = [("delta", C.c_float), ("root", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class pg_lights_records(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("position", "light", "value")]
+
+
 class pg_vertex_lanes(C.Structure):  # include/pgsd.h: the columns of pg_vertex_probe, device pointers
     _fields_ = [(n, C.c_void_p) for n in (
         "thr", "L", "ior", "depth", "flags", "Le", "p", "n", "ng", "wi", "refl", "mat", "em_w", "bv_em", "bp_em", "ds_pdf",
@@ -153,6 +161,7 @@ PG_FRACTION_LOSS_KL, PG_FRACTION_LOSS_VARIANCE = 0, 1
 PG_TARGET_SECOND_MOMENT = 1
 PG_BOUNCE_NONE, PG_BOUNCE_PDF, PG_BOUNCE_SAMPLE, PG_BOUNCE_CHOOSE = 0, 1, 2, 3
 PG_RESAMPLE_MAX_CANDIDATES, PG_RESAMPLE_NONE = 64, 0xFFFFFFFF
+PG_LIGHTS_MAX, PG_LIGHTS_WEIGHT_ONE, PG_LIGHTS_NONE = 4096, 65536, 0xFFFFFFFF
 
 V, U64, I32, U32, F32, P = C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_float, C.POINTER
 _RR = [V, U64, V, V, V, V, P(pg_rr_params), V, V, V, V, V, V, V]  # pg_radiance_rr and pg_irradiance_rr
@@ -232,17 +241,31 @@ SURFACE_EXTRA = {
     },
 }
 (EXPORTS_RESAMPLE,) = (tuple(entry_points) for entry_points in SURFACE_EXTRA.values())
+# Entry points whose headers live in a subdirectory of include/, keyed by the header's path under include/: a third table, because
+# the tests of SURFACE_EXTRA pin it to its one header and include/*.h to the headers there.  lib() binds it after
+# the other two, source_hash() hashes its headers after theirs.
+SURFACE_EXT = {
+    "ext/pg_lights.h": {  # light selection for next-event estimation, learned per KD leaf
+        "pg_lights_enable": [V, U32, P(pg_lights_params)], "pg_lights_record": [V, U64, P(pg_lights_records), V, V],
+        "pg_lights_build": [V, V], "pg_lights_sample": [V, U64, V, V, V, V, V, V, V, V],
+        "pg_lights_pmf": [V, U64, V, V, V, V, V], "pg_lights_accumulators": [V, P(V), P(U64)],
+        "pg_lights_status": [V, P(U32), P(U64)], "pg_lights_export": [V, U64, U32, V, V],
+        "pg_lights_import": [V, U64, U32, V],
+    },
+}
+(EXPORTS_LIGHTS,) = (tuple(entry_points) for entry_points in SURFACE_EXT.values())
 
 
 def source_hash() -> str:
     """sha256 (16 hex digits) over the library's sources (csrc/*.hip, csrc/*.hpp, then the headers of SURFACE in its order, then
-    those of SURFACE_EXTRA):
+    those of SURFACE_EXTRA, then those of SURFACE_EXT):
     names the code a profile was taken of (profiles/pmc_traffic.json) so that bench.py never pairs old counters with new kernels."""
     import glob
     import hashlib
     h = hashlib.sha256()
     files = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
-    files += [os.path.join(os.path.dirname(_PKG), "include", header) for header in list(SURFACE) + list(SURFACE_EXTRA)]
+    files += [os.path.join(os.path.dirname(_PKG), "include", *header.split("/"))
+              for header in list(SURFACE) + list(SURFACE_EXTRA) + list(SURFACE_EXT)]
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
@@ -281,7 +304,7 @@ def lib() -> C.CDLL:
     if L.pg_abi_version() != ABI_VERSION:  # (a library left over from an older build: its structs have other layouts)
         raise ImportError(f"{LIB_PATH} has ABI version {L.pg_abi_version()}, these bindings are written for {ABI_VERSION}: "
                           "rebuild it with `python -c 'import __graft_entry__ as g; g.build()'`")
-    for entry_points in list(SURFACE.values()) + list(SURFACE_EXTRA.values()):
+    for entry_points in list(SURFACE.values()) + list(SURFACE_EXTRA.values()) + list(SURFACE_EXT.values()):
         for name, argtypes in entry_points.items():
             fn = getattr(L, name)  # (a missing symbol is an AttributeError here)
             fn.argtypes = list(argtypes)

@@ -60,6 +60,7 @@ static int install(pg_context *ctx, const HostForest &h)
 	Forest &f = ctx->f;
 	ctx->frac.disable(); // (the learned fraction's table follows the forest: a new forest has none, pgsd_fraction.h)
 	ctx->rad.disable();  // (so do the quadtrees' statistical weights, pgsd_radiance.h)
+	ctx->lights.disable(); // (and the learned light selection, ext/pg_lights.h)
 	ctx->target_applied = 0; // (fresh accumulators: no target was applied to them, pgsd_target.h)
 	PG_HIP(ctx, upload(f.kd, h.kd, 1.5));
 	PG_HIP(ctx, upload(f.kd_bmin, h.kd_bmin, 1.5));

@@ -9,6 +9,7 @@
 
 #include "../../include/pgsd.h"
 #include "../../include/pgsd_fraction.h"
+#include "../../include/ext/pg_lights.h"
 #include "pg_kernels.hpp"
 #include "pg_math.hpp"
 #include "pg_tree.hpp"
@@ -150,6 +151,30 @@ struct Fraction {
 	}
 };
 
+// Light selection learned per KD leaf (include/ext/pg_lights.h, pg_kernels_lights.hip): off unless pg_lights_enable switched it
+// on.  One table for the n_trees leaves and L = n_lights lights, [ acc: n x L x kAccWords int64 | rows: n x L uint32 ], so that a
+// refine builds the next one in ONE spare buffer and commits it by one pointer swap (pg_refine.hip).
+constexpr uint64_t kLightsMaxEntries = 1ull << 31; // n_trees * n_lights: a record's key (tree * L + light) is a uint32
+struct Lights {
+	uint32_t n_lights = 0; // 0: the feature is off
+	pg_lights_params prm = {};
+	DevBuf<long long> tab, spare; // spare: the next refine's table (what a commit replaced)
+	bool on() const { return n_lights != 0; }
+	static size_t words(uint64_t entries) { return (size_t)(entries * kAccWords + (entries + 1) / 2); }
+	long long *acc() const { return tab.p; }
+	uint32_t *rows(uint32_t n_trees) const { return rows_of(tab.p, n_trees, n_lights); }
+	static uint32_t *rows_of(long long *tab, uint32_t n_trees, uint32_t n_lights)
+	{
+		return reinterpret_cast<uint32_t *>(tab + (size_t)n_trees * n_lights * kAccWords);
+	}
+	void disable()
+	{
+		n_lights = 0;
+		tab.release();
+		spare.release();
+	}
+};
+
 // Radiance estimates (include/pgsd_radiance.h, pg_kernels_radiance.hip): off unless pg_radiance_enable switched it on.  One uint64
 // per quadtree of sdTree_prev, the number of in-box records its energies were resolved from; a refine builds the next table in the
 // spare buffer and commits it, with the two flags, by one pointer swap (pg_refine.hip).
@@ -214,6 +239,7 @@ struct pg_context {
 	pg::Forest f;
 	pg::Fraction frac;               // the learned sampling fraction (disabled by pg_setup / pg_import)
 	pg::Radiance rad;                // the quadtrees' statistical weights (disabled by pg_setup / pg_import)
+	pg::Lights lights;               // the learned light selection (disabled by pg_setup / pg_import)
 	int32_t target_applied = 0;      // the target pg_target_apply gave f.acc since the last refine commit / setup / import (pgsd_target.h)
 	pg::DepthCounters *dc = nullptr; // device
 	bool dc_on = false;
@@ -269,6 +295,9 @@ int rebuild_jump(pg_context *ctx, hipStream_t s); // after every change of the q
 // pg_kernels_fraction.hip: the table of the refined forest -- new leaf t takes the state of old leaf tree_src[t], zero accumulators
 void launch_fraction_carry(const long long *old_tab, uint32_t n_old, const uint32_t *tree_src, long long *new_tab, uint32_t n_new,
                            hipStream_t s);
+// pg_kernels_lights.hip: the table of the refined forest -- new leaf t takes the row of old leaf tree_src[t], zero accumulators
+hipError_t launch_lights_carry(long long *old_tab, uint32_t n_old, const uint32_t *tree_src, long long *new_tab, uint32_t n_new,
+                               uint32_t n_lights, int n_cus, hipStream_t s);
 // pg_kernels_radiance.hip: the weights of the refined forest -- new tree t takes the count resolved for old tree tree_src[t]
 void launch_radiance_carry(const unsigned long long *tree_count, uint32_t n_old, const uint32_t *tree_src, unsigned long long *w_new,
                            uint32_t n_new, hipStream_t s);

@@ -16,6 +16,8 @@
 // Limb discipline: a limb's payload is below 2^32 per record, and every partial sum here lives in a 64-bit word
 // exactly like the accumulator itself -- a wave's sum stays below 2^38, a block's below 2^32 * (its records) -- so what reaches
 // the accumulator is the same integer per word as record-by-record adds would leave, and the 2^31-record bound is unchanged.
+// (k_lights_record, lights_table_add and lights_wave_sum_u64 of pg_kernels_lights.hip are copies of the three stages below with
+// another key: a fix to one belongs in the other.)
 #include "../../include/pgsd_fraction.h"
 #include "pg_context.hpp"
 #include "pg_descent.hpp"

@@ -637,6 +637,15 @@ int refine_and_swap(pg_context *ctx, hipStream_t s)
 		launch_fraction_carry(fr.tab.p, f.n_trees, w.tree_src.p, fr.spare.p, n_trees_new, s);
 		PG_HIP(ctx, hipGetLastError());
 	}
+	// ---- the learned light selection (ext/pg_lights.h), where it is on: the same, every new leaf with the row of the leaf it is
+	// a copy of
+	Lights &li = ctx->lights;
+	if (li.on()) {
+		const uint64_t entries = (uint64_t)n_trees_new * li.n_lights;
+		if (entries > kLightsMaxEntries) return fail(ctx, PG_ERR_NOMEM, "refine: leaves x lights would exceed 2^31 (pg_lights.h)");
+		PG_HIP(ctx, li.spare.ensure(Lights::words(entries), kGrow));
+		PG_HIP(ctx, launch_lights_carry(li.tab.p, f.n_trees, w.tree_src.p, li.spare.p, n_trees_new, li.n_lights, ctx->n_cus, s));
+	}
 	// ---- the quadtrees' statistical weights (pgsd_radiance.h), where they are on: every new tree with the count that was
 	// resolved for the tree it comes from (w.tree_count, k_resolve_roots), in the spare buffer; the running table stays until the commit
 	Radiance &rad = ctx->rad;
@@ -657,6 +666,7 @@ int refine_and_swap(pg_context *ctx, hipStream_t s)
 	f.tree_thr.swap(w.new_thr);
 	f.acc.swap(w.new_acc);
 	if (fr.on) fr.tab.swap(fr.spare);
+	if (li.on()) li.tab.swap(li.spare);
 	if (rad.on) {
 		rad.tab.swap(rad.spare);
 		rad.valid = 1;

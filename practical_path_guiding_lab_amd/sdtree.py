@@ -325,6 +325,96 @@ class SDTree:
             raise ValueError("theta, m, v, p1, p2 and steps must have one entry per leaf")
         self._ck(self._lib.pg_fraction_import(self._h, n, *[x.ctypes.data for x in a]))
 
+    # ---- light selection learned per KD leaf (include/ext/pg_lights.h; not in the reference) -------------------------------
+    def lightsEnable(self, n_lights: int, delta: float = 0.1, root: bool = False):
+        """Switches the learned light selection on for lights 0 .. n_lights - 1 with every leaf unlearned (pg_lights_enable).
+        delta: the share of the uniform choice on a learned leaf; root: weights follow the square roots of the recorded means
+        (record squared contributions for the variance-aware target).  setup() and load() switch the feature off."""
+        if int(n_lights) < 1:
+            raise ValueError("n_lights must be at least 1 (lightsDisable switches the feature off)")
+        prm = N.pg_lights_params(float(delta), int(bool(root)), 0)
+        self._ck(self._lib.pg_lights_enable(self._h, int(n_lights), C.byref(prm)))
+
+    def lightsDisable(self):
+        self._ck(self._lib.pg_lights_enable(self._h, 0, None))
+
+    def lightsSample(self, position: torch.Tensor, u: Optional[torch.Tensor] = None, sampler: Optional[PCG32Sampler] = None,
+                     active: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """A light for each position from the row of its KD leaf (pg_lights_sample): (light int32 (N,), pmf float32 (N,)).
+        u: float32 (N,) in [0, 1), or None to draw one number from `sampler`.  Inactive lanes get light -1 and pmf 0."""
+        n = position.shape[1]
+        _f32(position, (3, n))
+        if (u is None) == (sampler is None):
+            raise ValueError("give either u or a sampler")
+        up = None if u is None else _f32(u, (n,)).data_ptr()
+        sp, ip = (None, None) if sampler is None else (sampler.state.data_ptr(), sampler.inc.data_ptr())
+        if sampler is not None and sampler.n < n:
+            raise ValueError("the sampler has fewer streams than there are positions")
+        m, mp = _mask(active, n)
+        light = self._new(n, dtype=torch.int32)
+        pmf = self._new(n)
+        self._ck(self._lib.pg_lights_sample(self._h, n, position.data_ptr(), up, sp, ip, mp, light.data_ptr(), pmf.data_ptr(),
+                                            _stream_ptr()))
+        return light, pmf
+
+    def lightsPmf(self, position: torch.Tensor, light: torch.Tensor, active: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The probability lightsSample gives each light at each position (pg_lights_pmf), float32 (N,); light: int32 (N,)."""
+        n = position.shape[1]
+        _f32(position, (3, n))
+        if light.dtype != torch.int32 or not light.is_cuda or not light.is_contiguous() or tuple(light.shape) != (n,):
+            raise ValueError("light must be a contiguous CUDA int32 tensor of shape (N,)")
+        m, mp = _mask(active, n)
+        pmf = self._new(n)
+        self._ck(self._lib.pg_lights_pmf(self._h, n, position.data_ptr(), light.data_ptr(), mp, pmf.data_ptr(), _stream_ptr()))
+        return pmf
+
+    def lightsRecord(self, rec: Dict[str, torch.Tensor], count: Optional[torch.Tensor] = None):
+        """Adds the records' contributions to the accumulators of (leaf, light) (pg_lights_record).  rec: position (3, M), light
+        int32 (M,), value (M,): the NEE contribution estimate before the division by the selection probability.  count: as
+        addDataPropagate's."""
+        m = rec["position"].shape[1]
+        light = rec["light"]
+        if light.dtype != torch.int32 or not light.is_cuda or not light.is_contiguous() or tuple(light.shape) != (m,):
+            raise ValueError("light must be a contiguous CUDA int32 tensor of shape (M,)")
+        r = N.pg_lights_records()
+        r.position = _f32(rec["position"], (3, m)).data_ptr()
+        r.light = light.data_ptr()
+        r.value = _f32(rec["value"], (m,)).data_ptr()
+        self._ck(self._lib.pg_lights_record(self._h, m, C.byref(r), _count_ptr(count), _stream_ptr()))
+
+    def lightsBuild(self):
+        """Every leaf that has recorded energy gets its row from its accumulators, which stay (pg_lights_build)."""
+        self._ck(self._lib.pg_lights_build(self._h, _stream_ptr()))
+
+    def lightsAccumulators(self) -> torch.Tensor:
+        """int64 view of the accumulators (n_roots * n_lights * 4 words, leaf-major then light), for an element-wise sum over
+        ranks before lightsBuild."""
+        p = C.c_void_p()
+        n = C.c_uint64()
+        self._ck(self._lib.pg_lights_accumulators(self._h, C.byref(p), C.byref(n)))
+        return _wrap_device_i64(p.value, n.value, self.device)
+
+    def lightsStatus(self) -> Tuple[int, int]:
+        """(n_lights, leaves that have learned a row) -- (0, 0) while the feature is off (pg_lights_status)."""
+        n, k = C.c_uint32(), C.c_uint64()
+        self._ck(self._lib.pg_lights_status(self._h, C.byref(n), C.byref(k)))
+        return int(n.value), int(k.value)
+
+    def lightsState(self) -> Dict[str, np.ndarray]:
+        """The per-leaf state (pg_lights_export): rows uint32 (n_roots, n_lights), acc int64 (n_roots, n_lights, 4), indexed by
+        the tree number export() writes in kdtree_quadTreeRootIndex."""
+        n, L = int(self.sizes().n_roots), self.lightsStatus()[0]
+        st = {"rows": np.empty((n, L), np.uint32), "acc": np.empty((n, L, 4), np.int64)}
+        self._ck(self._lib.pg_lights_export(self._h, n, L, st["rows"].ctypes.data, st["acc"].ctypes.data))
+        return st
+
+    def lightsLoadState(self, st: Dict[str, np.ndarray]):
+        """Loads the rows (pg_lights_import); the accumulators become zero."""
+        rows = np.ascontiguousarray(st["rows"], np.uint32)
+        if rows.ndim != 2:
+            raise ValueError("rows must have shape (n_roots, n_lights)")
+        self._ck(self._lib.pg_lights_import(self._h, rows.shape[0], rows.shape[1], rows.ctypes.data))
+
     def compactLanes(self, select: torch.Tensor, nee_active: Optional[torch.Tensor] = None,
                      idx_out: Optional[torch.Tensor] = None, count_out: Optional[torch.Tensor] = None):
         """Active-ray stream compaction (pg_compact_lanes): returns (idx int32[n], counts int32[2]);
