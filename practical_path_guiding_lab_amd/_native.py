@@ -73,6 +73,12 @@ class pg_resample_args(C.Structure):
         "cand_dir_out", "cand_target_out", "cand_source_out")]
 
 
+class pg_resample_lobe_args(C.Structure):  # include/ext/guiding/pg_resample_lobe.h
+    _fields_ = [(n, C.c_void_p) for n in (
+        "p", "normal", "wi", "roughness", "specular", "active", "rng_state", "rng_inc", "dir_out", "weight_out", "target_out",
+        "source_out", "index_out", "cand_dir_out", "cand_target_out", "cand_source_out")]
+
+
 class pg_lights_params(C.Structure):  # include/ext/pg_lights.h
     _fields_ = [("delta", C.c_float), ("root", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -162,6 +168,7 @@ PG_TARGET_SECOND_MOMENT = 1
 PG_BOUNCE_NONE, PG_BOUNCE_PDF, PG_BOUNCE_SAMPLE, PG_BOUNCE_CHOOSE = 0, 1, 2, 3
 PG_RESAMPLE_MAX_CANDIDATES, PG_RESAMPLE_NONE = 64, 0xFFFFFFFF
 PG_LIGHTS_MAX, PG_LIGHTS_WEIGHT_ONE, PG_LIGHTS_NONE = 4096, 65536, 0xFFFFFFFF
+PG_RESAMPLE_LOBE_MIN_ROUGHNESS = 1e-3  # (the header's 1e-3f: the float32 nearest to it)
 
 V, U64, I32, U32, F32, P = C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_float, C.POINTER
 _RR = [V, U64, V, V, V, V, P(pg_rr_params), V, V, V, V, V, V, V]  # pg_radiance_rr and pg_irradiance_rr
@@ -254,18 +261,29 @@ SURFACE_EXT = {
     },
 }
 (EXPORTS_LIGHTS,) = (tuple(entry_points) for entry_points in SURFACE_EXT.values())
+# Entry points of every LATER header, keyed by the header's path under include/ at ANY depth: a fourth table, because the tests of
+# SURFACE_EXT pin it to its one header and include/*/*.h to that file, so this one's first header lies a directory deeper
+# (DESIGN.md 5.24).  It is the LAST table: the next header JOINS it -- nothing pins it to one header, to one depth or its glob to
+# one file, and its tests must not start to -- it does not get a fifth.  lib() binds it after the other three, source_hash()
+# hashes its headers after theirs.
+SURFACE_MORE = {
+    "ext/guiding/pg_resample_lobe.h": {  # product guiding for glossy surfaces: resampling against a GGX reflection lobe
+        "pg_resample_lobe": [V, U64, P(pg_resample_params), P(pg_resample_lobe_args), V],
+    },
+}
+EXPORTS_MORE = tuple(name for entry_points in SURFACE_MORE.values() for name in entry_points)
 
 
 def source_hash() -> str:
     """sha256 (16 hex digits) over the library's sources (csrc/*.hip, csrc/*.hpp, then the headers of SURFACE in its order, then
-    those of SURFACE_EXTRA, then those of SURFACE_EXT):
+    those of SURFACE_EXTRA, then those of SURFACE_EXT, then those of SURFACE_MORE):
     names the code a profile was taken of (profiles/pmc_traffic.json) so that bench.py never pairs old counters with new kernels."""
     import glob
     import hashlib
     h = hashlib.sha256()
     files = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
     files += [os.path.join(os.path.dirname(_PKG), "include", *header.split("/"))
-              for header in list(SURFACE) + list(SURFACE_EXTRA) + list(SURFACE_EXT)]
+              for header in list(SURFACE) + list(SURFACE_EXTRA) + list(SURFACE_EXT) + list(SURFACE_MORE)]
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
@@ -304,7 +322,8 @@ def lib() -> C.CDLL:
     if L.pg_abi_version() != ABI_VERSION:  # (a library left over from an older build: its structs have other layouts)
         raise ImportError(f"{LIB_PATH} has ABI version {L.pg_abi_version()}, these bindings are written for {ABI_VERSION}: "
                           "rebuild it with `python -c 'import __graft_entry__ as g; g.build()'`")
-    for entry_points in list(SURFACE.values()) + list(SURFACE_EXTRA.values()) + list(SURFACE_EXT.values()):
+    for entry_points in list(SURFACE.values()) + list(SURFACE_EXTRA.values()) + list(SURFACE_EXT.values()) + list(
+            SURFACE_MORE.values()):
         for name, argtypes in entry_points.items():
             fn = getattr(L, name)  # (a missing symbol is an AttributeError here)
             fn.argtypes = list(argtypes)

@@ -684,6 +684,42 @@ class SDTree:
         self._ck(self._lib.pg_resample_cosine(self._h, n, C.byref(prm), C.byref(a), _stream_ptr()))
         return d, w, info
 
+    def resampleLobe(self, position: torch.Tensor, normal: torch.Tensor, wi: torch.Tensor, roughness: torch.Tensor,
+                     specular: torch.Tensor, sampler: PCG32Sampler, candidates: int = 8, alpha: float = 0.5, delta: float = 0.1,
+                     active: Optional[torch.Tensor] = None,
+                     return_candidates: bool = False) -> Tuple[torch.Tensor, torch.Tensor, Dict[str, torch.Tensor]]:
+        """(direction float32 (3, N), weight float32 (N,), info) (pg_resample_lobe): a direction in proportion to the tree's
+        radiance times a glossy lobe about `normal`, by resampled importance sampling -- `candidates` draws from the mixture
+        of the lobe (share `alpha`) and the tree, one kept in proportion to target over source.  The lobe of a lane is
+        specular * (the GGX visible-normal density of reflecting `wi`, the world direction towards the viewer, at `roughness`
+        in [1e-3, 1]) + (1 - specular) * the clamped cosine; `roughness` and `specular` are float32 (N,), all vectors are used
+        as given.  The target is the lobe times (delta / 4 pi + (1 - delta) * the tree's density).  The estimator is
+        f(direction) * weight with f the whole integrand; weight is 0 where nothing could be kept, and on lanes whose inputs
+        the header calls invalid.  One kernel, one KD descent.  info is resampleCosine's: {"target", "source" float32 (N,),
+        "index" int32 (N,)}; with return_candidates also {"cand_dir" float32 (M, 3, N), "cand_target", "cand_source" float32
+        (M, N)}.  The lanes' streams advance by the candidates' draws."""
+        n = position.shape[1]
+        _f32(position, (3, n)); _f32(normal, (3, n)); _f32(wi, (3, n)); _f32(roughness, (n,)); _f32(specular, (n,))
+        if sampler.n != n:
+            raise ValueError("the sampler must have one stream per lane")
+        m, mp = _mask(active, n)
+        M = int(candidates)
+        prm = N.pg_resample_params(M & 0xFFFFFFFF if M >= 0 else 0, float(alpha), float(delta), 0)
+        a = N.pg_resample_lobe_args()
+        a.p, a.normal, a.wi, a.active = position.data_ptr(), normal.data_ptr(), wi.data_ptr(), mp
+        a.roughness, a.specular = roughness.data_ptr(), specular.data_ptr()
+        a.rng_state, a.rng_inc = sampler.state.data_ptr(), sampler.inc.data_ptr()
+        d, w = self._new(3, n), self._new(n)
+        info = {"target": self._new(n), "source": self._new(n), "index": self._new(n, dtype=torch.int32)}
+        a.dir_out, a.weight_out = d.data_ptr(), w.data_ptr()
+        a.target_out, a.source_out, a.index_out = info["target"].data_ptr(), info["source"].data_ptr(), info["index"].data_ptr()
+        if return_candidates and 1 <= M <= N.PG_RESAMPLE_MAX_CANDIDATES:  # (any other M is refused below, before a launch)
+            info["cand_dir"], info["cand_target"], info["cand_source"] = self._new(M, 3, n), self._new(M, n), self._new(M, n)
+            a.cand_dir_out = info["cand_dir"].data_ptr()
+            a.cand_target_out, a.cand_source_out = info["cand_target"].data_ptr(), info["cand_source"].data_ptr()
+        self._ck(self._lib.pg_resample_lobe(self._h, n, C.byref(prm), C.byref(a), _stream_ptr()))
+        return d, w, info
+
     def exportPassRecords(self, slot: int = 0) -> Dict[str, torch.Tensor]:
         """The kept path-vertex records of the most recent render pass of buffer set `slot` (pg_render_export_records): a
         recording pass of a WavefrontScene(record_geometry=True); anything else raises.  Returns the columns addDataPropagate
