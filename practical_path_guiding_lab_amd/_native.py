@@ -79,6 +79,12 @@ class pg_resample_lobe_args(C.Structure):  # include/ext/guiding/pg_resample_lob
         "source_out", "index_out", "cand_dir_out", "cand_target_out", "cand_source_out")]
 
 
+class pg_resample_interface_args(C.Structure):  # include/ext/guiding/pg_resample_interface.h
+    _fields_ = [(n, C.c_void_p) for n in (
+        "p", "normal", "wi", "roughness", "eta", "active", "rng_state", "rng_inc", "dir_out", "weight_out", "target_out",
+        "source_out", "index_out", "eta_out", "cand_dir_out", "cand_target_out", "cand_source_out")]
+
+
 class pg_lights_params(C.Structure):  # include/ext/pg_lights.h
     _fields_ = [("delta", C.c_float), ("root", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -169,6 +175,8 @@ PG_BOUNCE_NONE, PG_BOUNCE_PDF, PG_BOUNCE_SAMPLE, PG_BOUNCE_CHOOSE = 0, 1, 2, 3
 PG_RESAMPLE_MAX_CANDIDATES, PG_RESAMPLE_NONE = 64, 0xFFFFFFFF
 PG_LIGHTS_MAX, PG_LIGHTS_WEIGHT_ONE, PG_LIGHTS_NONE = 4096, 65536, 0xFFFFFFFF
 PG_RESAMPLE_LOBE_MIN_ROUGHNESS = 1e-3  # (the header's 1e-3f: the float32 nearest to it)
+PG_RESAMPLE_INTERFACE_MIN_ROUGHNESS = 1e-3  # (likewise)
+PG_RESAMPLE_INTERFACE_MIN_ETA, PG_RESAMPLE_INTERFACE_MAX_ETA = 0.25, 4.0
 
 V, U64, I32, U32, F32, P = C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_float, C.POINTER
 _RR = [V, U64, V, V, V, V, P(pg_rr_params), V, V, V, V, V, V, V]  # pg_radiance_rr and pg_irradiance_rr
@@ -269,6 +277,9 @@ SURFACE_EXT = {
 SURFACE_MORE = {
     "ext/guiding/pg_resample_lobe.h": {  # product guiding for glossy surfaces: resampling against a GGX reflection lobe
         "pg_resample_lobe": [V, U64, P(pg_resample_params), P(pg_resample_lobe_args), V],
+    },
+    "ext/guiding/pg_resample_interface.h": {  # product guiding through rough glass: the two-sided lobe of a rough dielectric
+        "pg_resample_interface": [V, U64, P(pg_resample_params), P(pg_resample_interface_args), V],
     },
 }
 EXPORTS_MORE = tuple(name for entry_points in SURFACE_MORE.values() for name in entry_points)

@@ -720,6 +720,46 @@ class SDTree:
         self._ck(self._lib.pg_resample_lobe(self._h, n, C.byref(prm), C.byref(a), _stream_ptr()))
         return d, w, info
 
+    def resampleInterface(self, position: torch.Tensor, normal: torch.Tensor, wi: torch.Tensor, roughness: torch.Tensor,
+                          eta: torch.Tensor, sampler: PCG32Sampler, candidates: int = 8, alpha: float = 0.5, delta: float = 0.1,
+                          active: Optional[torch.Tensor] = None,
+                          return_candidates: bool = False) -> Tuple[torch.Tensor, torch.Tensor, Dict[str, torch.Tensor]]:
+        """(direction float32 (3, N), weight float32 (N,), info) (pg_resample_interface): a direction in proportion to the
+        tree's radiance times the two-sided lobe of a rough dielectric interface, by resampled importance sampling --
+        `candidates` draws from the mixture of the lobe (share `alpha`) and the tree, one kept in proportion to target over
+        source.  The lobe of a lane is the density of the renderer's rough dielectric: `wi`, the world direction towards the
+        viewer on either side of the surface, reflected (share Fresnel) or refracted about a GGX visible normal at `roughness`
+        in [1e-3, 1]; `normal` points to the exterior and `eta` is int_ior / ext_ior in [0.25, 4], not 1; `roughness` and `eta`
+        are float32 (N,), all vectors are used as given.  The target is the lobe times (delta / 4 pi + (1 - delta) * the
+        tree's density).  The estimator is f(direction) * weight with f the whole integrand; weight is 0 where nothing could
+        be kept, and on lanes whose inputs the header calls invalid.  One kernel, one KD descent.  info is resampleLobe's
+        {"target", "source" float32 (N,), "index" int32 (N,)} and "eta" float32 (N,): 1 for a kept direction on wi's side,
+        else the relative index the path enters (eta from above, 1 / eta from below), 0 with nothing kept; with
+        return_candidates also {"cand_dir" float32 (M, 3, N), "cand_target", "cand_source" float32 (M, N)}.  The lanes'
+        streams advance by the candidates' draws."""
+        n = position.shape[1]
+        _f32(position, (3, n)); _f32(normal, (3, n)); _f32(wi, (3, n)); _f32(roughness, (n,)); _f32(eta, (n,))
+        if sampler.n != n:
+            raise ValueError("the sampler must have one stream per lane")
+        m, mp = _mask(active, n)
+        M = int(candidates)
+        prm = N.pg_resample_params(M & 0xFFFFFFFF if M >= 0 else 0, float(alpha), float(delta), 0)
+        a = N.pg_resample_interface_args()
+        a.p, a.normal, a.wi, a.active = position.data_ptr(), normal.data_ptr(), wi.data_ptr(), mp
+        a.roughness, a.eta = roughness.data_ptr(), eta.data_ptr()
+        a.rng_state, a.rng_inc = sampler.state.data_ptr(), sampler.inc.data_ptr()
+        d, w = self._new(3, n), self._new(n)
+        info = {"target": self._new(n), "source": self._new(n), "index": self._new(n, dtype=torch.int32), "eta": self._new(n)}
+        a.dir_out, a.weight_out = d.data_ptr(), w.data_ptr()
+        a.target_out, a.source_out, a.index_out = info["target"].data_ptr(), info["source"].data_ptr(), info["index"].data_ptr()
+        a.eta_out = info["eta"].data_ptr()
+        if return_candidates and 1 <= M <= N.PG_RESAMPLE_MAX_CANDIDATES:  # (any other M is refused below, before a launch)
+            info["cand_dir"], info["cand_target"], info["cand_source"] = self._new(M, 3, n), self._new(M, n), self._new(M, n)
+            a.cand_dir_out = info["cand_dir"].data_ptr()
+            a.cand_target_out, a.cand_source_out = info["cand_target"].data_ptr(), info["cand_source"].data_ptr()
+        self._ck(self._lib.pg_resample_interface(self._h, n, C.byref(prm), C.byref(a), _stream_ptr()))
+        return d, w, info
+
     def exportPassRecords(self, slot: int = 0) -> Dict[str, torch.Tensor]:
         """The kept path-vertex records of the most recent render pass of buffer set `slot` (pg_render_export_records): a
         recording pass of a WavefrontScene(record_geometry=True); anything else raises.  Returns the columns addDataPropagate
