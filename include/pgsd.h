@@ -771,6 +771,40 @@ int pg_vertex_probe(pg_context *ctx, uint64_t n, uint64_t n_mat, const float *d_
                     const pg_vertex_lanes *lanes, float frac, int32_t guided, int32_t record, int32_t store_nee, int32_t rr_depth,
                     const pg_vertex_out *out, void *stream);
 
+/* The head of one path vertex by itself, for tests: lane i goes through the very device function the render kernels call
+ * between the closest hit and the SD-tree calls (stage_a of csrc/pg_render_stages.hpp, that is stage_a1 then stage_a2) at the
+ * scene's feature level -- the surface at the hit, wi, emitted radiance with its MIS weight against emitter sampling from the
+ * previous vertex, active_next, the emitter sample and the BSDF towards it, the shadow ray, the BSDF sample, wo in the world
+ * and the lane's class.  Needs a scene (pg_scene_set).  The lane's inputs are columns (pg_head_lanes; a 3-vector column
+ * holds lane i at [3 i ..]): the ray, the path's throughput, the previous vertex with its BSDF pdf and delta flag, the hit as
+ * pg_scene_intersect reports it (prim -1: a miss), the depth and the sampler.  The outputs are every field of the stage's
+ * result; flags holds the lane's class, the eight bits PG_VERTEX_* above and */
+#define PG_VERTEX_ACTIVE_EM 4u    /* emitter sampling happened and the sample's density is not zero */
+#define PG_VERTEX_NEED_SHADOW 8u  /* em_w holds the unoccluded value: (sh_o, sh_d, sh_tmax) is to be cast */
+#define PG_VERTEX_BSDF_MIS 256u   /* wo is the BSDF's, woPdf the mixture */
+typedef struct pg_head_lanes {    /* device pointers, n lanes each */
+	const float *ray_o, *ray_d, *thr, *prev_p; /* float[3 n] each */
+	const float *prev_bsdf_pdf;            /* float[n] */
+	const int32_t *prev_delta;             /* int32[n]: the previous vertex sampled a delta lobe (the camera counts as one) */
+	const int32_t *prim;                   /* int32[n]: the shape hit, -1 for a miss (checked on the host) */
+	const float *t, *uv;                   /* float[n], float[2 n] */
+	const uint32_t *depth;                 /* uint32[n] */
+	const uint64_t *rng_state, *rng_inc;   /* uint64[n] each: the lane's sampler, as pg_sample takes it */
+} pg_head_lanes;
+typedef struct pg_head_out {      /* device pointers */
+	float *p, *n, *ng, *wi, *refl, *Le, *ds_d, *em_w, *bv_em, *sh_o, *sh_d, *wo, *bsdf_w; /* float[3 n] each */
+	float *ds_pdf, *bp_em, *sh_tmax, *bsdf_pdf, *eta; /* float[n] each */
+	int32_t *mat;                          /* int32[n]: the material row (0 at feature level 0 and for a miss) */
+	uint32_t *flags;                       /* uint32[n] */
+	uint64_t *rng_state;                   /* uint64[n]: the sampler after the head's draws (2, or 6 where PG_VERTEX_ACTIVE_NEXT) */
+} pg_head_out;
+/* Call parameters: max_depth (>= 1), frac (the BSDF sampling fraction), guided.  Any float is safe in any column.  n = 0 does
+ * nothing; no scene, max_depth < 1, n > 2^20, a NULL pointer (the structs', or any of their members) and a shape number
+ * outside [-1, shapes of the scene) are refused.  Synchronises the stream (before reading the shape numbers back, and after
+ * the kernel). */
+int pg_head_probe(pg_context *ctx, uint64_t n, const pg_head_lanes *lanes, int32_t max_depth, float frac, int32_t guided,
+                  const pg_head_out *out, void *stream);
+
 /* Per-kernel device time of pg_render_pass, measured with HIP events recorded on the launch
  * stream around each kernel (off by default).  pg_read_kernel_timing synchronises. */
 typedef struct pg_kernel_timing {

@@ -720,6 +720,56 @@ def vertex_probe(materials, lanes, level, frac, guided, record, store_nee, rr_de
     return out
 
 
+# pgo_head_lanes and pgo_head_out of pg_oracle_render.h, in the structs' order: (column, dtype, components per lane)
+HEAD_LANES = (("ray_o", np.float32, 3), ("ray_d", np.float32, 3), ("thr", np.float32, 3), ("prev_p", np.float32, 3),
+              ("prev_bsdf_pdf", np.float32, 1), ("prev_delta", np.int32, 1), ("prim", np.int32, 1), ("t", np.float32, 1),
+              ("uv", np.float32, 2), ("depth", np.uint32, 1), ("rng_state", np.uint64, 1), ("rng_inc", np.uint64, 1))
+HEAD_VECTORS = ("p", "n", "ng", "wi", "refl", "Le", "ds_d", "em_w", "bv_em", "sh_o", "sh_d", "wo", "bsdf_w")
+HEAD_SCALARS = ("ds_pdf", "bp_em", "sh_tmax", "bsdf_pdf", "eta")
+HEAD_OUT = tuple((k, np.float32, 3) for k in HEAD_VECTORS) + tuple((k, np.float32, 1) for k in HEAD_SCALARS) + \
+    (("mat", np.int32, 1), ("flags", np.uint32, 1), ("rng_state", np.uint64, 1))
+F_ACTIVE_EM, F_NEED_SHADOW, F_BSDF_MIS = 4, 8, 256
+
+
+def head_lanes(lanes):
+    """the columns of HEAD_LANES out of a dict, contiguous and of their types -> (n, [arrays in the struct's order])"""
+    n = np.asarray(lanes["prim"]).reshape(-1).shape[0]
+    return n, [np.ascontiguousarray(lanes[k], t).reshape((n, w) if w > 1 else (n,)) for k, t, w in HEAD_LANES]
+
+
+def head_outputs(n):
+    """fresh output columns of HEAD_OUT (the advanced sampler state as "rng_out")"""
+    return {("rng_out" if k == "rng_state" else k): np.zeros((n, w) if w > 1 else (n,), t) for k, t, w in HEAD_OUT}
+
+
+def head_probe(scene_obj, lanes, max_depth, frac, guided, level=None):
+    """pgo_head_probe: the head of one path vertex (vertex_head of pg_oracle_render.c, which the render pass calls) over
+    arrays.  lanes: dict of the columns HEAD_LANES (prim -1: a miss) -> dict of the columns HEAD_OUT (the advanced sampler
+    state as "rng_out").  level: the device's feature level (None: feature_level(scene))."""
+    lb = lib()
+
+    class Lanes(C.Structure):
+        _fields_ = [(k, _P) for k, _, _ in HEAD_LANES]
+
+    class Out(C.Structure):
+        _fields_ = [(k, _P) for k, _, _ in HEAD_OUT]
+
+    lb.pgo_head_probe.argtypes = [C.POINTER(_Scene), C.c_size_t, C.c_int, C.POINTER(Lanes), C.c_int, C.c_float, C.c_int, C.POINTER(Out)]
+    lb.pgo_head_probe.restype = None
+    sc, keep = _scene_struct(scene_obj, None, None, None, None)
+    n, cols = head_lanes(lanes)
+    prim = cols[[k for k, _, _ in HEAD_LANES].index("prim")]
+    n_shapes = keep[0].shape[0] + keep[1].shape[0] + 6 * keep[3].shape[0] + keep[4].shape[0]
+    assert int(max_depth) >= 1 and (n == 0 or (prim.min() >= -1 and prim.max() < n_shapes))
+    out = head_outputs(n)
+    li = Lanes(*[_ptr(c) for c in cols])
+    oo = Out(*[_ptr(out["rng_out" if k == "rng_state" else k]) for k, _, _ in HEAD_OUT])
+    lb.pgo_head_probe(C.byref(sc), n, feature_level(scene_obj) if level is None else int(level), C.byref(li), int(max_depth),
+                      float(frac), int(bool(guided)), C.byref(oo))
+    del keep
+    return out
+
+
 def render_pass(pair: "OracleSDTreePair", quads, cam, max_depth, rr_depth, iteration, is_final, seed, spp=1,
                 store_nee=True, bsdf_sampling_fraction=0.5, sumL=None, sumL2=None, spheres=None, materials=None,
                 boxes=None):

@@ -570,16 +570,7 @@ static void sample_emitter_ray(const pgo_scene *sc, const int *em, int n_em, v3 
 }
 
 
-/* ... with its visibility test (test_visibility=True): em_weight is zero where the shadow ray meets anything */
-static void sample_emitter(const pgo_scene *sc, const int *em, int n_em, v3 p, v3 n, float e1, float e2, v3 *ds_d,
-                           float *ds_pdf, v3 *em_weight, int *ds_delta)
-{
-	int need_shadow;
-	v3 sh_o, sh_d;
-	float sh_tmax, th;
-	sample_emitter_ray(sc, em, n_em, p, n, e1, e2, ds_d, ds_pdf, em_weight, ds_delta, &need_shadow, &sh_o, &sh_d, &sh_tmax);
-	if (need_shadow && intersect(sc, sh_o, sh_d, sh_tmax, &th) >= 0) *em_weight = V(0, 0, 0);
-}
+/* (its visibility test, test_visibility=True, is the caller's: the render pass casts the shadow ray vertex_head hands back) */
 
 /* Emitter sampling of the render pass by itself: lane i makes one call of sample_emitter_ray from the point p[3 i ..] with
  * the geometric normal nrm[3 i ..] and the sample e[2 i ..], against the emitter list the render pass builds (flagged quads,
@@ -999,14 +990,15 @@ void pgo_bsdf_sample_full(const float *m, const float wi[3], float lobe, float u
 /* The material a render kernel of feature level `level` makes of a row (the device's load_material and the kGeneral tests of
  * its bsdf_eval_pdf<> / bsdf_sample<>): level 0 knows two-sided diffuse only and reads every row as that; levels 1 and 2 know
  * roughconductor besides; one-sided rows and the types from the smooth conductor on are honoured from level 3 only. */
-static material load_material_at_level(const float *M, int level)
+static material material_at_level(material mt, int level)
 {
-	material mt = load_material(M);
 	if (level < 3) mt.one_sided = 0;
 	if (level < 3 && mt.type >= 2) mt.type = 0;
 	if (level < 1) mt.type = 0;
 	return mt;
 }
+
+static material load_material_at_level(const float *M, int level) { return material_at_level(load_material(M), level); }
 
 void pgo_bsdf_probe(size_t n, const float *materials, const int32_t *material_index, const float *wi, const float *wo,
                     const float *u, int level, float *value, float *pdf, float *sampled_wo, float *sampled_pdf, float *weight,
@@ -1178,6 +1170,124 @@ void pgo_vertex_probe(size_t n, size_t n_mat, const float *materials, int level,
 	}
 }
 
+/* ---- the head of one path vertex (:185-220, 272-297): the surface at the hit, wi, emitted radiance with its MIS weight against
+ * emitter sampling from the PREVIOUS vertex, active_next, the emitter sample and the BSDF towards it, the BSDF sample, wo in
+ * the world and the lane's class.  The device's stage_a<> (stage_a1 then stage_a2 of csrc/pg_render_stages.hpp), operation by
+ * operation: a feature level, the flags word with all eleven bits, and the shadow ray handed back for the caller to cast
+ * (PGO_F_NEED_SHADOW).  The lane loop of pgo_render_pass_scene and pgo_head_probe call it. ---- */
+typedef struct {
+	v3 p, n, ng, wi, refl, Le, ds_d, em_w, bv_em, sh_o, sh_d, wo, bsdf_w;
+	float ds_pdf, bp_em, sh_tmax, bsdf_pdf, eta;
+	int mat;        /* the row of the material table (0 at level 0, and for a miss) */
+	uint32_t flags; /* PGO_F_* */
+	material mt;    /* the vertex's material as a kernel of that level reads it, with the reflectance the surface left */
+} vertex_head_out;
+
+/* em, n_em, inv_em_count: the emitter list of the render pass; q, t_hit: the hit (q < 0: the ray left the scene); D: max_depth */
+static void vertex_head(const pgo_scene *sc, const int *em, int n_em, float inv_em_count, int level, v3 ray_o, v3 ray_d, v3 thr,
+                        v3 prev_p, float prev_bsdf_pdf, int prev_delta, int q, float t_hit, uint32_t depth, int D, float f, int guided,
+                        pgo_pcg32 *rng, vertex_head_out *o)
+{
+	const int valid = q >= 0;
+	surface sf;
+	memset(&sf, 0, sizeof sf);
+	sf.n = V(0, 0, 1);
+	if (valid) sf = surface_at(sc, q, ray_o, ray_d, t_hit);
+	if (sf.ng.x == 0.0f && sf.ng.y == 0.0f && sf.ng.z == 0.0f) sf.ng = sf.n; /* every shape but a smooth-shaded triangle */
+	const v3 p = sf.p, n = sf.n, ng = sf.ng;
+	o->mt = material_at_level(sf.m, level);
+	const material *mt = &o->mt;
+	frame fr;
+	fr.n = n;
+	frame_from_normal(n, &fr.s, &fr.t);
+	const v3 wi = to_local(&fr, V(-ray_d.x, -ray_d.y, -ray_d.z));
+	const int is_em = valid && sf.is_em;
+	/* ---- :189-200 direct emission ---- */
+	const v3 em_radiance = (is_em && wi.z > 0.0f) ? sf.radiance : V(0, 0, 0);
+	float emitter_pdf = 0.0f;
+	if (is_em && !prev_delta) emitter_pdf = emitter_hit_pdf(sc, q, prev_p, p, n, inv_em_count);
+	const float mis = mis_weight(prev_bsdf_pdf, emitter_pdf);
+	const v3 Le = vmul(vscale(thr, mis), em_radiance);
+	/* ---- :207-220 emitter sampling ---- */
+	const int active_next = (depth + 1 < (uint32_t)D) && valid;
+	int active_em = active_next && material_is_smooth(mt); /* :210 BSDFFlags.Smooth */
+	const float e1 = pgo_pcg32_next_f32(rng), e2 = pgo_pcg32_next_f32(rng); /* :214 next_2d, unmasked */
+	int ds_delta = 0, need_shadow = 0;
+	o->ds_d = V(0, 0, 0); o->em_w = V(0, 0, 0); o->ds_pdf = 0.0f;
+	o->sh_o = V(0, 0, 0); o->sh_d = V(0, 0, 1); o->sh_tmax = 0.0f;
+	if (active_em)
+		sample_emitter_ray(sc, em, n_em, p, ng, e1, e2, &o->ds_d, &o->ds_pdf, &o->em_w, &ds_delta, &need_shadow, &o->sh_o, &o->sh_d,
+		                   &o->sh_tmax);
+	active_em = active_em && (o->ds_pdf != 0.0f); /* :216 */
+	const v3 wo_em = to_local(&fr, o->ds_d);
+	bsdf_eval_pdf(mt, wi, wo_em, active_em, &o->bv_em, &o->bp_em);
+	/* an emitter sample whose BSDF value is zero and whose weight is finite adds +0 whatever the shadow ray finds: no ray */
+	const int nee_live = vertex_nee_live(active_em, o->bv_em, o->em_w);
+	if (!nee_live) need_shadow = 0;
+	/* ---- :272-297 next direction ---- */
+	float s1 = 0.0f, s2x = 0.0f, s2y = 0.0f;
+	if (active_next) { /* next_1d (the lobe choice: only the dielectrics, which exist from level 3 on, read it), next_2d */
+		const float lobe = pgo_pcg32_next_f32(rng);
+		if (level >= 3) s1 = lobe;
+		s2x = pgo_pcg32_next_f32(rng);
+		s2y = pgo_pcg32_next_f32(rng);
+	}
+	v3 wo_local;
+	int delta;
+	bsdf_sample(mt, wi, s1, s2x, s2y, active_next, &wo_local, &o->bsdf_pdf, &o->bsdf_w, &o->eta, &delta);
+	o->wo = to_world(&fr, wo_local);
+	const int do_mis = active_next && !delta && guided; /* :283 */
+	int pick_tree = 0;
+	if (active_next) pick_tree = pgo_pcg32_next_f32(rng) > f; /* :286 */
+	const int smp_tree = pick_tree && do_mis;
+	const int bsdf_mis = do_mis && !smp_tree;
+	o->p = p; o->n = n; o->ng = ng; o->wi = wi; o->refl = mt->refl; o->Le = Le;
+	o->mat = (level > 0 && valid) ? sf.row : 0;
+	o->flags = (valid ? PGO_F_VALID : 0u) | (active_next ? PGO_F_ACTIVE_NEXT : 0u) | (active_em ? PGO_F_ACTIVE_EM : 0u) |
+	           (need_shadow ? PGO_F_NEED_SHADOW : 0u) | (ds_delta ? PGO_F_DS_DELTA : 0u) | (delta ? PGO_F_DELTA : 0u) |
+	           (do_mis ? PGO_F_DO_MIS : 0u) | (smp_tree ? PGO_F_SMP_TREE : 0u) | (bsdf_mis ? PGO_F_BSDF_MIS : 0u) |
+	           (nee_live ? PGO_F_NEE_LIVE : 0u) | ((pgo_f2u(Le.x) | pgo_f2u(Le.y) | pgo_f2u(Le.z)) != 0u ? PGO_F_HAS_LE : 0u);
+}
+
+/* the emitter list of the render pass: flagged quads, then flagged spheres, then the directional lights as negative codes
+ * (one entry more than the list can hold: never malloc(0)) */
+static int *emitter_list(const pgo_scene *sc, int *n_out)
+{
+	int *em = malloc((sc->n_quads + sc->n_spheres + sc->n_dir_lights + 1) * sizeof(int));
+	int n_em = 0;
+	for (size_t q = 0; q < sc->n_quads; ++q)
+		if (sc->quads[q * PGO_QUAD_STRIDE + 15] != 0.0f) em[n_em++] = (int)q;
+	for (size_t s = 0; s < sc->n_spheres; ++s)
+		if (sc->spheres[s * PGO_SPHERE_STRIDE + 5] != 0.0f) em[n_em++] = (int)(sc->n_quads + s);
+	for (size_t k = 0; k < sc->n_dir_lights; ++k) em[n_em++] = -1 - (int)k;
+	*n_out = n_em;
+	return em;
+}
+
+void pgo_head_probe(const pgo_scene *sc, size_t n, int level, const pgo_head_lanes *in, int max_depth, float frac, int guided,
+                    const pgo_head_out *out)
+{
+	int n_em;
+	int *em = emitter_list(sc, &n_em);
+	const float inv_em_count = n_em > 0 ? 1.0f / (float)n_em : 0.0f;
+	for (size_t i = 0; i < n; ++i) {
+		pgo_pcg32 rng = { in->rng_state[i], in->rng_inc[i] };
+		vertex_head_out H;
+		vertex_head(sc, em, n_em, inv_em_count, level, ld3(in->ray_o + 3 * i), ld3(in->ray_d + 3 * i), ld3(in->thr + 3 * i),
+		            ld3(in->prev_p + 3 * i), in->prev_bsdf_pdf[i], in->prev_delta[i] != 0, in->prim[i], in->t[i], in->depth[i], max_depth,
+		            frac, guided, &rng, &H);
+		const v3 *src[13] = { &H.p, &H.n, &H.ng, &H.wi, &H.refl, &H.Le, &H.ds_d, &H.em_w, &H.bv_em, &H.sh_o, &H.sh_d, &H.wo, &H.bsdf_w };
+		float *const dst[13] = { out->p, out->n, out->ng, out->wi, out->refl, out->Le, out->ds_d, out->em_w, out->bv_em, out->sh_o,
+		                         out->sh_d, out->wo, out->bsdf_w };
+		for (int k = 0; k < 13; ++k) { dst[k][3 * i] = src[k]->x; dst[k][3 * i + 1] = src[k]->y; dst[k][3 * i + 2] = src[k]->z; }
+		out->ds_pdf[i] = H.ds_pdf; out->bp_em[i] = H.bp_em; out->sh_tmax[i] = H.sh_tmax; out->bsdf_pdf[i] = H.bsdf_pdf; out->eta[i] = H.eta;
+		out->mat[i] = H.mat;
+		out->flags[i] = H.flags;
+		out->rng_state[i] = rng.state;
+	}
+	free(em);
+}
+
 void pgo_render_pass(const pgo_tree *prev, pgo_tree *current, size_t nq, const float *quads,
                      const pgo_camera *cam, const pgo_render_params *prm, float *L_out, uint8_t *valid_out,
                      float *sumL, float *sumL2)
@@ -1245,38 +1355,18 @@ void pgo_render_pass_scene(const pgo_tree *prev, pgo_tree *current, const pgo_sc
 			/* ---- :185 ray_intersect ---- */
 			float t_hit;
 			int q = intersect(sc, ray_o, ray_d, INFINITY, &t_hit);
-			int valid = q >= 0;
-			surface sf;
-			memset(&sf, 0, sizeof sf);
-			sf.n = V(0, 0, 1);
-			if (valid) sf = surface_at(sc, q, ray_o, ray_d, t_hit);
-			if (sf.ng.x == 0.0f && sf.ng.y == 0.0f && sf.ng.z == 0.0f) sf.ng = sf.n; /* every shape but a smooth-shaded triangle */
-			const v3 p = sf.p, n = sf.n, ng = sf.ng;
-			const material *mt = &sf.m;
-			frame fr;
-			fr.n = n;
-			frame_from_normal(n, &fr.s, &fr.t);
-			v3 wi = to_local(&fr, V(-ray_d.x, -ray_d.y, -ray_d.z));
-			int is_em = valid && sf.is_em;
-			/* ---- :189-200 direct emission ---- */
-			v3 em_radiance = (is_em && wi.z > 0.0f) ? sf.radiance : V(0, 0, 0);
-			float emitter_pdf = 0.0f;
-			if (is_em && !prev_delta) emitter_pdf = emitter_hit_pdf(sc, q, prev_p, p, n, inv_em_count);
-			float mis = mis_weight(prev_bsdf_pdf, emitter_pdf);
-			v3 Le = vmul(vscale(thr, mis), em_radiance);
-			/* ---- :207-220 emitter sampling ---- */
-			int active_next = (depth + 1 < (uint32_t)D) && valid;
-			int active_em = active_next && material_is_smooth(mt); /* :210 BSDFFlags.Smooth */
-			float e1 = pgo_pcg32_next_f32(&rng), e2 = pgo_pcg32_next_f32(&rng); /* :214 next_2d, unmasked */
-			v3 ds_d = V(0, 0, 0), em_weight = V(0, 0, 0);
-			float ds_pdf = 0.0f;
-			int ds_delta = 0;
-			if (active_em) sample_emitter(sc, em, n_em, p, ng, e1, e2, &ds_d, &ds_pdf, &em_weight, &ds_delta);
-			active_em = active_em && (ds_pdf != 0.0f); /* :216 */
-			v3 wo_em = to_local(&fr, ds_d);
-			v3 bsdf_value_em;
-			float bsdf_pdf_em;
-			bsdf_eval_pdf(mt, wi, wo_em, active_em, &bsdf_value_em, &bsdf_pdf_em);
+			/* ---- :185-220, 272-297: the vertex's head ---- */
+			vertex_head_out H;
+			vertex_head(sc, em, n_em, inv_em_count, 3, ray_o, ray_d, thr, prev_p, prev_bsdf_pdf, prev_delta, q, t_hit, depth, D, f, guided,
+			            &rng, &H);
+			const int valid = (H.flags & PGO_F_VALID) != 0u, active_em = (H.flags & PGO_F_ACTIVE_EM) != 0u;
+			const int smp_tree = (H.flags & PGO_F_SMP_TREE) != 0u, bsdf_mis = (H.flags & PGO_F_BSDF_MIS) != 0u;
+			const v3 p = H.p, ds_d = H.ds_d;
+			const material *mt = &H.mt;
+			v3 wo_world = H.wo;
+			/* the shadow ray (test_visibility=True of :214), where the head asks for it */
+			float th;
+			const int occluded = (H.flags & PGO_F_NEED_SHADOW) && intersect(sc, H.sh_o, H.sh_d, H.sh_tmax, &th) >= 0;
 			/* ---- :244 the SD-tree's pdf of the emitter direction ---- */
 			int active_sd_em = active_em && guided;
 			float pp[3] = { p.x, p.y, p.z };
@@ -1289,19 +1379,7 @@ void pgo_render_pass_scene(const pgo_tree *prev, pgo_tree *current, const pgo_sc
 				float dv[3] = { ds_d.x, ds_d.y, ds_d.z };
 				sdtree_pdf_em = pgo_i_pdf(prev, tree, dv, 1);
 			}
-			/* ---- :272-297 next direction ---- */
-			float s1 = 0.0f, s2x = 0.0f, s2y = 0.0f;
-			if (active_next) { s1 = pgo_pcg32_next_f32(&rng); s2x = pgo_pcg32_next_f32(&rng); s2y = pgo_pcg32_next_f32(&rng); }
-			v3 wo_local, bsdf_weight;
-			float bsdf_pdf, eta;
-			int delta;
-			bsdf_sample(mt, wi, s1, s2x, s2y, active_next, &wo_local, &bsdf_pdf, &bsdf_weight, &eta, &delta);
-			v3 wo_world = to_world(&fr, wo_local);
-			int do_mis = active_next && !delta && guided;
-			int pick_tree = 0;
-			if (active_next) pick_tree = pgo_pcg32_next_f32(&rng) > f; /* :286 */
-			int smp_tree = pick_tree && do_mis;
-			int bsdf_mis = do_mis && !smp_tree;
+			/* ---- :301, 307 the SD-tree's direction and pdf ---- */
 			float sdtree_pdf = 1.0f;
 			if (smp_tree) { /* :301 (the BSDF at that direction, :302-304: vertex_bookkeeping) */
 				if (!tree_known) { tree = pgo_i_quadtree_of(prev, pp, 1); tree_known = 1; }
@@ -1317,16 +1395,13 @@ void pgo_render_pass_scene(const pgo_tree *prev, pgo_tree *current, const pgo_sc
 			}
 			/* ---- :247-261, 302-311, 318-346, 352-378: the vertex's bookkeeping ---- */
 			vertex_in A;
-			A.p = p; A.n = n; A.ng = ng; A.wi = wi; A.Le = Le; A.em_w = em_weight; A.bv_em = bsdf_value_em; A.bsdf_w = bsdf_weight;
-			A.wo = wo_world; A.ds_pdf = ds_pdf; A.bp_em = bsdf_pdf_em; A.bsdf_pdf = bsdf_pdf; A.eta = eta;
+			A.p = p; A.n = H.n; A.ng = H.ng; A.wi = H.wi; A.Le = H.Le; A.em_w = H.em_w; A.bv_em = H.bv_em; A.bsdf_w = H.bsdf_w;
+			A.wo = wo_world; A.ds_pdf = H.ds_pdf; A.bp_em = H.bp_em; A.bsdf_pdf = H.bsdf_pdf; A.eta = H.eta;
 			A.pdf_nee = sdtree_pdf_em; A.pdf_tree = sdtree_pdf;
-			A.occluded = 0; /* (sample_emitter has cast the shadow ray: em_weight is zero behind an occluder) */
-			A.flags = (valid ? PGO_F_VALID : 0u) | (active_next ? PGO_F_ACTIVE_NEXT : 0u) | (ds_delta ? PGO_F_DS_DELTA : 0u) |
-			          (delta ? PGO_F_DELTA : 0u) | (do_mis ? PGO_F_DO_MIS : 0u) | (smp_tree ? PGO_F_SMP_TREE : 0u) |
-			          (vertex_nee_live(active_em, bsdf_value_em, em_weight) ? PGO_F_NEE_LIVE : 0u) |
-			          ((pgo_f2u(Le.x) | pgo_f2u(Le.y) | pgo_f2u(Le.z)) != 0u ? PGO_F_HAS_LE : 0u);
+			A.occluded = occluded;
+			A.flags = H.flags;
 			vertex_rec rec;
-			active_next = vertex_bookkeeping(&A, mt, 3, f, guided, record, prm->store_nee, prm->rr_depth, depth, &rng, &thr, &L, &ior,
+			const int active_next = vertex_bookkeeping(&A, mt, 3, f, guided, record, prm->store_nee, prm->rr_depth, depth, &rng, &thr, &L, &ior,
 			                                 &rec, &ray_o, &ray_d, &prev_bsdf_pdf, &prev_delta);
 			if (rec.recorded) { /* the record as the reference keeps it: position and directions beside what the bookkeeping gives */
 				size_t g = lane * (size_t)D + depth;

@@ -219,6 +219,36 @@ typedef struct pgo_vertex_out {
 void pgo_vertex_probe(size_t n, size_t n_mat, const float *materials, int level, const pgo_vertex_lanes *in, float frac, int guided,
                       int record, int store_nee, int rr_depth, const pgo_vertex_out *out);
 
+/* The head of one path vertex by itself (path_guiding_integrator.py:185-220, 272-297): the surface at the hit, wi, emitted
+ * radiance with its MIS weight against the previous vertex's emitter sampling, active_next, the emitter sample, the BSDF
+ * towards it, the BSDF sample, wo in the world and the lane's class -- the function the lane loop of pgo_render_pass_scene
+ * calls before the SD-tree calls and the bookkeeping, over arrays.  The flags are the device's F_*, all eleven: the eight
+ * above and */
+#define PGO_F_ACTIVE_EM 4u    /* emitter sampling happened and ds.pdf != 0 (:210, 216) */
+#define PGO_F_NEED_SHADOW 8u  /* em_w holds the unoccluded value: the caller casts (sh_o, sh_d, sh_tmax) */
+#define PGO_F_BSDF_MIS 256u   /* bsdf-mis: BSDF direction, SD-tree pdf (:293) */
+typedef struct pgo_head_lanes {
+	const float *ray_o, *ray_d, *thr, *prev_p; /* (n,3) each: the ray, the path's throughput, the previous vertex */
+	const float *prev_bsdf_pdf;       /* (n) */
+	const int32_t *prev_delta;        /* (n) */
+	const int32_t *prim;              /* (n): the shape hit, -1 for a miss */
+	const float *t, *uv;              /* (n), (n,2): the hit's distance; its barycentrics (the device's form of the hit: surface_at
+	                                     here derives them again from the ray, as it does in the render pass) */
+	const uint32_t *depth;            /* (n) */
+	const uint64_t *rng_state, *rng_inc; /* (n) each: the lane's sampler */
+} pgo_head_lanes;
+typedef struct pgo_head_out {
+	float *p, *n, *ng, *wi, *refl, *Le, *ds_d, *em_w, *bv_em, *sh_o, *sh_d, *wo, *bsdf_w; /* (n,3) each */
+	float *ds_pdf, *bp_em, *sh_tmax, *bsdf_pdf, *eta; /* (n) each */
+	int32_t *mat;                     /* (n): the row of the material table (0 at level 0 and for a miss) */
+	uint32_t *flags;                  /* (n) */
+	uint64_t *rng_state;              /* (n): the sampler after the head's 2 or 6 draws */
+} pgo_head_out;
+/* level: the feature level of the device kernel whose reading is wanted (how a material row is read, and whether the lobe
+ * draw's value is kept: level 3 only). */
+void pgo_head_probe(const pgo_scene *sc, size_t n, int level, const pgo_head_lanes *in, int max_depth, float frac, int guided,
+                    const pgo_head_out *out);
+
 /* Film reconstruction of one full-frame pass with Mitsuba's `tent` reconstruction filter, radius one
  * pixel (the <rfilter type="tent"/> of scenes/cornell-box/scene.xml:27): what mi.render returns at
  * main.py:218.  Sample s of pixel (px,py) sits at (px + jx, py + jy), its first two sampler draws;

@@ -105,6 +105,17 @@ class pg_vertex_out(C.Structure):
         "r_wp")]
 
 
+class pg_head_lanes(C.Structure):  # include/pgsd.h: the columns of pg_head_probe, device pointers
+    _fields_ = [(n, C.c_void_p) for n in (
+        "ray_o", "ray_d", "thr", "prev_p", "prev_bsdf_pdf", "prev_delta", "prim", "t", "uv", "depth", "rng_state", "rng_inc")]
+
+
+class pg_head_out(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in (
+        "p", "n", "ng", "wi", "refl", "Le", "ds_d", "em_w", "bv_em", "sh_o", "sh_d", "wo", "bsdf_w", "ds_pdf", "bp_em", "sh_tmax",
+        "bsdf_pdf", "eta", "mat", "flags", "rng_state")]
+
+
 class pg_tree_sizes(C.Structure):
     _fields_ = [("n_kd", C.c_uint64), ("n_quad", C.c_uint64), ("n_roots", C.c_uint64)]
 
@@ -218,6 +229,7 @@ SURFACE = {
         "pg_surface_probe": [V, U64, V, V, V, V, V, V, V, V, V],
         "pg_emitter_probe": [V, U64, V, V, V, V, V, V],
         "pg_vertex_probe": [V, U64, U64, V, I32, P(pg_vertex_lanes), F32, I32, I32, I32, I32, P(pg_vertex_out), V],
+        "pg_head_probe": [V, U64, P(pg_head_lanes), I32, F32, I32, P(pg_head_out), V],
     },
     "pgsd_warp.h": {  # sample warping: same library, same ABI version
         "pg_sample_warp": [V, U64, V, V, V, V, V, V], "pg_invert_warp": [V, U64, V, V, V, V, V, V],

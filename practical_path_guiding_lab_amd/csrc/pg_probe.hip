@@ -9,6 +9,8 @@
 // sample_emitter_ray<> with the scene's own emitter list, directional lights and bounding sphere, as stage_a1 passes them.
 // pg_vertex_probe: a vertex's bookkeeping by itself -- one lane per item through stage_b<> of pg_render_stages.hpp, fed with
 // columns that hold what StageA, GuideOut and the path state hold, its record planes the caller's output planes.
+// pg_head_probe: a vertex's head by itself -- one (ray, hit, path state, sampler) per lane through stage_a<> (stage_a1 then
+// stage_a2) of the same header at the scene's feature level, every field of StageA an output column.
 // Nothing of the product path launches these kernels.
 #include <string>
 #include <type_traits>
@@ -240,6 +242,43 @@ __global__ __launch_bounds__(kRBlock) void k_probe_vertex(VertexProbeArgs v)
 	o.rng_state[tid] = rng.state;
 }
 
+struct HeadProbeArgs {
+	RenderArgs a; // what stage_a reads of it: shapes, mats, dir_lights, emitters, n_emitters, max_depth, frac, guided
+	uint64_t n;
+	pg_head_lanes in;
+	pg_head_out out;
+};
+static_assert(sizeof(HeadProbeArgs) <= 4096, "kernel arguments are at most 4 KB");
+static_assert(PG_VERTEX_ACTIVE_EM == F_ACTIVE_EM && PG_VERTEX_NEED_SHADOW == F_NEED_SHADOW && PG_VERTEX_BSDF_MIS == F_BSDF_MIS,
+              "include/pgsd.h names the lane classes of pg_render_stages.hpp");
+
+// No loop but rc_sample_visible_11's three Newton steps; every address is a function of tid < n and of a checked shape number
+// (the rows a shape names -- material, texture, texels -- were checked by pg_scene_set_ex, and texture_eval wraps its texel
+// indices into the bitmap whatever the uv are) but the emitter's row, whose number sample_emitter_ray clamps to
+// [0, n_emitters) whatever the lane's own sampler draws and whose entry pg_scene_set_ex made from the scene's own counts.
+template <int kLevel>
+__global__ __launch_bounds__(kRBlock) void k_probe_head(HeadProbeArgs v)
+{
+	const uint64_t tid = (uint64_t)blockIdx.x * kRBlock + threadIdx.x;
+	if (tid >= v.n) return;
+	const pg_head_lanes &in = v.in;
+	Pcg32 rng;
+	rng.state = in.rng_state[tid]; rng.inc = in.rng_inc[tid];
+	HitRec h;
+	h.prim = in.prim[tid]; h.t = in.t[tid]; h.u = in.uv[2 * tid]; h.v = in.uv[2 * tid + 1];
+	StageA A;
+	stage_a<kLevel>(v.a, rng, ld3(in.ray_o + 3 * tid), ld3(in.ray_d + 3 * tid), ld3(in.thr + 3 * tid), ld3(in.prev_p + 3 * tid),
+	                in.prev_bsdf_pdf[tid], in.prev_delta[tid] != 0, h, in.depth[tid], A);
+	const pg_head_out &o = v.out;
+	auto put = [tid](float *d, v3 s) { d[3 * tid] = s.x; d[3 * tid + 1] = s.y; d[3 * tid + 2] = s.z; };
+	put(o.p, A.p); put(o.n, A.n); put(o.ng, A.ng); put(o.wi, A.wi); put(o.refl, A.refl); put(o.Le, A.Le); put(o.ds_d, A.ds_d);
+	put(o.em_w, A.em_w); put(o.bv_em, A.bv_em); put(o.sh_o, A.sh_o); put(o.sh_d, A.sh_d); put(o.wo, A.wo); put(o.bsdf_w, A.bsdf_w);
+	o.ds_pdf[tid] = A.ds_pdf; o.bp_em[tid] = A.bp_em; o.sh_tmax[tid] = A.sh_tmax; o.bsdf_pdf[tid] = A.bsdf_pdf; o.eta[tid] = A.eta;
+	o.mat[tid] = A.mat;
+	o.flags[tid] = A.flags;
+	o.rng_state[tid] = rng.state;
+}
+
 // What every probe does before it reads an argument, in the order in which a caller sees the refusals: the context, the
 // scene (where the probe reads one), the probe's first check of its own (own_first, own_last: the message, or nullptr where
 // the check passes), the lane count, n == 0 (PG_OK: nothing is read), the pointers, its last check, the device.
@@ -315,6 +354,48 @@ int pg_vertex_probe(pg_context *ctx, uint64_t n, uint64_t n_mat, const float *d_
 	v.a.frac = frac; v.a.guided = guided ? 1 : 0; v.a.record = record ? 1 : 0; v.a.store_nee = store_nee ? 1 : 0; v.a.rr_depth = rr_depth;
 	v.a.ray_of = out->ray_of; v.a.r_bsdf = out->r_bsdf; v.a.r_tb = out->r_tb; v.a.r_tr = out->r_tr; v.a.r_nee = out->r_nee; v.a.r_wp = out->r_wp;
 	return run_at_level(ctx, level, n, stream, v, [](auto L) { return k_probe_vertex<decltype(L)::value>; });
+}
+
+int pg_head_probe(pg_context *ctx, uint64_t n, const pg_head_lanes *lanes, int32_t max_depth, float frac, int32_t guided,
+                  const pg_head_out *out, void *stream)
+{
+	bool null_pointer = !lanes || !out;
+	if (lanes && out) {
+		const pg_head_lanes &l = *lanes;
+		const pg_head_out &o = *out;
+		for (const void *q : {(const void *)l.ray_o, (const void *)l.ray_d, (const void *)l.thr, (const void *)l.prev_p,
+		                      (const void *)l.prev_bsdf_pdf, (const void *)l.prev_delta, (const void *)l.prim, (const void *)l.t,
+		                      (const void *)l.uv, (const void *)l.depth, (const void *)l.rng_state, (const void *)l.rng_inc,
+		                      (const void *)o.p, (const void *)o.n, (const void *)o.ng, (const void *)o.wi, (const void *)o.refl,
+		                      (const void *)o.Le, (const void *)o.ds_d, (const void *)o.em_w, (const void *)o.bv_em, (const void *)o.sh_o,
+		                      (const void *)o.sh_d, (const void *)o.wo, (const void *)o.bsdf_w, (const void *)o.ds_pdf, (const void *)o.bp_em,
+		                      (const void *)o.sh_tmax, (const void *)o.bsdf_pdf, (const void *)o.eta, (const void *)o.mat,
+		                      (const void *)o.flags, (const void *)o.rng_state})
+			null_pointer = null_pointer || !q;
+	}
+	const int rc = probe_ready(ctx, "pg_head_probe", true, max_depth < 1 ? "max_depth must be at least 1" : nullptr, n, "lanes", null_pointer);
+	if (rc != kProbeGo) return rc;
+	const SceneState &sc = scene_state(ctx);
+	PG_HIP(ctx, hipStreamSynchronize((hipStream_t)stream)); // (the caller's writes of the inputs, before the host reads them)
+	// the shape numbers are checked on the host before a lane follows them (-1: the ray left the scene)
+	const int64_t n_shapes = (int64_t)sc.n_quads + sc.n_spheres + 6 * (int64_t)sc.n_boxes + (int64_t)sc.n_tris;
+	std::vector<int32_t> prim(n);
+	PG_HIP(ctx, hipMemcpy(prim.data(), lanes->prim, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+	for (uint64_t i = 0; i < n; ++i)
+		if (prim[i] < -1 || (int64_t)prim[i] >= n_shapes) return fail(ctx, PG_ERR_INVALID, "pg_head_probe: shape number outside the scene");
+	// (no other input needs a check: the emitter's row comes from the lane's own sampler and is clamped to the scene's list,
+	// and pg_surface_probe, pg_emitter_probe and pg_bsdf_probe send arbitrary floats through these functions)
+	HeadProbeArgs v = {};
+	v.in = *lanes;
+	v.out = *out;
+	v.n = n;
+	v.a.shapes = scene_shapes(sc, true);
+	v.a.mats = sc.mats.p;
+	v.a.dir_lights.lights = sc.dir_lights.p;
+	for (int c = 0; c < 4; ++c) v.a.dir_lights.bsphere[c] = sc.bsphere[c];
+	v.a.emitters = sc.emitters.p; v.a.n_emitters = sc.n_emitters;
+	v.a.max_depth = max_depth; v.a.frac = frac; v.a.guided = guided ? 1 : 0;
+	return run_at_level(ctx, sc.general, n, stream, v, [](auto L) { return k_probe_head<decltype(L)::value>; });
 }
 
 int pg_emitter_probe(pg_context *ctx, uint64_t n, const float *d_p, const float *d_n, const float *d_e, float *d_out,

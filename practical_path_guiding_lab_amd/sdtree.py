@@ -892,6 +892,22 @@ class SDTree:
         self._ck(self._lib.pg_vertex_probe(self._h, n, m.shape[0], m.data_ptr(), int(level), C.byref(li), float(frac), int(bool(guided)),
                                            int(bool(record)), int(bool(store_nee)), int(rr_depth), C.byref(oo), _stream_ptr()))
 
+    def headProbe(self, lanes: Dict[str, torch.Tensor], out: Dict[str, torch.Tensor], max_depth: int, frac: float,
+                  guided: bool) -> None:
+        """pg_head_probe: the renderer's head of one path vertex by itself, for tests -- lanes: the columns of pg_head_lanes by
+        name, out: those of pg_head_out by name (include/pgsd.h), contiguous tensors on this device of the header's types
+        (uint32 as int32 bits, uint64 as int64 bits); the outputs are written in place.  Needs a scene."""
+        n = int(lanes["prim"].numel())
+        li, oo = N.pg_head_lanes(), N.pg_head_out()
+        for struct, cols in ((li, lanes), (oo, out)):
+            for name, _ in struct._fields_:
+                t = cols[name]
+                if not t.is_contiguous() or t.device != self.device:
+                    raise ValueError(name + ": a contiguous tensor on the tree's device")
+                setattr(struct, name, t.data_ptr())
+        self._ck(self._lib.pg_head_probe(self._h, n, C.byref(li), int(max_depth), float(frac), int(bool(guided)), C.byref(oo),
+                                         _stream_ptr()))
+
     def packAccumulators(self) -> torch.Tensor:
         """sdTree_current's accumulators in the 24-byte exchange format (pg_exchange_pack, on the current stream): the int64
         tensor a host-side collective sums instead of accumulators() -- a quarter fewer bytes; unpackAccumulators() writes

@@ -12,11 +12,11 @@ INCLUDE = os.path.join(ROOT, "include")
 
 # header -> entry points it declares, in the order of _native.SURFACE.  (pgsd.h: 55 when the filters of recording passes were
 # planned, 56 with pg_set_splat_filter, 58 with the two calls of that change, then one each for pg_scene_intersect,
-# pg_bsdf_probe, pg_surface_probe, pg_emitter_probe and pg_vertex_probe, the probes of the tests.)
-COUNTS = {"pgsd.h": 63, "pgsd_warp.h": 3, "pgsd_fraction.h": 7, "pgsd_target.h": 2, "pgsd_radiance.h": 6, "pgsd_bounce.h": 1,
+# pg_bsdf_probe, pg_surface_probe, pg_emitter_probe, pg_vertex_probe and pg_head_probe, the probes of the tests.)
+COUNTS = {"pgsd.h": 64, "pgsd_warp.h": 3, "pgsd_fraction.h": 7, "pgsd_target.h": 2, "pgsd_radiance.h": 6, "pgsd_bounce.h": 1,
           "pgsd_irradiance.h": 6}
 HEADERS = tuple(COUNTS)
-TOTAL = 88
+TOTAL = 89
 ABI_VERSION = 6
 
 

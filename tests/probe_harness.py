@@ -1,4 +1,4 @@
-"""What the GPU tests of the stage probes share (test_gpu_raycast, test_gpu_bsdf, test_gpu_surface, test_gpu_emitter, test_gpu_vertex): the
+"""What the GPU tests of the stage probes share (test_gpu_raycast, test_gpu_bsdf, test_gpu_surface, test_gpu_emitter, test_gpu_vertex, test_gpu_head): the
 contexts, the scenes on the device, the copy to the device, and the bit-for-bit comparison of a probe's columns with the CPU
 oracle's.  A test module keeps its own probe() call and its tests.  (A plain module: nothing of it runs at import, and the
 package is imported where a test first needs the device.)"""

@@ -246,7 +246,7 @@ def test_struct_layout_and_constant(native):  # noqa: F811
 
 
 def test_the_pinned_surfaces_are_untouched(native):  # noqa: F811
-    assert tuple(native.SURFACE) == abi_table.HEADERS and sum(len(v) for v in native.SURFACE.values()) == abi_table.TOTAL == 88
+    assert tuple(native.SURFACE) == abi_table.HEADERS and sum(len(v) for v in native.SURFACE.values()) == abi_table.TOTAL == 89
     assert list(native.SURFACE_EXTRA) == ["pg_resample.h"] and list(native.SURFACE_EXTRA["pg_resample.h"]) == ["pg_resample_cosine"]
     assert list(native.SURFACE_EXT) == ["ext/pg_lights.h"] and len(native.SURFACE_EXT["ext/pg_lights.h"]) == 9
     assert native.ABI_VERSION == abi_table.ABI_VERSION == 6

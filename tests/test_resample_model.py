@@ -206,7 +206,7 @@ def test_struct_layouts(native):  # noqa: F811
 
 def test_the_pinned_surface_is_untouched(native):  # noqa: F811
     assert HEADER not in native.SURFACE and tuple(native.SURFACE) == abi_table.HEADERS
-    assert sum(len(v) for v in native.SURFACE.values()) == abi_table.TOTAL == 88   # (87 when this header came; pg_vertex_probe, a probe of the tests in pgsd.h, since)
+    assert sum(len(v) for v in native.SURFACE.values()) == abi_table.TOTAL == 89   # (87 when this header came; pg_vertex_probe and pg_head_probe, probes of the tests in pgsd.h, since)
     assert not any("pg_resample_cosine" in v for v in native.SURFACE.values())
     assert native.ABI_VERSION == abi_table.ABI_VERSION == 6
     on_disk = sorted(os.path.basename(f) for f in glob.glob(os.path.join(abi_table.INCLUDE, "*.h")))

@@ -1,4 +1,4 @@
-"""What tools/surface_mutants.py, emitter_mutants.py, vertex_mutants.py and bsdf_mutants.py share: scratch copies of the CPU oracle with one
+"""What tools/surface_mutants.py, emitter_mutants.py, vertex_mutants.py, head_mutants.py and bsdf_mutants.py share: scratch copies of the CPU oracle with one
 deliberate error each (in a temporary directory: nothing of the tree is touched, and nothing is ever built for the device),
 swapped in behind oracle.pg_oracle, the tests run against every copy, and the report of which tests catch the error.  A tool
 keeps its MUTANTS (name, [(text of oracle/pg_oracle_render.c, its replacement[, how often the text occurs: 1])]), its TESTS
