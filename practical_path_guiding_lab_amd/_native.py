@@ -93,6 +93,16 @@ class pg_lights_records(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("position", "light", "value")]
 
 
+class pg_nee_params(C.Structure):  # include/ext/lights/pg_nee.h
+    _fields_ = [("candidates", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class pg_nee_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in (
+        "p", "normal", "active", "rng_state", "rng_inc", "light_out", "point_out", "weight_out", "dir_out", "dist_out", "target_out",
+        "source_out", "index_out", "cand_light_out", "cand_point_out", "cand_target_out", "cand_source_out")]
+
+
 class pg_vertex_lanes(C.Structure):  # include/pgsd.h: the columns of pg_vertex_probe, device pointers
     _fields_ = [(n, C.c_void_p) for n in (
         "thr", "L", "ior", "depth", "flags", "Le", "p", "n", "ng", "wi", "refl", "mat", "em_w", "bv_em", "bp_em", "ds_pdf",
@@ -185,6 +195,7 @@ PG_TARGET_SECOND_MOMENT = 1
 PG_BOUNCE_NONE, PG_BOUNCE_PDF, PG_BOUNCE_SAMPLE, PG_BOUNCE_CHOOSE = 0, 1, 2, 3
 PG_RESAMPLE_MAX_CANDIDATES, PG_RESAMPLE_NONE = 64, 0xFFFFFFFF
 PG_LIGHTS_MAX, PG_LIGHTS_WEIGHT_ONE, PG_LIGHTS_NONE = 4096, 65536, 0xFFFFFFFF
+PG_NEE_TABLE_WORDS = 12  # 32-bit words of pg_nee_set_lights' host table per light
 PG_RESAMPLE_LOBE_MIN_ROUGHNESS = 1e-3  # (the header's 1e-3f: the float32 nearest to it)
 PG_RESAMPLE_INTERFACE_MIN_ROUGHNESS = 1e-3  # (likewise)
 PG_RESAMPLE_INTERFACE_MIN_ETA, PG_RESAMPLE_INTERFACE_MAX_ETA = 0.25, 4.0
@@ -292,6 +303,10 @@ SURFACE_MORE = {
     },
     "ext/guiding/pg_resample_interface.h": {  # product guiding through rough glass: the two-sided lobe of a rough dielectric
         "pg_resample_interface": [V, U64, P(pg_resample_params), P(pg_resample_interface_args), V],
+    },
+    "ext/lights/pg_nee.h": {  # resampled next-event estimation: a light and a point on it, from the learned rows and the geometry
+        "pg_nee_set_lights": [V, U32, V, V], "pg_nee_status": [V, P(U32)],
+        "pg_nee_resample": [V, U64, P(pg_nee_params), P(pg_nee_args), V],
     },
 }
 EXPORTS_MORE = tuple(name for entry_points in SURFACE_MORE.values() for name in entry_points)

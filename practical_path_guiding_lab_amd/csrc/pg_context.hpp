@@ -175,6 +175,25 @@ struct Lights {
 	}
 };
 
+// The lights' geometry for the resampled next-event estimation (include/ext/lights/pg_nee.h, pg_kernels_nee.hip): nothing unless
+// pg_nee_set_lights gave a table.  One 64-byte record per light, what k_nee_prepare made of the host's twelve words; a candidate
+// gathers one whole record.  It belongs to the context, not to the tree: setup, import and a refine leave it alone.
+struct alignas(64) NeeLight {
+	float o[3], a[3], b[3], N[3];
+	float invA, radiance;
+	uint32_t kind, two_sided;
+};
+static_assert(sizeof(NeeLight) == 64, "a light's record is one 64-byte line");
+struct Nee {
+	uint32_t n_lights = 0; // 0: no table
+	DevBuf<NeeLight> tab;
+	void release()
+	{
+		n_lights = 0;
+		tab.release();
+	}
+};
+
 // Radiance estimates (include/pgsd_radiance.h, pg_kernels_radiance.hip): off unless pg_radiance_enable switched it on.  One uint64
 // per quadtree of sdTree_prev, the number of in-box records its energies were resolved from; a refine builds the next table in the
 // spare buffer and commits it, with the two flags, by one pointer swap (pg_refine.hip).
@@ -240,6 +259,7 @@ struct pg_context {
 	pg::Fraction frac;               // the learned sampling fraction (disabled by pg_setup / pg_import)
 	pg::Radiance rad;                // the quadtrees' statistical weights (disabled by pg_setup / pg_import)
 	pg::Lights lights;               // the learned light selection (disabled by pg_setup / pg_import)
+	pg::Nee nee;                     // the lights' geometry of pg_nee_resample (kept by pg_setup / pg_import / a refine)
 	int32_t target_applied = 0;      // the target pg_target_apply gave f.acc since the last refine commit / setup / import (pgsd_target.h)
 	pg::DepthCounters *dc = nullptr; // device
 	bool dc_on = false;

@@ -415,6 +415,75 @@ class SDTree:
             raise ValueError("rows must have shape (n_roots, n_lights)")
         self._ck(self._lib.pg_lights_import(self._h, rows.shape[0], rows.shape[1], rows.ctypes.data))
 
+    # ---- resampled next-event estimation (include/ext/lights/pg_nee.h; not in the reference) -------------------------------
+    def lightsSetGeometry(self, table: Optional[Dict[str, np.ndarray]]):
+        """Gives the context the lights' geometry (pg_nee_set_lights), light j being light j of lightsEnable.  table: numpy
+        arrays origin, edge_a, edge_b (L, 3), radiance (L,) (a scalar per light, such as the luminance of its emitted radiance),
+        triangle (L,) bool (else a parallelogram), two_sided (L,) bool.  None, or a table of no lights, frees it.  The table
+        stays through setup(), load() and refineAndPrepare(); setting it again replaces it."""
+        if table is None or len(table["radiance"]) == 0:
+            self._ck(self._lib.pg_nee_set_lights(self._h, 0, None, _stream_ptr()))
+            return
+        L = len(table["radiance"])
+        words = np.zeros((L, N.PG_NEE_TABLE_WORDS), np.float32)
+        for k, name in enumerate(("origin", "edge_a", "edge_b")):
+            v = np.asarray(table[name], np.float32)
+            if v.shape != (L, 3):
+                raise ValueError(f"{name} must have shape (L, 3)")
+            words[:, 3 * k:3 * k + 3] = v
+        for name in ("radiance", "triangle", "two_sided"):
+            if np.shape(table[name]) != (L,):
+                raise ValueError(f"{name} must have shape (L,)")
+        words[:, 9] = np.asarray(table["radiance"], np.float32)
+        bits = words.view(np.uint32)
+        bits[:, 10] = np.asarray(table["triangle"]).astype(bool)
+        bits[:, 11] = np.asarray(table["two_sided"]).astype(bool)
+        self._ck(self._lib.pg_nee_set_lights(self._h, L, words.ctypes.data, _stream_ptr()))
+
+    def lightsGeometryStatus(self) -> int:
+        """The number of lights of the geometry table, 0 when none is set (pg_nee_status)."""
+        n = C.c_uint32()
+        self._ck(self._lib.pg_nee_status(self._h, C.byref(n)))
+        return int(n.value)
+
+    def lightsResample(self, position: torch.Tensor, normal: torch.Tensor, sampler: PCG32Sampler, candidates: int = 8,
+                       active: Optional[torch.Tensor] = None, return_candidates: bool = False
+                       ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Dict[str, torch.Tensor]]:
+        """(light int32 (N,), point float32 (3, N), weight float32 (N,), info) (pg_nee_resample): a light and a point on it in
+        proportion to the unshadowed contribution at a diffuse surface with `normal` (used as given), by resampled importance
+        sampling -- `candidates` draws of a light from the row of the position's KD leaf (lightsSample's selection) and a
+        uniform point on it, one kept in proportion to target over source.  Needs lightsEnable and lightsSetGeometry with the
+        same number of lights.  The estimator is f(point) * weight, f the whole integrand in area measure (emitted radiance,
+        BSDF, both cosines over the squared distance, and the visibility of the ONE shadow ray the host traces); weight is 0 and
+        light -1 where nothing could be kept.  One kernel, one KD descent.  info: {"direction" float32 (3, N), "distance",
+        "target", "source" float32 (N,), "index" int32 (N,) (the bits of a uint32: the kept candidate, 0xFFFFFFFF if none)};
+        with return_candidates also {"cand_light" int32 (M, N), "cand_point" float32 (M, 3, N), "cand_target", "cand_source"
+        float32 (M, N)}, what a host with another BSDF resamples itself.  Every served lane's stream advances by 4 * candidates
+        draws."""
+        n = position.shape[1]
+        _f32(position, (3, n)); _f32(normal, (3, n))
+        if sampler.n != n:
+            raise ValueError("the sampler must have one stream per lane")
+        m, mp = _mask(active, n)
+        M = int(candidates)
+        prm = N.pg_nee_params(M & 0xFFFFFFFF if M >= 0 else 0)
+        a = N.pg_nee_args()
+        a.p, a.normal, a.active = position.data_ptr(), normal.data_ptr(), mp
+        a.rng_state, a.rng_inc = sampler.state.data_ptr(), sampler.inc.data_ptr()
+        light, point, w = self._new(n, dtype=torch.int32), self._new(3, n), self._new(n)
+        info = {"direction": self._new(3, n), "distance": self._new(n), "target": self._new(n), "source": self._new(n),
+                "index": self._new(n, dtype=torch.int32)}
+        a.light_out, a.point_out, a.weight_out = light.data_ptr(), point.data_ptr(), w.data_ptr()
+        a.dir_out, a.dist_out = info["direction"].data_ptr(), info["distance"].data_ptr()
+        a.target_out, a.source_out, a.index_out = info["target"].data_ptr(), info["source"].data_ptr(), info["index"].data_ptr()
+        if return_candidates and 1 <= M <= N.PG_RESAMPLE_MAX_CANDIDATES:  # (any other M is refused below, before a launch)
+            info["cand_light"], info["cand_point"] = self._new(M, n, dtype=torch.int32), self._new(M, 3, n)
+            info["cand_target"], info["cand_source"] = self._new(M, n), self._new(M, n)
+            a.cand_light_out, a.cand_point_out = info["cand_light"].data_ptr(), info["cand_point"].data_ptr()
+            a.cand_target_out, a.cand_source_out = info["cand_target"].data_ptr(), info["cand_source"].data_ptr()
+        self._ck(self._lib.pg_nee_resample(self._h, n, C.byref(prm), C.byref(a), _stream_ptr()))
+        return light, point, w, info
+
     def compactLanes(self, select: torch.Tensor, nee_active: Optional[torch.Tensor] = None,
                      idx_out: Optional[torch.Tensor] = None, count_out: Optional[torch.Tensor] = None):
         """Active-ray stream compaction (pg_compact_lanes): returns (idx int32[n], counts int32[2]);
