@@ -239,7 +239,9 @@ struct pg_render_state; // pg_render.hip (its scene: pg_scene_state.hpp)
 struct pg_rr_params;    // include/pgsd_radiance.h
 namespace pg {
 struct RrArgs;          // pg_guide_dev.hpp
+struct RisConsts;       // pg_ris_dev.hpp
 }
+struct pg_resample_params; // include/pg_resample.h
 
 struct pg_context {
 	pg_render_state *render = nullptr;
@@ -326,6 +328,13 @@ void launch_radiance_carry(const unsigned long long *tree_count, uint32_t n_old,
 int radiance_source(pg_context *ctx, const char *who);
 // and pg_rr_params are valid, which fills the window (lo, hi) and the split limit (max_split, max_split_f) of rr
 int rr_window(pg_context *ctx, const char *who, const pg_rr_params *params, RrArgs &rr);
+// pg_kernels_resample.hip: the host checks the resampled calls share (pg_resample_cosine / _lobe / _interface, pg_nee_resample),
+// each PG_OK or the refusal with `who` in front: candidates lies in 1..64; n fits 32 bits;
+int resample_candidates(pg_context *ctx, const char *who, uint32_t candidates);
+int resample_lanes(pg_context *ctx, const char *who, uint64_t n);
+// and all the refusals of pg_resample_params in the order of include/pg_resample.h (candidates, alpha, delta, reserved, n), which
+// fills the kernels' constants c
+int resample_consts(pg_context *ctx, const char *who, uint64_t n, const pg_resample_params &prm, RisConsts &c);
 // pg_render.hip
 void destroy_render_state(pg_context *ctx);
 // pg_render_wave.hip

@@ -3,14 +3,16 @@
 // from the learned row of the vertex's KD leaf.  One lane per vertex, wave64, 256-thread groups.
 //
 // k_nee_resample follows k_lights_sample for the descent -- the staged KD planes, one descent, one row pointer, K read once --
-// and k_resample_cosine for the loop: the reservoir lives in registers and there is no per-candidate array, so nothing can
-// spill.  Per candidate: SELECT and PMF of pg_lights_dev.hpp as they are (the binary search of the row is a chain of up to twelve
-// dependent loads at L = 4096), then ONE gather of the light's 64-byte record as four 16-byte loads of one line.  Bound by the
-// latency of those dependent loads; occupancy hides it (tests/test_nee_resources.py).
+// and pg_ris_dev.hpp for the resampling step (the weight, the reservoir's rule, W, and the stores that fit: the point goes
+// where the direction calls have a direction, and the kept light stays here): the reservoir lives in registers and there is no
+// per-candidate array, so nothing can spill.  Per candidate: SELECT and PMF of pg_lights_dev.hpp as they are (the binary search
+// of the row is a chain of up to twelve dependent loads at L = 4096), then ONE gather of the light's 64-byte record as four
+// 16-byte loads of one line.  Bound by the latency of those dependent loads; occupancy hides it (tests/test_nee_resources.py).
 #include "../../include/ext/lights/pg_nee.h"
 #include "pg_context.hpp"
 #include "pg_descent.hpp"
 #include "pg_lights_dev.hpp"
+#include "pg_ris_dev.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -92,11 +94,8 @@ __global__ __launch_bounds__(kQueryBlock) void k_nee_resample(TreeView t, Lights
 			const float g = (d2 > 0.0f && cs > 0.0f && cl > 0.0f) ? (cs * cl) / d2 : 0.0f;
 			const float tg = r3.y * g;
 			const float s = pm * r3.x;
-			const float ratio = tg / s;
-			const float wk = (s > 0.0f && tg > 0.0f && finite_f32(ratio)) ? ratio : 0.0f;
-			const float zeta = rng.next_f32();
-			wsum = wsum + wk;
-			if (wk > 0.0f && zeta * wsum < wk) {
+			const float wk = ris_weight(tg, s);
+			if (ris_keep(rng, wk, wsum)) {
 				kk = k;
 				kj = j;
 				kyx = yx; kyy = yy; kyz = yz;
@@ -105,19 +104,13 @@ __global__ __launch_bounds__(kQueryBlock) void k_nee_resample(TreeView t, Lights
 			}
 			if (kCand) {
 				if (a.cand_light_out) a.cand_light_out[(size_t)k * n + i] = j;
-				if (a.cand_point_out) {
-					float *o = a.cand_point_out + ((size_t)k * 3u * n + i);
-					o[0] = yx;
-					o[n] = yy;
-					o[2 * n] = yz;
-				}
-				if (a.cand_target_out) a.cand_target_out[(size_t)k * n + i] = tg;
-				if (a.cand_source_out) a.cand_source_out[(size_t)k * n + i] = s;
+				ris_store_cand_vec(a.cand_point_out, n, i, k, yx, yy, yz);
+				ris_store_cand_ts(a, n, i, k, tg, s);
 			}
 		}
 		a.rng_state[i] = rng.state;
 		if (kk != PG_RESAMPLE_NONE) {
-			W = (wsum / Mf) / kt;
+			W = ris_W(wsum, Mf, kt);
 			// w and dist of the kept point: the candidate's own operations again on the same numbers (the same bits), which spares
 			// the loop four registers
 			const float vx = kyx - px, vy = kyy - py, vz = kyz - pz;
@@ -127,14 +120,8 @@ __global__ __launch_bounds__(kQueryBlock) void k_nee_resample(TreeView t, Lights
 	} else if (kCand) { // zeros in all the lane's candidate slots
 		for (uint32_t k = 0; k < M; ++k) {
 			if (a.cand_light_out) a.cand_light_out[(size_t)k * n + i] = 0u;
-			if (a.cand_point_out) {
-				float *o = a.cand_point_out + ((size_t)k * 3u * n + i);
-				o[0] = 0.0f;
-				o[n] = 0.0f;
-				o[2 * n] = 0.0f;
-			}
-			if (a.cand_target_out) a.cand_target_out[(size_t)k * n + i] = 0.0f;
-			if (a.cand_source_out) a.cand_source_out[(size_t)k * n + i] = 0.0f;
+			ris_store_cand_vec(a.cand_point_out, n, i, k, 0.0f, 0.0f, 0.0f);
+			ris_store_cand_ts(a, n, i, k, 0.0f, 0.0f);
 		}
 	}
 	a.light_out[i] = kj;
@@ -148,9 +135,7 @@ __global__ __launch_bounds__(kQueryBlock) void k_nee_resample(TreeView t, Lights
 		a.dir_out[2 * n + i] = kwz;
 	}
 	if (a.dist_out) a.dist_out[i] = kdist;
-	if (a.target_out) a.target_out[i] = kt;
-	if (a.source_out) a.source_out[i] = ks;
-	if (a.index_out) a.index_out[i] = kk;
+	ris_store_kept_tsi(a, i, kt, ks, kk);
 }
 
 } // namespace pg
@@ -222,11 +207,10 @@ int pg_nee_resample(pg_context *ctx, uint64_t n, const pg_nee_params *params, co
 		return fail(ctx, PG_ERR_INVALID, "pg_nee_resample: n_lights of pg_lights_enable does not match the light table's");
 	if (n && (!a.p || !a.normal || !a.rng_state || !a.rng_inc || !a.light_out || !a.point_out || !a.weight_out))
 		return fail(ctx, PG_ERR_INVALID, "pg_nee_resample: NULL pointer");
-	if (prm.candidates < 1u || prm.candidates > (uint32_t)PG_RESAMPLE_MAX_CANDIDATES)
-		return fail(ctx, PG_ERR_INVALID, "pg_nee_resample: candidates must be 1..64");
+	if (int rc = resample_candidates(ctx, "pg_nee_resample", prm.candidates)) return rc;
 	if (prm.reserved[0] != 0u || prm.reserved[1] != 0u || prm.reserved[2] != 0u)
 		return fail(ctx, PG_ERR_INVALID, "pg_nee_resample: reserved must be 0");
-	if (n > 0xffffffffull) return fail(ctx, PG_ERR_INVALID, "pg_nee_resample: more than 2^32 - 1 lanes");
+	if (int rc = resample_lanes(ctx, "pg_nee_resample", n)) return rc;
 	if (n == 0) return PG_OK;
 	const TreeView t = ctx->view();
 	const LightsView v = lights_view(ctx);

@@ -10,25 +10,19 @@
 // Lanes of a wave take the sampling walk and the cosine-plus-pdf walk side by side, as k_guided_bounce's CHOOSE lanes do: the
 // choice is the lane's own draw, per candidate, and lanes are not reordered.
 // Built from the device functions the stand-alone calls use (pg_descent.hpp) and the renderer's frame and cosine map
-// (pg_render_dev.hpp) as they are.
+// (pg_render_dev.hpp) as they are.  The resampling step itself -- a candidate's weight, the reservoir's rule, W, the stores --
+// is pg_ris_dev.hpp's, shared with the three calls that followed this one; the host checks they share are defined below.
 #include "../../include/pg_resample.h"
 #include "pg_context.hpp"
 #include "pg_descent.hpp"
 #include "pg_render_dev.hpp"
+#include "pg_ris_dev.hpp"
 
 namespace pg {
 
-// what the kernel needs beside the caller's arrays: the parameters and what follows from them alone (fp32, one rounding each)
-struct ResampleConsts {
-	uint32_t M;
-	float Mf;         // (float)M
-	float alpha, om;  // om = 1 - alpha
-	float d4, omd;    // delta * INV_4PI, 1 - delta
-};
-
 // kCand: one of the cand_* outputs is given.
 template <bool kCand>
-__global__ __launch_bounds__(kQueryBlock) void k_resample_cosine(TreeView t, uint64_t n, pg_resample_args a, ResampleConsts c)
+__global__ __launch_bounds__(kQueryBlock) void k_resample_cosine(TreeView t, uint64_t n, pg_resample_args a, RisConsts c)
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
 	stage_kd_planes(s_planes, t);
@@ -70,48 +64,51 @@ __global__ __launch_bounds__(kQueryBlock) void k_resample_cosine(TreeView t, uin
 			const float cl = d > 0.0f ? d * kInvPiF : 0.0f;
 			const float s = c.alpha * cl + c.om * q;
 			const float tg = cl * (c.d4 + c.omd * q);
-			const float ratio = tg / s;
-			const float wk = (s > 0.0f && tg > 0.0f && finite_f32(ratio)) ? ratio : 0.0f;
-			const float zeta = rng.next_f32();
-			wsum = wsum + wk;
-			if (wk > 0.0f && zeta * wsum < wk) {
+			const float wk = ris_weight(tg, s);
+			if (ris_keep(rng, wk, wsum)) {
 				kk = k;
 				kx = w.x; ky = w.y; kz = w.z;
 				kt = tg;
 				ks = s;
 			}
-			if (kCand) {
-				if (a.cand_dir_out) {
-					float *o = a.cand_dir_out + ((size_t)k * 3u * n + i);
-					o[0] = w.x;
-					o[n] = w.y;
-					o[2 * n] = w.z;
-				}
-				if (a.cand_target_out) a.cand_target_out[(size_t)k * n + i] = tg;
-				if (a.cand_source_out) a.cand_source_out[(size_t)k * n + i] = s;
-			}
+			if (kCand) ris_store_cand(a, n, i, k, w.x, w.y, w.z, tg, s);
 		}
 		a.rng_state[i] = rng.state;
-		if (kk != PG_RESAMPLE_NONE) W = (wsum / c.Mf) / kt;
-	} else if (kCand) { // zeros in all the lane's candidate slots
-		for (uint32_t k = 0; k < c.M; ++k) {
-			if (a.cand_dir_out) {
-				float *o = a.cand_dir_out + ((size_t)k * 3u * n + i);
-				o[0] = 0.0f;
-				o[n] = 0.0f;
-				o[2 * n] = 0.0f;
-			}
-			if (a.cand_target_out) a.cand_target_out[(size_t)k * n + i] = 0.0f;
-			if (a.cand_source_out) a.cand_source_out[(size_t)k * n + i] = 0.0f;
-		}
+		if (kk != PG_RESAMPLE_NONE) W = ris_W(wsum, c.Mf, kt);
+	} else if (kCand) {
+		ris_zero_cands(a, n, i, c.M);
 	}
-	a.dir_out[i] = kx;
-	a.dir_out[n + i] = ky;
-	a.dir_out[2 * n + i] = kz;
-	a.weight_out[i] = W;
-	if (a.target_out) a.target_out[i] = kt;
-	if (a.source_out) a.source_out[i] = ks;
-	if (a.index_out) a.index_out[i] = kk;
+	ris_store_kept(a, n, i, kx, ky, kz, W, kt, ks, kk);
+}
+
+int resample_candidates(pg_context *ctx, const char *who, uint32_t candidates)
+{
+	if (candidates < 1u || candidates > (uint32_t)PG_RESAMPLE_MAX_CANDIDATES)
+		return fail(ctx, PG_ERR_INVALID, std::string(who) + ": candidates must be 1..64");
+	return PG_OK;
+}
+
+int resample_lanes(pg_context *ctx, const char *who, uint64_t n)
+{
+	if (n > 0xffffffffull) return fail(ctx, PG_ERR_INVALID, std::string(who) + ": more than 2^32 - 1 lanes");
+	return PG_OK;
+}
+
+int resample_consts(pg_context *ctx, const char *who, uint64_t n, const pg_resample_params &prm, RisConsts &c)
+{
+	const std::string w = std::string(who) + ": ";
+	if (int rc = resample_candidates(ctx, who, prm.candidates)) return rc;
+	if (!(prm.alpha >= 0.0f && prm.alpha <= 1.0f)) return fail(ctx, PG_ERR_INVALID, w + "alpha must be in [0, 1]");
+	if (!(prm.delta >= 0.0f && prm.delta <= 1.0f)) return fail(ctx, PG_ERR_INVALID, w + "delta must be in [0, 1]");
+	if (prm.reserved != 0u) return fail(ctx, PG_ERR_INVALID, w + "reserved must be 0");
+	if (int rc = resample_lanes(ctx, who, n)) return rc;
+	c.M = prm.candidates;
+	c.Mf = (float)prm.candidates;
+	c.alpha = prm.alpha;
+	c.om = 1.0f - prm.alpha; // (fp32, each operation rounded on its own: the build's -ffp-contract=off holds for the host too)
+	c.d4 = prm.delta * kInvFourPiF;
+	c.omd = 1.0f - prm.delta;
+	return PG_OK;
 }
 
 } // namespace pg
@@ -125,24 +122,12 @@ int pg_resample_cosine(pg_context *ctx, uint64_t n, const pg_resample_params *pa
 	PG_READY(ctx);
 	if (!params) return fail(ctx, PG_ERR_INVALID, "pg_resample_cosine: NULL params");
 	if (!args) return fail(ctx, PG_ERR_INVALID, "pg_resample_cosine: NULL args");
-	const pg_resample_params &prm = *params;
 	const pg_resample_args &a = *args;
 	if (n && (!a.p || !a.normal || !a.rng_state || !a.rng_inc || !a.dir_out || !a.weight_out))
 		return fail(ctx, PG_ERR_INVALID, "pg_resample_cosine: NULL pointer");
-	if (prm.candidates < 1u || prm.candidates > (uint32_t)PG_RESAMPLE_MAX_CANDIDATES)
-		return fail(ctx, PG_ERR_INVALID, "pg_resample_cosine: candidates must be 1..64");
-	if (!(prm.alpha >= 0.0f && prm.alpha <= 1.0f)) return fail(ctx, PG_ERR_INVALID, "pg_resample_cosine: alpha must be in [0, 1]");
-	if (!(prm.delta >= 0.0f && prm.delta <= 1.0f)) return fail(ctx, PG_ERR_INVALID, "pg_resample_cosine: delta must be in [0, 1]");
-	if (prm.reserved != 0u) return fail(ctx, PG_ERR_INVALID, "pg_resample_cosine: reserved must be 0");
-	if (n > 0xffffffffull) return fail(ctx, PG_ERR_INVALID, "pg_resample_cosine: more than 2^32 - 1 lanes");
+	RisConsts c;
+	if (int rc = resample_consts(ctx, "pg_resample_cosine", n, *params, c)) return rc;
 	if (n == 0) return PG_OK;
-	ResampleConsts c;
-	c.M = prm.candidates;
-	c.Mf = (float)prm.candidates;
-	c.alpha = prm.alpha;
-	c.om = 1.0f - prm.alpha;
-	c.d4 = prm.delta * kInvFourPiF;
-	c.omd = 1.0f - prm.delta;
 	const TreeView t = ctx->view();
 	const hipStream_t s = (hipStream_t)stream;
 	if (a.cand_dir_out || a.cand_target_out || a.cand_source_out)

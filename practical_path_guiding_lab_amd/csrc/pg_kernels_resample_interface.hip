@@ -4,7 +4,8 @@
 // rough-dielectric sampling (reflection or refraction about a GGX visible normal, chosen by Fresnel) and the SD-tree.
 // One lane per vertex, wave64, 256-thread groups.
 //
-// The shape is k_resample_lobe's (pg_kernels_resample_lobe.hip) and so is the bound: the latency of dependent gathers -- the KD
+// The resampling step is pg_ris_dev.hpp's; what is written here is which lanes are served, how a candidate is drawn, the
+// interface's density and eta_out.  The bound: the latency of dependent gathers -- the KD
 // grid entry, the tree's head, then per candidate a quadtree walk of 32 bytes per level.  The KD descent and the head are read
 // ONCE for the M candidates; the reservoir is four numbers and a direction in registers, there is no per-candidate array:
 // nothing can spill.  What the interface adds over the reflection lobe is arithmetic between the gathers: the Fresnel term of
@@ -21,16 +22,9 @@
 #include "pg_context.hpp"
 #include "pg_descent.hpp"
 #include "pg_render_dev.hpp"
+#include "pg_ris_dev.hpp"
 
 namespace pg {
-
-// what the kernel needs beside the caller's arrays: the parameters and what follows from them alone (fp32, one rounding each)
-struct ResampleInterfaceConsts {
-	uint32_t M;
-	float Mf;         // (float)M
-	float alpha, om;  // om = 1 - alpha
-	float d4, omd;    // delta * INV_4PI, 1 - delta
-};
 
 // the material row rd_sample and rd_eval_pdf read: words MAT_ALPHA and MAT_ETA
 struct InterfaceRow {
@@ -59,7 +53,7 @@ __device__ __forceinline__ float interface_density(const InterfaceRow &row, v3 w
 // Left alone the compiler takes 103 registers without the candidate stores and 109 with them: four waves per SIMD, no scratch.
 // Held to five waves the first would take 96 registers and 32 bytes of scratch per lane, so there is no such bound here.
 template <bool kCand>
-__global__ __launch_bounds__(kQueryBlock) void k_resample_interface(TreeView t, uint64_t n, pg_resample_interface_args a, ResampleInterfaceConsts c)
+__global__ __launch_bounds__(kQueryBlock) void k_resample_interface(TreeView t, uint64_t n, pg_resample_interface_args a, RisConsts c)
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
 	stage_kd_planes(s_planes, t);
@@ -118,53 +112,26 @@ __global__ __launch_bounds__(kQueryBlock) void k_resample_interface(TreeView t, 
 				const float b = interface_density(row, wil, to_local(fr, w));
 				s = c.alpha * b + c.om * q;
 				tg = b * (c.d4 + c.omd * q);
-				const float ratio = tg / s;
-				wk = (s > 0.0f && tg > 0.0f && finite_f32(ratio)) ? ratio : 0.0f;
+				wk = ris_weight(tg, s);
 			}
-			const float zeta = rng.next_f32();
-			wsum = wsum + wk;
-			if (wk > 0.0f && zeta * wsum < wk) {
+			if (ris_keep(rng, wk, wsum)) {
 				kk = k;
 				kx = w.x; ky = w.y; kz = w.z;
 				kt = tg;
 				ks = s;
 			}
-			if (kCand) {
-				if (a.cand_dir_out) {
-					float *o = a.cand_dir_out + ((size_t)k * 3u * n + i);
-					o[0] = w.x;
-					o[n] = w.y;
-					o[2 * n] = w.z;
-				}
-				if (a.cand_target_out) a.cand_target_out[(size_t)k * n + i] = tg;
-				if (a.cand_source_out) a.cand_source_out[(size_t)k * n + i] = s;
-			}
+			if (kCand) ris_store_cand(a, n, i, k, w.x, w.y, w.z, tg, s);
 		}
 		a.rng_state[i] = rng.state;
 		if (kk != PG_RESAMPLE_NONE) {
-			W = (wsum / c.Mf) / kt;
+			W = ris_W(wsum, c.Mf, kt);
 			// the index the path is in behind the kept direction, relative to the viewer's: 1 on wi's side
 			eo = wil.z * to_local(fr, V(kx, ky, kz)).z > 0.0f ? 1.0f : (wil.z > 0.0f ? eta : 1.0f / eta);
 		}
-	} else if (kCand) { // zeros in all the lane's candidate slots
-		for (uint32_t k = 0; k < c.M; ++k) {
-			if (a.cand_dir_out) {
-				float *o = a.cand_dir_out + ((size_t)k * 3u * n + i);
-				o[0] = 0.0f;
-				o[n] = 0.0f;
-				o[2 * n] = 0.0f;
-			}
-			if (a.cand_target_out) a.cand_target_out[(size_t)k * n + i] = 0.0f;
-			if (a.cand_source_out) a.cand_source_out[(size_t)k * n + i] = 0.0f;
-		}
+	} else if (kCand) {
+		ris_zero_cands(a, n, i, c.M);
 	}
-	a.dir_out[i] = kx;
-	a.dir_out[n + i] = ky;
-	a.dir_out[2 * n + i] = kz;
-	a.weight_out[i] = W;
-	if (a.target_out) a.target_out[i] = kt;
-	if (a.source_out) a.source_out[i] = ks;
-	if (a.index_out) a.index_out[i] = kk;
+	ris_store_kept(a, n, i, kx, ky, kz, W, kt, ks, kk);
 	if (a.eta_out) a.eta_out[i] = eo;
 }
 
@@ -179,24 +146,12 @@ int pg_resample_interface(pg_context *ctx, uint64_t n, const pg_resample_params 
 	PG_READY(ctx);
 	if (!params) return fail(ctx, PG_ERR_INVALID, "pg_resample_interface: NULL params");
 	if (!args) return fail(ctx, PG_ERR_INVALID, "pg_resample_interface: NULL args");
-	const pg_resample_params &prm = *params;
 	const pg_resample_interface_args &a = *args;
 	if (n && (!a.p || !a.normal || !a.wi || !a.roughness || !a.eta || !a.rng_state || !a.rng_inc || !a.dir_out || !a.weight_out))
 		return fail(ctx, PG_ERR_INVALID, "pg_resample_interface: NULL pointer");
-	if (prm.candidates < 1u || prm.candidates > (uint32_t)PG_RESAMPLE_MAX_CANDIDATES)
-		return fail(ctx, PG_ERR_INVALID, "pg_resample_interface: candidates must be 1..64");
-	if (!(prm.alpha >= 0.0f && prm.alpha <= 1.0f)) return fail(ctx, PG_ERR_INVALID, "pg_resample_interface: alpha must be in [0, 1]");
-	if (!(prm.delta >= 0.0f && prm.delta <= 1.0f)) return fail(ctx, PG_ERR_INVALID, "pg_resample_interface: delta must be in [0, 1]");
-	if (prm.reserved != 0u) return fail(ctx, PG_ERR_INVALID, "pg_resample_interface: reserved must be 0");
-	if (n > 0xffffffffull) return fail(ctx, PG_ERR_INVALID, "pg_resample_interface: more than 2^32 - 1 lanes");
+	RisConsts c;
+	if (int rc = resample_consts(ctx, "pg_resample_interface", n, *params, c)) return rc;
 	if (n == 0) return PG_OK;
-	ResampleInterfaceConsts c;
-	c.M = prm.candidates;
-	c.Mf = (float)prm.candidates;
-	c.alpha = prm.alpha;
-	c.om = 1.0f - prm.alpha;
-	c.d4 = prm.delta * kInvFourPiF;
-	c.omd = 1.0f - prm.delta;
 	const TreeView t = ctx->view();
 	const hipStream_t s = (hipStream_t)stream;
 	if (a.cand_dir_out || a.cand_target_out || a.cand_source_out)

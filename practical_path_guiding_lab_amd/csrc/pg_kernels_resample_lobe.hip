@@ -3,7 +3,8 @@
 // importance sampling of M candidates from the three-way mixture of the GGX reflection lobe, the cosine lobe and the SD-tree.
 // One lane per vertex, wave64, 256-thread groups.
 //
-// The shape is k_resample_cosine's (pg_kernels_resample.hip) and so is the bound: the latency of dependent gathers -- the KD
+// The resampling step is pg_ris_dev.hpp's; what is written here is which lanes are served, how a candidate is drawn and the
+// lobe's density.  The bound: the latency of dependent gathers -- the KD
 // grid entry, the tree's head, then per candidate a quadtree walk of 32 bytes per level.  The KD descent and the head are read
 // ONCE for the M candidates; the reservoir is four numbers and a direction in registers, there is no per-candidate array:
 // nothing can spill.  What the lobe adds is arithmetic between the gathers: the visible-normal sample of a GGX candidate, and
@@ -17,16 +18,9 @@
 #include "pg_context.hpp"
 #include "pg_descent.hpp"
 #include "pg_render_dev.hpp"
+#include "pg_ris_dev.hpp"
 
 namespace pg {
-
-// what the kernel needs beside the caller's arrays: the parameters and what follows from them alone (fp32, one rounding each)
-struct ResampleLobeConsts {
-	uint32_t M;
-	float Mf;         // (float)M
-	float alpha, om;  // om = 1 - alpha
-	float d4, omd;    // delta * INV_4PI, 1 - delta
-};
 
 // g(wl): the density of the reflection of wil about a GGX visible normal, rc_eval_pdf's pdf (a = -roughness)
 __device__ __forceinline__ float lobe_ggx_density(v3 wil, v3 wl, float a)
@@ -44,7 +38,7 @@ __device__ __forceinline__ float lobe_ggx_density(v3 wil, v3 wl, float a)
 // and four waves ran 7 % slower than the five it reaches when asked to (profiles/resample_lobe/timing_five_waves.txt); with
 // the candidate stores five waves would cost scratch, so that instantiation stays at the four it reaches by itself.
 template <bool kCand>
-__global__ __launch_bounds__(kQueryBlock, kCand ? 4 : 5) void k_resample_lobe(TreeView t, uint64_t n, pg_resample_lobe_args a, ResampleLobeConsts c)
+__global__ __launch_bounds__(kQueryBlock, kCand ? 4 : 5) void k_resample_lobe(TreeView t, uint64_t n, pg_resample_lobe_args a, RisConsts c)
 {
 	__shared__ float s_planes[3 * kKdGridPlanes];
 	stage_kd_planes(s_planes, t);
@@ -111,49 +105,22 @@ __global__ __launch_bounds__(kQueryBlock, kCand ? 4 : 5) void k_resample_lobe(Tr
 				b = finite_f32(b) ? b : 0.0f;
 				s = c.alpha * b + c.om * q;
 				tg = b * (c.d4 + c.omd * q);
-				const float ratio = tg / s;
-				wk = (s > 0.0f && tg > 0.0f && finite_f32(ratio)) ? ratio : 0.0f;
+				wk = ris_weight(tg, s);
 			}
-			const float zeta = rng.next_f32();
-			wsum = wsum + wk;
-			if (wk > 0.0f && zeta * wsum < wk) {
+			if (ris_keep(rng, wk, wsum)) {
 				kk = k;
 				kx = w.x; ky = w.y; kz = w.z;
 				kt = tg;
 				ks = s;
 			}
-			if (kCand) {
-				if (a.cand_dir_out) {
-					float *o = a.cand_dir_out + ((size_t)k * 3u * n + i);
-					o[0] = w.x;
-					o[n] = w.y;
-					o[2 * n] = w.z;
-				}
-				if (a.cand_target_out) a.cand_target_out[(size_t)k * n + i] = tg;
-				if (a.cand_source_out) a.cand_source_out[(size_t)k * n + i] = s;
-			}
+			if (kCand) ris_store_cand(a, n, i, k, w.x, w.y, w.z, tg, s);
 		}
 		a.rng_state[i] = rng.state;
-		if (kk != PG_RESAMPLE_NONE) W = (wsum / c.Mf) / kt;
-	} else if (kCand) { // zeros in all the lane's candidate slots
-		for (uint32_t k = 0; k < c.M; ++k) {
-			if (a.cand_dir_out) {
-				float *o = a.cand_dir_out + ((size_t)k * 3u * n + i);
-				o[0] = 0.0f;
-				o[n] = 0.0f;
-				o[2 * n] = 0.0f;
-			}
-			if (a.cand_target_out) a.cand_target_out[(size_t)k * n + i] = 0.0f;
-			if (a.cand_source_out) a.cand_source_out[(size_t)k * n + i] = 0.0f;
-		}
+		if (kk != PG_RESAMPLE_NONE) W = ris_W(wsum, c.Mf, kt);
+	} else if (kCand) {
+		ris_zero_cands(a, n, i, c.M);
 	}
-	a.dir_out[i] = kx;
-	a.dir_out[n + i] = ky;
-	a.dir_out[2 * n + i] = kz;
-	a.weight_out[i] = W;
-	if (a.target_out) a.target_out[i] = kt;
-	if (a.source_out) a.source_out[i] = ks;
-	if (a.index_out) a.index_out[i] = kk;
+	ris_store_kept(a, n, i, kx, ky, kz, W, kt, ks, kk);
 }
 
 } // namespace pg
@@ -167,24 +134,12 @@ int pg_resample_lobe(pg_context *ctx, uint64_t n, const pg_resample_params *para
 	PG_READY(ctx);
 	if (!params) return fail(ctx, PG_ERR_INVALID, "pg_resample_lobe: NULL params");
 	if (!args) return fail(ctx, PG_ERR_INVALID, "pg_resample_lobe: NULL args");
-	const pg_resample_params &prm = *params;
 	const pg_resample_lobe_args &a = *args;
 	if (n && (!a.p || !a.normal || !a.wi || !a.roughness || !a.specular || !a.rng_state || !a.rng_inc || !a.dir_out || !a.weight_out))
 		return fail(ctx, PG_ERR_INVALID, "pg_resample_lobe: NULL pointer");
-	if (prm.candidates < 1u || prm.candidates > (uint32_t)PG_RESAMPLE_MAX_CANDIDATES)
-		return fail(ctx, PG_ERR_INVALID, "pg_resample_lobe: candidates must be 1..64");
-	if (!(prm.alpha >= 0.0f && prm.alpha <= 1.0f)) return fail(ctx, PG_ERR_INVALID, "pg_resample_lobe: alpha must be in [0, 1]");
-	if (!(prm.delta >= 0.0f && prm.delta <= 1.0f)) return fail(ctx, PG_ERR_INVALID, "pg_resample_lobe: delta must be in [0, 1]");
-	if (prm.reserved != 0u) return fail(ctx, PG_ERR_INVALID, "pg_resample_lobe: reserved must be 0");
-	if (n > 0xffffffffull) return fail(ctx, PG_ERR_INVALID, "pg_resample_lobe: more than 2^32 - 1 lanes");
+	RisConsts c;
+	if (int rc = resample_consts(ctx, "pg_resample_lobe", n, *params, c)) return rc;
 	if (n == 0) return PG_OK;
-	ResampleLobeConsts c;
-	c.M = prm.candidates;
-	c.Mf = (float)prm.candidates;
-	c.alpha = prm.alpha;
-	c.om = 1.0f - prm.alpha;
-	c.d4 = prm.delta * kInvFourPiF;
-	c.omd = 1.0f - prm.delta;
 	const TreeView t = ctx->view();
 	const hipStream_t s = (hipStream_t)stream;
 	if (a.cand_dir_out || a.cand_target_out || a.cand_source_out)

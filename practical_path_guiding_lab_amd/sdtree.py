@@ -462,27 +462,12 @@ class SDTree:
         draws."""
         n = position.shape[1]
         _f32(position, (3, n)); _f32(normal, (3, n))
-        if sampler.n != n:
-            raise ValueError("the sampler must have one stream per lane")
-        m, mp = _mask(active, n)
-        M = int(candidates)
-        prm = N.pg_nee_params(M & 0xFFFFFFFF if M >= 0 else 0)
         a = N.pg_nee_args()
-        a.p, a.normal, a.active = position.data_ptr(), normal.data_ptr(), mp
-        a.rng_state, a.rng_inc = sampler.state.data_ptr(), sampler.inc.data_ptr()
-        light, point, w = self._new(n, dtype=torch.int32), self._new(3, n), self._new(n)
-        info = {"direction": self._new(3, n), "distance": self._new(n), "target": self._new(n), "source": self._new(n),
-                "index": self._new(n, dtype=torch.int32)}
-        a.light_out, a.point_out, a.weight_out = light.data_ptr(), point.data_ptr(), w.data_ptr()
-        a.dir_out, a.dist_out = info["direction"].data_ptr(), info["distance"].data_ptr()
-        a.target_out, a.source_out, a.index_out = info["target"].data_ptr(), info["source"].data_ptr(), info["index"].data_ptr()
-        if return_candidates and 1 <= M <= N.PG_RESAMPLE_MAX_CANDIDATES:  # (any other M is refused below, before a launch)
-            info["cand_light"], info["cand_point"] = self._new(M, n, dtype=torch.int32), self._new(M, 3, n)
-            info["cand_target"], info["cand_source"] = self._new(M, n), self._new(M, n)
-            a.cand_light_out, a.cand_point_out = info["cand_light"].data_ptr(), info["cand_point"].data_ptr()
-            a.cand_target_out, a.cand_source_out = info["cand_target"].data_ptr(), info["cand_source"].data_ptr()
-        self._ck(self._lib.pg_nee_resample(self._h, n, C.byref(prm), C.byref(a), _stream_ptr()))
-        return light, point, w, info
+        light, point, dist = self._new(n, dtype=torch.int32), self._new(3, n), self._new(n)
+        a.light_out, a.point_out, a.dist_out = light.data_ptr(), point.data_ptr(), dist.data_ptr()
+        d, w, info = self._resample(self._lib.pg_nee_resample, a, (N.pg_nee_params,), position, normal, sampler, candidates, active,
+                                    return_candidates, lead=(("cand_light", torch.int32), ("cand_point", torch.float32, 3)))
+        return light, point, w, {"direction": d, "distance": dist, **info}
 
     def compactLanes(self, select: torch.Tensor, nee_active: Optional[torch.Tensor] = None,
                      idx_out: Optional[torch.Tensor] = None, count_out: Optional[torch.Tensor] = None):
@@ -734,24 +719,8 @@ class SDTree:
         what a host with another BSDF resamples itself.  The lanes' streams advance by the candidates' draws."""
         n = position.shape[1]
         _f32(position, (3, n)); _f32(normal, (3, n))
-        if sampler.n != n:
-            raise ValueError("the sampler must have one stream per lane")
-        m, mp = _mask(active, n)
-        M = int(candidates)
-        prm = N.pg_resample_params(M & 0xFFFFFFFF if M >= 0 else 0, float(alpha), float(delta), 0)
-        a = N.pg_resample_args()
-        a.p, a.normal, a.active = position.data_ptr(), normal.data_ptr(), mp
-        a.rng_state, a.rng_inc = sampler.state.data_ptr(), sampler.inc.data_ptr()
-        d, w = self._new(3, n), self._new(n)
-        info = {"target": self._new(n), "source": self._new(n), "index": self._new(n, dtype=torch.int32)}
-        a.dir_out, a.weight_out = d.data_ptr(), w.data_ptr()
-        a.target_out, a.source_out, a.index_out = info["target"].data_ptr(), info["source"].data_ptr(), info["index"].data_ptr()
-        if return_candidates and 1 <= M <= N.PG_RESAMPLE_MAX_CANDIDATES:  # (any other M is refused below, before a launch)
-            info["cand_dir"], info["cand_target"], info["cand_source"] = self._new(M, 3, n), self._new(M, n), self._new(M, n)
-            a.cand_dir_out = info["cand_dir"].data_ptr()
-            a.cand_target_out, a.cand_source_out = info["cand_target"].data_ptr(), info["cand_source"].data_ptr()
-        self._ck(self._lib.pg_resample_cosine(self._h, n, C.byref(prm), C.byref(a), _stream_ptr()))
-        return d, w, info
+        return self._resample(self._lib.pg_resample_cosine, N.pg_resample_args(), (N.pg_resample_params, float(alpha), float(delta), 0),
+                              position, normal, sampler, candidates, active, return_candidates)
 
     def resampleLobe(self, position: torch.Tensor, normal: torch.Tensor, wi: torch.Tensor, roughness: torch.Tensor,
                      specular: torch.Tensor, sampler: PCG32Sampler, candidates: int = 8, alpha: float = 0.5, delta: float = 0.1,
@@ -769,25 +738,10 @@ class SDTree:
         (M, N)}.  The lanes' streams advance by the candidates' draws."""
         n = position.shape[1]
         _f32(position, (3, n)); _f32(normal, (3, n)); _f32(wi, (3, n)); _f32(roughness, (n,)); _f32(specular, (n,))
-        if sampler.n != n:
-            raise ValueError("the sampler must have one stream per lane")
-        m, mp = _mask(active, n)
-        M = int(candidates)
-        prm = N.pg_resample_params(M & 0xFFFFFFFF if M >= 0 else 0, float(alpha), float(delta), 0)
         a = N.pg_resample_lobe_args()
-        a.p, a.normal, a.wi, a.active = position.data_ptr(), normal.data_ptr(), wi.data_ptr(), mp
-        a.roughness, a.specular = roughness.data_ptr(), specular.data_ptr()
-        a.rng_state, a.rng_inc = sampler.state.data_ptr(), sampler.inc.data_ptr()
-        d, w = self._new(3, n), self._new(n)
-        info = {"target": self._new(n), "source": self._new(n), "index": self._new(n, dtype=torch.int32)}
-        a.dir_out, a.weight_out = d.data_ptr(), w.data_ptr()
-        a.target_out, a.source_out, a.index_out = info["target"].data_ptr(), info["source"].data_ptr(), info["index"].data_ptr()
-        if return_candidates and 1 <= M <= N.PG_RESAMPLE_MAX_CANDIDATES:  # (any other M is refused below, before a launch)
-            info["cand_dir"], info["cand_target"], info["cand_source"] = self._new(M, 3, n), self._new(M, n), self._new(M, n)
-            a.cand_dir_out = info["cand_dir"].data_ptr()
-            a.cand_target_out, a.cand_source_out = info["cand_target"].data_ptr(), info["cand_source"].data_ptr()
-        self._ck(self._lib.pg_resample_lobe(self._h, n, C.byref(prm), C.byref(a), _stream_ptr()))
-        return d, w, info
+        a.wi, a.roughness, a.specular = wi.data_ptr(), roughness.data_ptr(), specular.data_ptr()
+        return self._resample(self._lib.pg_resample_lobe, a, (N.pg_resample_params, float(alpha), float(delta), 0),
+                              position, normal, sampler, candidates, active, return_candidates)
 
     def resampleInterface(self, position: torch.Tensor, normal: torch.Tensor, wi: torch.Tensor, roughness: torch.Tensor,
                           eta: torch.Tensor, sampler: PCG32Sampler, candidates: int = 8, alpha: float = 0.5, delta: float = 0.1,
@@ -808,26 +762,12 @@ class SDTree:
         streams advance by the candidates' draws."""
         n = position.shape[1]
         _f32(position, (3, n)); _f32(normal, (3, n)); _f32(wi, (3, n)); _f32(roughness, (n,)); _f32(eta, (n,))
-        if sampler.n != n:
-            raise ValueError("the sampler must have one stream per lane")
-        m, mp = _mask(active, n)
-        M = int(candidates)
-        prm = N.pg_resample_params(M & 0xFFFFFFFF if M >= 0 else 0, float(alpha), float(delta), 0)
         a = N.pg_resample_interface_args()
-        a.p, a.normal, a.wi, a.active = position.data_ptr(), normal.data_ptr(), wi.data_ptr(), mp
-        a.roughness, a.eta = roughness.data_ptr(), eta.data_ptr()
-        a.rng_state, a.rng_inc = sampler.state.data_ptr(), sampler.inc.data_ptr()
-        d, w = self._new(3, n), self._new(n)
-        info = {"target": self._new(n), "source": self._new(n), "index": self._new(n, dtype=torch.int32), "eta": self._new(n)}
-        a.dir_out, a.weight_out = d.data_ptr(), w.data_ptr()
-        a.target_out, a.source_out, a.index_out = info["target"].data_ptr(), info["source"].data_ptr(), info["index"].data_ptr()
-        a.eta_out = info["eta"].data_ptr()
-        if return_candidates and 1 <= M <= N.PG_RESAMPLE_MAX_CANDIDATES:  # (any other M is refused below, before a launch)
-            info["cand_dir"], info["cand_target"], info["cand_source"] = self._new(M, 3, n), self._new(M, n), self._new(M, n)
-            a.cand_dir_out = info["cand_dir"].data_ptr()
-            a.cand_target_out, a.cand_source_out = info["cand_target"].data_ptr(), info["cand_source"].data_ptr()
-        self._ck(self._lib.pg_resample_interface(self._h, n, C.byref(prm), C.byref(a), _stream_ptr()))
-        return d, w, info
+        a.wi, a.roughness, a.eta = wi.data_ptr(), roughness.data_ptr(), eta.data_ptr()
+        eta_out = self._new(n)
+        a.eta_out = eta_out.data_ptr()
+        return self._resample(self._lib.pg_resample_interface, a, (N.pg_resample_params, float(alpha), float(delta), 0),
+                              position, normal, sampler, candidates, active, return_candidates, more={"eta": eta_out})
 
     def exportPassRecords(self, slot: int = 0) -> Dict[str, torch.Tensor]:
         """The kept path-vertex records of the most recent render pass of buffer set `slot` (pg_render_export_records): a
@@ -845,6 +785,33 @@ class SDTree:
         self._ck(self._lib.pg_render_export_records(self._h, int(slot), C.byref(o), out["slot"].data_ptr() or None,
                                                     out["count"].data_ptr(), _stream_ptr()))
         return out
+
+    def _resample(self, fn, a, params, position, normal, sampler, candidates, active, return_candidates, more=None,
+                  lead=(("cand_dir", torch.float32, 3),)):
+        """What the four resampled calls share (csrc/pg_ris_dev.hpp), whose argument structs name these members alike: fills
+        `a` with position, normal and the lane mask, the stream pointers, and fresh dir_out, weight_out and info's "target",
+        "source", "index" (then `more`, outputs the caller has set itself); under return_candidates the candidate arrays,
+        `lead` -- (key, dtype, shape of one candidate's entry of a lane) of those in front -- then "cand_target" and
+        "cand_source", each filling the member key + "_out".  `params`: the parameter struct and its members behind
+        `candidates`.  Calls fn and returns (dir_out's tensor, weight, info)."""
+        n = position.shape[1]
+        if sampler.n != n:
+            raise ValueError("the sampler must have one stream per lane")
+        m, mp = _mask(active, n)  # (m lives until the call is made)
+        M = int(candidates)
+        prm = params[0](M & 0xFFFFFFFF if M >= 0 else 0, *params[1:])
+        a.p, a.normal, a.active = position.data_ptr(), normal.data_ptr(), mp
+        a.rng_state, a.rng_inc = sampler.state.data_ptr(), sampler.inc.data_ptr()
+        d, w = self._new(3, n), self._new(n)
+        info = {"target": self._new(n), "source": self._new(n), "index": self._new(n, dtype=torch.int32), **(more or {})}
+        a.dir_out, a.weight_out = d.data_ptr(), w.data_ptr()
+        a.target_out, a.source_out, a.index_out = info["target"].data_ptr(), info["source"].data_ptr(), info["index"].data_ptr()
+        if return_candidates and 1 <= M <= N.PG_RESAMPLE_MAX_CANDIDATES:  # (any other M is refused below, before a launch)
+            for key, dtype, *shape in lead + (("cand_target", torch.float32), ("cand_source", torch.float32)):
+                info[key] = self._new(M, *shape, n, dtype=dtype)
+                setattr(a, key + "_out", info[key].data_ptr())
+        self._ck(fn(self._h, n, C.byref(prm), C.byref(a), _stream_ptr()))
+        return d, w, info
 
     def _records_out(self, S: int, null=None):
         """The six columns addDataPropagate takes, fresh and S records long, and the pg_records_out that points at them (`null`:
